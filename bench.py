@@ -16,7 +16,12 @@ reads; `roofline.full_owner_map` times the public full-map forward beside it).  
 scaling, no data-path collective -- crops are independent); value =
 crops of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 (the driver's contract), with
+Prints ONE JSON line on rank 0 (the driver's contract).  A plain run sets up, warms up, times the K steps and
+prints the headline: metric, value (crops/s), unit, higher_is_better, dtype, ms_per_step (one timed step), the
+step counts and the config.  --dump-outputs DIR also writes what the last timed step handed its caller on rank 0,
+DIR/depth.npy [256,128,128] and DIR/grad_spheres.npy [256,41,4] (float32; the inputs are seeded, so two builds
+can be compared output for output).  --full adds everything else, each measured after the timed steps:
+  value_full_owner_map, strong   the same K steps with the public forward; the strong-scaling leg (N > 1)
   roofline      the dominant kernel's algorithmic HBM bytes / its MEAN launch
                 duration (HIP events on the launching stream) vs the 8 TB/s peak;
                 `large_batch` repeats it at 1152 and 9216 crops per launch (more
@@ -44,6 +49,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -748,8 +754,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--launch", choices=["direct", "graph"], default="direct",
                     help="direct: two C-ABI calls per step; graph: one hipGraph replay per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the large-batch and secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: launch means and roofline, the public-forward "
+                         "region, the strong-scaling leg, large batches, secondary kernels, collectives, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the large-batch and secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` started plainly (no launcher in front of it): start the N ranks here, exactly as the
@@ -850,129 +861,101 @@ def main():
         owner.fill_(254)
         fwd(sh)
         stream.synchronize()
-        owner_written = float((owner != 254).float().mean())
+        owner_written = float((owner != 254).float().mean()) if args.full else None
         t0 = time.perf_counter()
         while (time.perf_counter() - t0) * 1e3 < CLOCK_WARMUP_MS:
             for _ in range(50):
                 step()
             stream.synchronize()
         elapsed = timed_steps(step, args.steps, args.warmup, dist, dev)
+        # what the last timed step handed its caller (the owner map never leaves the pair), copied on the device before
+        # --full's measurements overwrite these buffers; written out at the end
+        outputs = None
+        if args.dump_outputs and rank == 0:
+            outputs = {"depth": depth.clone(), "grad_spheres": gsph.clone()}
+            stream.synchronize()                        # (copied back on the default stream below)
+        big = sec = strong = None
+        if args.full:
+            def kernel_us(fn, reps=200, batches=5, warm=20):
+                return mean_launch_us(fn, stream, reps, batches, warm)
+            fwd_us = kernel_us(fwd)
+            bwd_us = kernel_us(bwd)
+            fwd_full_us = kernel_us(fwd_full)
+            # context for the roofline: what ONE plain fill launch of the depth output (16.8 of the
+            # forward's 21.1 MB, no arithmetic, same stream) takes at this batch size -- the practical
+            # ceiling of any kernel that has to write a 256-crop batch per launch
+            fill_us = kernel_us(lambda _s: depth.fill_(100.0))
+            # the launch floor of the forward's shape (one 1024-thread workgroup with the whole CU's LDS per crop) over
+            # the forward's bytes: records in, depth + the touched rows' owner bytes out, nothing else (capi.hip)
+            rows_t = int(round(owner_written * S))
+            floor_lds = 160 * 1024
+            r0f = (S - rows_t) // 2
 
-        def kernel_us(fn, reps=200, batches=5, warm=20):
-            return mean_launch_us(fn, stream, reps, batches, warm)
-        fwd_us = kernel_us(fwd)
-        bwd_us = kernel_us(bwd)
-        fwd_full_us = kernel_us(fwd_full)
-        # context for the roofline: what ONE plain fill launch of the depth output (16.8 of the
-        # forward's 21.1 MB, no arithmetic, same stream) takes at this batch size -- the practical
-        # ceiling of any kernel that has to write a 256-crop batch per launch
-        fill_us = kernel_us(lambda _s: depth.fill_(100.0))
-        # the launch floor of the forward's shape (one 1024-thread workgroup with the whole CU's LDS per crop) over
-        # the forward's bytes: records in, depth + the touched rows' owner bytes out, nothing else (capi.hip)
-        rows_t = int(round(owner_written * S))
-        floor_lds = 160 * 1024
-        r0f = (S - rows_t) // 2
-
-        def floor(s):
-            _lib.check(lib.shr_selftest_launch_floor(sp, BATCH, J, S, S, r0f, r0f + rows_t, dp, ap, floor_lds, s), "floor")
-        floor_us = kernel_us(floor)
-        # the same K steps with the PUBLIC forward (complete owner map), timed like the headline
-        def step_full():
-            fwd_full(sh); bwd(sh)
-        # (the same clock warm-up as the headline region: this one follows a run of single-kernel loops and read 13.5 M on
-        # the driver's box against 16.7 M here in round 4 -- a cold region, not a slower step)
-        t0 = time.perf_counter()
-        while (time.perf_counter() - t0) * 1e3 < CLOCK_WARMUP_MS:
-            for _ in range(50):
-                step_full()
-            stream.synchronize()
-        elapsed_full = timed_steps(step_full, args.steps, args.warmup, dist, dev)
-        # STRONG-scaling leg: BASELINE's batch of 256 crops split over the ranks (256 / N each, the same step, max-over-ranks
-        # time) -- the metric as BASELINE.json words it ("batch 256 ... at 1/2/4/8 MI355X"); at N = 1 it IS the headline.
-        strong = None
-        if world > 1 or dist is not None:
-            n_strong = max(1, BATCH // world)
-            sp_s, gp_s = spheres[:n_strong].contiguous(), grad[:n_strong].contiguous()
-            d_s, o_s, g_s = depth[:n_strong], owner[:n_strong], gsph[:n_strong]
-            ps = [t.data_ptr() for t in (sp_s, gp_s, d_s, g_s, o_s)]
-
-            def step_strong():
-                _lib.check(lib.shr_sphere_raster_fwd_ex(ps[0], n_strong, J, S, S, ps[2], ps[4], OWNER_TOUCHED_ROWS, sh), "fwd")
-                _lib.check(lib.shr_sphere_raster_bwd(ps[0], ps[1], ps[4], n_strong, J, S, S, ps[3], sh), "bwd")
+            def floor(s):
+                _lib.check(lib.shr_selftest_launch_floor(sp, BATCH, J, S, S, r0f, r0f + rows_t, dp, ap, floor_lds, s), "floor")
+            floor_us = kernel_us(floor)
+            # the same K steps with the PUBLIC forward (complete owner map), timed like the headline
+            def step_full():
+                fwd_full(sh); bwd(sh)
+            # (the same clock warm-up as the headline region: this one follows a run of single-kernel loops and read 13.5 M on
+            # the driver's box against 16.7 M here in round 4 -- a cold region, not a slower step)
             t0 = time.perf_counter()
             while (time.perf_counter() - t0) * 1e3 < CLOCK_WARMUP_MS:
                 for _ in range(50):
-                    step_strong()
+                    step_full()
                 stream.synchronize()
-            el_s = timed_steps(step_strong, args.steps, args.warmup, dist, dev)
-            strong = {"value": round(world * n_strong * args.steps / el_s, 1), "unit": "crops/s", "crops_per_rank": n_strong,
-                      "global_batch": world * n_strong, "ms_per_step": round(el_s / args.steps * 1e3, 6)}
-        big = sec = None
-        if rank == 0 and world == 1 and dist is None and not args.no_secondary:
-            # one hipGraph replay of the headline step (forward + backward as one graph launch)
-            g2 = torch.cuda.CUDAGraph()
-            fwd(sh); bwd(sh); stream.synchronize()
-            with torch.cuda.graph(g2, stream=stream):
-                fwd(sh); bwd(sh)
-            graph_us = mean_launch_us(lambda _s: g2.replay(), stream, 200, 3, 20)
-            # what a graph launch costs by itself: EIGHT steps in one graph, per step -- the difference to the one-step
-            # graph is the fixed cost of a hipGraphLaunch on this runtime (a submission of its own with its barrier
-            # packets, where direct launches pipeline in the queue), not the kernels
-            g8 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g8, stream=stream):
-                for _ in range(8):
+            elapsed_full = timed_steps(step_full, args.steps, args.warmup, dist, dev)
+            # STRONG-scaling leg: BASELINE's batch of 256 crops split over the ranks (256 / N each, the same step, max-over-ranks
+            # time) -- the metric as BASELINE.json words it ("batch 256 ... at 1/2/4/8 MI355X"); at N = 1 it IS the headline.
+            if world > 1 or dist is not None:
+                n_strong = max(1, BATCH // world)
+                sp_s, gp_s = spheres[:n_strong].contiguous(), grad[:n_strong].contiguous()
+                d_s, o_s, g_s = depth[:n_strong], owner[:n_strong], gsph[:n_strong]
+                ps = [t.data_ptr() for t in (sp_s, gp_s, d_s, g_s, o_s)]
+
+                def step_strong():
+                    _lib.check(lib.shr_sphere_raster_fwd_ex(ps[0], n_strong, J, S, S, ps[2], ps[4], OWNER_TOUCHED_ROWS, sh), "fwd")
+                    _lib.check(lib.shr_sphere_raster_bwd(ps[0], ps[1], ps[4], n_strong, J, S, S, ps[3], sh), "bwd")
+                t0 = time.perf_counter()
+                while (time.perf_counter() - t0) * 1e3 < CLOCK_WARMUP_MS:
+                    for _ in range(50):
+                        step_strong()
+                    stream.synchronize()
+                el_s = timed_steps(step_strong, args.steps, args.warmup, dist, dev)
+                strong = {"value": round(world * n_strong * args.steps / el_s, 1), "unit": "crops/s", "crops_per_rank": n_strong,
+                          "global_batch": world * n_strong, "ms_per_step": round(el_s / args.steps * 1e3, 6)}
+            if rank == 0 and world == 1 and dist is None and not args.no_secondary:
+                # one hipGraph replay of the headline step (forward + backward as one graph launch)
+                g2 = torch.cuda.CUDAGraph()
+                fwd(sh); bwd(sh); stream.synchronize()
+                with torch.cuda.graph(g2, stream=stream):
                     fwd(sh); bwd(sh)
-            graph8_us = mean_launch_us(lambda _s: g8.replay(), stream, 50, 3, 5) / 8.0
-            del g8
-            big = large_batch(lib, _lib, dev, stream)
-            sec = secondary(lib, _lib, dev, stream, graph_us)
-            sec["headline_step_in_a_graph_of_8_steps_us"] = round(graph8_us, 3)
+                graph_us = mean_launch_us(lambda _s: g2.replay(), stream, 200, 3, 20)
+                # what a graph launch costs by itself: EIGHT steps in one graph, per step -- the difference to the one-step
+                # graph is the fixed cost of a hipGraphLaunch on this runtime (a submission of its own with its barrier
+                # packets, where direct launches pipeline in the queue), not the kernels
+                g8 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g8, stream=stream):
+                    for _ in range(8):
+                        fwd(sh); bwd(sh)
+                graph8_us = mean_launch_us(lambda _s: g8.replay(), stream, 50, 3, 5) / 8.0
+                del g8
+                big = large_batch(lib, _lib, dev, stream)
+                sec = secondary(lib, _lib, dev, stream, graph_us)
+                sec["headline_step_in_a_graph_of_8_steps_us"] = round(graph8_us, 3)
 
     coll = None
-    if dist is not None and not args.no_secondary:
+    if args.full and dist is not None and not args.no_secondary:
         try:                                                  # (the headline line is printed whatever happens here)
             coll = collective_secondary(dist, rank, world, dev)   # every rank takes part; rank 0 prints
         except Exception as e:                                # noqa: BLE001
             coll = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
     if rank == 0:
-        # algorithmic bytes ("u8 argmin saved" variant: 165 808 B/crop fwd+bwd @128):
-        #   fwd writes depth f32 + owner u8, reads the spheres; bwd reads grad f32 + owner u8 +
-        #   spheres, writes grad_spheres
-        #   (forward with SHR_RASTER_OWNER_TOUCHED_ROWS: the owner bytes of the touched rows only -- the measured
-        #   fraction; the backward is priced at the whole images although it reads the touched rows only)
-        # Three byte conventions, each applied to BOTH directions and named in the line:
-        #   touched   depth / grad image + the owner bytes of the touched rows (what this pair has to move) + records
-        #   full      ... + the complete owner map (the public argmin contract; SURVEY 8d "u8 argmin saved")
-        #   survey8d  SURVEY 8d's primary figure: no owner map at all (66 192 + 66 848 B per crop)
-        bytes_fwd = int(BATCH * (4 * S * S + owner_written * S * S + 16 * J))
-        bytes_bwd = int(BATCH * (4 * S * S + owner_written * S * S + 16 * J + 16 * J))
-        bytes_fwd_full = BATCH * (4 * S * S + S * S + 16 * J)
-        bytes_bwd_full = BATCH * (4 * S * S + S * S + 16 * J + 16 * J)
-        bytes_fwd_8d = BATCH * (4 * S * S + 16 * J)
-        bytes_bwd_8d = BATCH * (4 * S * S + 16 * J + 16 * J)
-        dom, dom_us, dom_bytes = ("sphere_zbuf_bwd_kernel", bwd_us, bytes_bwd) if bwd_us >= fwd_us else \
-            ("sphere_zbuf_fwd_kernel", fwd_us, bytes_fwd)
-        achieved = dom_bytes / (dom_us * 1e-6) / 1e9
-        traffic, traffic_src = pmc_traffic(dom)
-        rp = rocprof_avg_us()
-        frac_rocprof = None
-        if rp is not None and "launched_from_c" in rp:      # the committed rocprofv3 summary of the C-loop launches
-            key = "bwd" if dom.endswith("bwd_kernel") else "fwd"
-            frac_rocprof = {"frac": roof(dom_bytes, rp["launched_from_c"][key])["frac"],
-                            "frac_fwd": roof(bytes_fwd, rp["launched_from_c"]["fwd"])["frac"],
-                            "frac_bwd": roof(bytes_bwd, rp["launched_from_c"]["bwd"])["frac"],
-                            "avg_us": {"fwd": rp["launched_from_c"]["fwd"], "bwd": rp["launched_from_c"]["bwd"]},
-                            "source": rp["launched_from_c"]["source"],
-                            "is": "same algorithmic bytes / AverageNs of the committed rocprofv3 --kernel-trace --stats "
-                                  "run of the C-loop launches (tools/collect_profiles_r06.sh); a different process "
-                                  "than this line's live HIP-event means"}
         out = {
             "metric": "depth crops/s (raster fwd+bwd, 128x128, batch 256)",
             "value": round(world * BATCH * args.steps / elapsed, 1),
-            "value_full_owner_map": round(world * BATCH * args.steps / elapsed_full, 1),
             "value_is": "forward with SHR_RASTER_OWNER_TOUCHED_ROWS + backward: the pair ops.SphereDepthRaster issues "
-                        "(the owner map never leaves it); value_full_owner_map = the same steps with the public "
-                        "forward that completes the uint8 owner map (round 2's definition of the step)",
+                        "(the owner map never leaves it)",
             "unit": "crops/s",
             "n_gpus": world,
             "steps": args.steps,
@@ -980,12 +963,6 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 6),
             "higher_is_better": True,
             "scaling": "weak",
-            # the same metric with BASELINE's batch of 256 SPLIT over the ranks (256 / N crops each; N = 1: the headline itself)
-            "strong": strong if strong is not None else {"value": round(world * BATCH * args.steps / elapsed, 1), "unit": "crops/s",
-                                                         "crops_per_rank": BATCH, "global_batch": BATCH,
-                                                         "ms_per_step": round(elapsed / args.steps * 1e3, 6)},
-            "strong_is": "strong scaling: a global batch of 256 crops, 256 / N per rank, max-over-ranks time of the same K steps; "
-                         "`value` is weak scaling (256 crops per rank)",
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
@@ -995,56 +972,101 @@ def main():
                        "launch": args.launch, "clock_warmup_ms": CLOCK_WARMUP_MS,
                        "parallelism": "batch-sharded x%d, no data-path collective" % world,
                        "rccl_ranks": rccl_ranks, "backend": dist.get_backend() if dist is not None else None},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": dom_bytes,
-                         "launch_us": {"fwd": round(fwd_us, 3), "bwd": round(bwd_us, 3)},
-                         "launch_us_is": "mean of 1000 back-to-back launches (HIP events on the launching stream, this "
-                                         "process); `frac` uses it.  rocprof_avg_us = AverageNs of the committed "
-                                         "rocprofv3 --kernel-trace --stats run of this command (the tracer "
-                                         "serialises the dispatches and, from Python, the host then costs more per "
-                                         "launch than the kernel takes; launched_from_c = the same launches from a C "
-                                         "loop under the tracer: profiles/README.md)",
-                         "rocprof_avg_us": rp,
-                         "frac_rocprof": frac_rocprof,
-                         "owner_map": "touched rows only (SHR_RASTER_OWNER_TOUCHED_ROWS): %.1f %% of the owner bytes"
-                                      % (100 * owner_written),
-                         "full_owner_map": dict(fwd_us=round(fwd_full_us, 3), **roof(bytes_fwd_full, fwd_full_us)),
-                         "frac_fwd": roof(bytes_fwd, fwd_us)["frac"], "frac_bwd": roof(bytes_bwd, bwd_us)["frac"],
-                         "byte_conventions": {
-                             "touched_rows": {"fwd_bytes": bytes_fwd, "bwd_bytes": bytes_bwd,
-                                              "frac_fwd": roof(bytes_fwd, fwd_us)["frac"],
-                                              "frac_bwd": roof(bytes_bwd, bwd_us)["frac"],
-                                              "is": "depth / grad image + owner bytes of the touched rows + records; "
-                                                    "`frac`, `frac_fwd`, `frac_bwd` use it"},
-                             "full_owner_map": {"fwd_bytes": bytes_fwd_full, "bwd_bytes": bytes_bwd_full,
-                                                "frac_fwd": roof(bytes_fwd_full, fwd_full_us)["frac"],
-                                                "frac_bwd": roof(bytes_bwd_full, bwd_us)["frac"],
-                                                "is": "SURVEY 8d 'u8 argmin saved' (165 808 B per crop fwd + bwd); the "
-                                                      "forward timed is the public one that writes the whole map"},
-                             "survey8d_no_owner_map": {"fwd_bytes": bytes_fwd_8d, "bwd_bytes": bytes_bwd_8d,
-                                                       "frac_fwd": roof(bytes_fwd_8d, fwd_us)["frac"],
-                                                       "frac_bwd": roof(bytes_bwd_8d, bwd_us)["frac"],
-                                                       "is": "SURVEY 8d's primary 133 040 B per crop (argmin recomputed): "
-                                                             "the owner bytes these kernels do move are not counted"}},
-                         "launch_floor": {"us": round(floor_us, 3), "fwd_over_floor": round(fwd_us / floor_us, 3),
-                                          "bytes": bytes_fwd,
-                                          "shape": "%d workgroups x 1024 threads, %d B of LDS each (one per CU), 16-byte "
-                                                   "sc1 stores of depth + the owner bytes of %d rows, the records read: "
-                                                   "no arithmetic (shr_selftest_launch_floor)" % (BATCH, floor_lds, rows_t),
-                                          **{k: v for k, v in roof(bytes_fwd, floor_us).items() if k in ("achieved", "frac")}},
-                         "plain_fill_of_the_depth_output_us": round(fill_us, 3),
-                         "timeline": headline_timeline()},
         }
-        if big is not None:
-            out["roofline"]["large_batch"] = big
-        if sec is not None:
-            out["secondary"] = sec
-        if coll is not None:
-            out["secondary"] = coll
-        if world == 1 and dist is None and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(spheres.cpu().numpy(), grad.cpu().numpy())
+        if args.full:
+            # algorithmic bytes ("u8 argmin saved" variant: 165 808 B/crop fwd+bwd @128):
+            #   fwd writes depth f32 + owner u8, reads the spheres; bwd reads grad f32 + owner u8 +
+            #   spheres, writes grad_spheres
+            #   (forward with SHR_RASTER_OWNER_TOUCHED_ROWS: the owner bytes of the touched rows only -- the measured
+            #   fraction; the backward is priced at the whole images although it reads the touched rows only)
+            # Three byte conventions, each applied to BOTH directions and named in the line:
+            #   touched   depth / grad image + the owner bytes of the touched rows (what this pair has to move) + records
+            #   full      ... + the complete owner map (the public argmin contract; SURVEY 8d "u8 argmin saved")
+            #   survey8d  SURVEY 8d's primary figure: no owner map at all (66 192 + 66 848 B per crop)
+            bytes_fwd = int(BATCH * (4 * S * S + owner_written * S * S + 16 * J))
+            bytes_bwd = int(BATCH * (4 * S * S + owner_written * S * S + 16 * J + 16 * J))
+            bytes_fwd_full = BATCH * (4 * S * S + S * S + 16 * J)
+            bytes_bwd_full = BATCH * (4 * S * S + S * S + 16 * J + 16 * J)
+            bytes_fwd_8d = BATCH * (4 * S * S + 16 * J)
+            bytes_bwd_8d = BATCH * (4 * S * S + 16 * J + 16 * J)
+            dom, dom_us, dom_bytes = ("sphere_zbuf_bwd_kernel", bwd_us, bytes_bwd) if bwd_us >= fwd_us else \
+                ("sphere_zbuf_fwd_kernel", fwd_us, bytes_fwd)
+            achieved = dom_bytes / (dom_us * 1e-6) / 1e9
+            traffic, traffic_src = pmc_traffic(dom)
+            rp = rocprof_avg_us()
+            frac_rocprof = None
+            if rp is not None and "launched_from_c" in rp:      # the committed rocprofv3 summary of the C-loop launches
+                key = "bwd" if dom.endswith("bwd_kernel") else "fwd"
+                frac_rocprof = {"frac": roof(dom_bytes, rp["launched_from_c"][key])["frac"],
+                                "frac_fwd": roof(bytes_fwd, rp["launched_from_c"]["fwd"])["frac"],
+                                "frac_bwd": roof(bytes_bwd, rp["launched_from_c"]["bwd"])["frac"],
+                                "avg_us": {"fwd": rp["launched_from_c"]["fwd"], "bwd": rp["launched_from_c"]["bwd"]},
+                                "source": rp["launched_from_c"]["source"],
+                                "is": "same algorithmic bytes / AverageNs of the committed rocprofv3 --kernel-trace --stats "
+                                      "run of the C-loop launches (tools/collect_profiles_r06.sh); a different process "
+                                      "than this line's live HIP-event means"}
+            out["value_full_owner_map"] = round(world * BATCH * args.steps / elapsed_full, 1)
+            out["value_is"] += ("; value_full_owner_map = the same steps with the public forward that completes the uint8 "
+                                "owner map (round 2's definition of the step)")
+            # the same metric with BASELINE's batch of 256 SPLIT over the ranks (256 / N crops each; N = 1: the headline itself)
+            out["strong"] = strong if strong is not None else {"value": round(world * BATCH * args.steps / elapsed, 1),
+                                                               "unit": "crops/s", "crops_per_rank": BATCH, "global_batch": BATCH,
+                                                               "ms_per_step": round(elapsed / args.steps * 1e3, 6)}
+            out["strong_is"] = ("strong scaling: a global batch of 256 crops, 256 / N per rank, max-over-ranks time of the same "
+                                "K steps; `value` is weak scaling (256 crops per rank)")
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                               "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": dom_bytes,
+                               "launch_us": {"fwd": round(fwd_us, 3), "bwd": round(bwd_us, 3)},
+                               "launch_us_is": "mean of 1000 back-to-back launches (HIP events on the launching stream, this "
+                                               "process); `frac` uses it.  rocprof_avg_us = AverageNs of the committed "
+                                               "rocprofv3 --kernel-trace --stats run of this command (the tracer "
+                                               "serialises the dispatches and, from Python, the host then costs more per "
+                                               "launch than the kernel takes; launched_from_c = the same launches from a C "
+                                               "loop under the tracer: profiles/README.md)",
+                               "rocprof_avg_us": rp,
+                               "frac_rocprof": frac_rocprof,
+                               "owner_map": "touched rows only (SHR_RASTER_OWNER_TOUCHED_ROWS): %.1f %% of the owner bytes"
+                                            % (100 * owner_written),
+                               "full_owner_map": dict(fwd_us=round(fwd_full_us, 3), **roof(bytes_fwd_full, fwd_full_us)),
+                               "frac_fwd": roof(bytes_fwd, fwd_us)["frac"], "frac_bwd": roof(bytes_bwd, bwd_us)["frac"],
+                               "byte_conventions": {
+                                   "touched_rows": {"fwd_bytes": bytes_fwd, "bwd_bytes": bytes_bwd,
+                                                    "frac_fwd": roof(bytes_fwd, fwd_us)["frac"],
+                                                    "frac_bwd": roof(bytes_bwd, bwd_us)["frac"],
+                                                    "is": "depth / grad image + owner bytes of the touched rows + records; "
+                                                          "`frac`, `frac_fwd`, `frac_bwd` use it"},
+                                   "full_owner_map": {"fwd_bytes": bytes_fwd_full, "bwd_bytes": bytes_bwd_full,
+                                                      "frac_fwd": roof(bytes_fwd_full, fwd_full_us)["frac"],
+                                                      "frac_bwd": roof(bytes_bwd_full, bwd_us)["frac"],
+                                                      "is": "SURVEY 8d 'u8 argmin saved' (165 808 B per crop fwd + bwd); the "
+                                                            "forward timed is the public one that writes the whole map"},
+                                   "survey8d_no_owner_map": {"fwd_bytes": bytes_fwd_8d, "bwd_bytes": bytes_bwd_8d,
+                                                             "frac_fwd": roof(bytes_fwd_8d, fwd_us)["frac"],
+                                                             "frac_bwd": roof(bytes_bwd_8d, bwd_us)["frac"],
+                                                             "is": "SURVEY 8d's primary 133 040 B per crop (argmin recomputed): "
+                                                                   "the owner bytes these kernels do move are not counted"}},
+                               "launch_floor": {"us": round(floor_us, 3), "fwd_over_floor": round(fwd_us / floor_us, 3),
+                                                "bytes": bytes_fwd,
+                                                "shape": "%d workgroups x 1024 threads, %d B of LDS each (one per CU), 16-byte "
+                                                         "sc1 stores of depth + the owner bytes of %d rows, the records read: "
+                                                         "no arithmetic (shr_selftest_launch_floor)" % (BATCH, floor_lds, rows_t),
+                                                **{k: v for k, v in roof(bytes_fwd, floor_us).items() if k in ("achieved", "frac")}},
+                               "plain_fill_of_the_depth_output_us": round(fill_us, 3),
+                               "timeline": headline_timeline()}
+            if big is not None:
+                out["roofline"]["large_batch"] = big
+            if sec is not None:
+                out["secondary"] = sec
+            if coll is not None:
+                out["secondary"] = coll
+            if world == 1 and dist is None and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(spheres.cpu().numpy(), grad.cpu().numpy())
+        if outputs is not None:                    # after the timed steps: costs nothing the line reports
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy().astype(np.float32))
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -20,7 +20,7 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, SHR_BENCH_BACKEND="gloo", SHR_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2",
                SHR_BENCH_DDP_STEPS="3")
     from conftest import run_torchrun
-    out = run_torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10"], env=env,
+    out = run_torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10", "--full"], env=env,
                        timeout=600, capture=True)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out                               # rank 0 prints ONE line
@@ -42,7 +42,7 @@ def test_bench_one_rank_over_rccl():
     gradient-bucket all-reduce and the DDP-wrapped training step all run through RCCL on the MI355X."""
     env = dict(os.environ, SHR_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", SHR_BENCH_DDP_STEPS="3")
     from conftest import run_torchrun
-    out = run_torchrun(1, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10"], env=env,
+    out = run_torchrun(1, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10", "--full"], env=env,
                        timeout=600, capture=True)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out
@@ -64,7 +64,7 @@ def test_bench_starts_its_own_ranks():
                SHR_BENCH_DDP_STEPS="2")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -76,6 +76,37 @@ def test_bench_starts_its_own_ranks():
     assert d["scaling"] == "weak" and d["strong"]["crops_per_rank"] == 128 and d["strong"]["global_batch"] == 256
     assert abs(d["strong"]["value"] - 256 / (d["strong"]["ms_per_step"] * 1e-3)) <= 1e-3 * d["strong"]["value"]
     assert d["strong"]["value"] > 1e5
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line only, K timed steps.  --dump-outputs
+    writes what the last timed step handed its caller; on the same seeded inputs the same two launches through ops give
+    it bit for bit."""
+    import numpy as np
+    import torch
+    import bench
+    from conftest import bits
+    from spherehand_amd import ops
+    d_out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(d_out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "crops/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["metric"] == "depth crops/s (raster fwd+bwd, 128x128, batch 256)"
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for k in ("roofline", "secondary", "cpu_baseline", "strong", "value_full_owner_map"):
+        assert k not in d, k                                  # --full only
+    depth, gsph = np.load(d_out / "depth.npy"), np.load(d_out / "grad_spheres.npy")
+    assert depth.dtype == gsph.dtype == np.float32 and depth.shape == (256, 128, 128) and gsph.shape == (256, 41, 4)
+    with torch.random.fork_rng(devices=[]):                   # make_inputs seeds torch's CPU generator
+        spheres, grad = bench.make_inputs(0, torch.device("cuda:0"))
+    ref_d, owner = ops.sphere_raster_fwd(spheres, 128, 128, want_argmin=True, flags=ops.RASTER_OWNER_TOUCHED_ROWS)
+    ref_g = ops.sphere_raster_bwd(spheres, grad, owner)
+    assert np.array_equal(bits(depth), bits(ref_d.cpu().numpy()))
+    assert np.array_equal(bits(gsph), bits(ref_g.cpu().numpy()))
 
 
 def test_bench_rejects_a_world_size_mismatch():

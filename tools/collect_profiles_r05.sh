@@ -5,10 +5,10 @@ set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05; rm -rf "$O"; mkdir -p "$O"
 # (a) the headline kernels over >= 2000 steps: stats summary + per-launch trace (medians)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_headline" -o bench -- python bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-secondary > "$O/stats_headline.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats_headline" -o bench -- python bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline --no-secondary > "$O/stats_headline.log" 2>&1
 # (b) the same tracing over the full bench (secondary set)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o bench -- python bench.py --steps 300 --warmup 30 --no-cpu-baseline > "$O/stats.log" 2>&1
-BS="python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o bench -- python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline > "$O/stats.log" 2>&1
+BS="python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -o bench -- $BS > "$O/pmc_fetch.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -o bench -- $BS > "$O/pmc_write.log" 2>&1
 SQA="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU"
@@ -16,8 +16,8 @@ SQB="SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_IN
 timeout 300 rocprofv3 --kernel-trace --pmc $SQA --output-format csv -d "$O/sq_a_raster" -o bench -- $BS > "$O/sq_a_raster.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc $SQB --output-format csv -d "$O/sq_b_raster" -o bench -- $BS > "$O/sq_b_raster.log" 2>&1
 export SHR_BENCH_SKIP_TRAIN=1
-timeout 400 rocprofv3 --kernel-trace --pmc $SQA --output-format csv -d "$O/sq_a_secondary" -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/sq_a_secondary.log" 2>&1
-timeout 400 rocprofv3 --kernel-trace --pmc $SQB --output-format csv -d "$O/sq_b_secondary" -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/sq_b_secondary.log" 2>&1
+timeout 400 rocprofv3 --kernel-trace --pmc $SQA --output-format csv -d "$O/sq_a_secondary" -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/sq_a_secondary.log" 2>&1
+timeout 400 rocprofv3 --kernel-trace --pmc $SQB --output-format csv -d "$O/sq_b_secondary" -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/sq_b_secondary.log" 2>&1
 unset SHR_BENCH_SKIP_TRAIN
 for S in 128 256; do
   S=$S REPS=10 timeout 300 rocprofv3 --kernel-trace --pmc $SQA --output-format csv -d "$O/sq_a_d2m$S" -o d2m -- python tools/prof_d2m.py > "$O/sq_a_d2m$S.log" 2>&1
@@ -48,9 +48,9 @@ timeout 200 python tools/bench_mvloss_graph.py > "$O/mvloss_graph.log" 2>&1
 timeout 200 python tools/prof_cloop.py > "$O/cloop_plain.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/cloop" -o cloop -- python tools/prof_cloop.py > "$O/cloop_traced.log" 2>&1
 # (c) the unprofiled lines: the default run, the driver's short run, the graph variant
-timeout 500 python bench.py > "$O/bench_line.json" 2> "$O/bench_line.err"
-timeout 300 python bench.py --steps 20 --warmup 5 > "$O/bench_line_steps20.json" 2>> "$O/bench_line.err"
-timeout 300 python bench.py --launch graph --no-secondary --no-cpu-baseline > "$O/bench_line_graph.json" 2>> "$O/bench_line.err"
+timeout 500 python bench.py --full > "$O/bench_line.json" 2> "$O/bench_line.err"
+timeout 300 python bench.py --full --steps 20 --warmup 5 > "$O/bench_line_steps20.json" 2>> "$O/bench_line.err"
+timeout 300 python bench.py --full --launch graph --no-secondary --no-cpu-baseline > "$O/bench_line_graph.json" 2>> "$O/bench_line.err"
 # (d) the fuzzer on these kernels: FUZZ_SECONDS per family (default 45)
 timeout 1200 python tools/fuzz.py ${FUZZ_SECONDS:-45} 3 > "$O/fuzz.log" 2>&1
 python tools/summarize_r05.py gpurun_out/r05_profiles > "$O/summarize.log" 2>&1
