@@ -446,6 +446,32 @@ int shr_mesh_render_fwd(const float *T, int B, int NB, int NV, const int32_t *sk
                         float fx, float fy, const float *rand_f, const int32_t *faces, int F, int src_size,
                         int S, float clamp_max, float *vertices_ws, float *depth, void *stream);
 
+/* Differentiable DepthRender / DepthRasterization (the reference defines no backward for the mesh path,
+ * mesh/render.py:282-287).  The gradient routes to each bilinear tap's OWNER face and holds coverage fixed, as the sphere
+ * backward does: no edge, silhouette or visibility terms.  Square S <= src_size / 2 only (SHR_ETOOLARGE otherwise).
+ *   shr_mesh_depth_owner_fwd   shr_mesh_depth_fwd's arguments and depth[B,S,S] bits, plus owner[B,S,S,4] int32 (16-byte
+ *                              aligned): the face of each of the output pixel's four ATen taps (y0x0, y0x1, y1x0, y1x1) --
+ *                              the smallest offered depth at that source pixel of the raster (.cu:97-110), ties to the
+ *                              smallest face index; -1 for background, zero-weight taps and taps whose raw depth is above
+ *                              clamp_max (mesh/render.py:286: torch's clamp passes the gradient at equality).
+ *   shr_mesh_depth_bwd         grad_depth[B,S,S] + the owners + vertices[B,NV,4] (the forward's) -> grad_vertices[B,NV,4] =
+ *                              (d/du, d/dv, d/dz, 0): per tap, bilinear weight x d zp / d (the owner's three corners) of
+ *                              .cu:57-110 (a weight clamped strictly outside [0, 1] contributes nothing).  64-bit
+ *                              fixed-point sums in a per-crop unit computed on the device: bitwise reproducible,
+ *                              independent of the batch, no host synchronisation.  workspace: 16-byte aligned,
+ *                              shr_mesh_depth_bwd_workspace_bytes(B, NV) bytes, cleared by the call itself.
+ *   shr_lbs_project_bwd        shr_lbs_project's backward (project = 1, mesh/pointTransformation.py:39-46, :84-99):
+ *                              grad_vertices[B,NV,4] -> grad_T[B,NB,4,4]; rand_f gets no gradient.  Fixed summation
+ *                              order (bitwise reproducible, independent of the batch). */
+int shr_mesh_depth_owner_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int src_size, int S,
+                             float clamp_max, float *depth, int32_t *owner, void *stream);
+long long shr_mesh_depth_bwd_workspace_bytes(int B, int NV);
+int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, const int32_t *owner, const float *grad_depth, int B,
+                       int NV, int F, int src_size, int S, float *grad_vertices, void *workspace, void *stream);
+int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
+                        const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy, float fx,
+                        float fy, const float *rand_f, float *grad_T, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -21,6 +21,7 @@
 // input on which this differs from the reference chain is a raster value of -inf next to a
 // sampled pixel (an exactly zero 1/z denominator), where the reference's 0 * -inf is NaN.
 #include <cstdlib>
+#include <type_traits>
 
 #include "fk_rows.h"
 
@@ -178,11 +179,16 @@ __device__ __forceinline__ FaceRow face_row(const FaceSetup &fs) {
 // EXACT: the resize ratio R = src / S is an integer -- odd (SL = 1: output d samples source R d + (R - 1) / 2 with weight
 // 1) or even (SL = 2: sources R d + R / 2 - 1 and the next one, weights 1/2 each; lin_index's fma is exact in both
 // cases) -- and "the output pixels with a sample inside [lo, hi]" is a closed form instead of a loop over candidates.
-template <int TO, int SL, bool EXACT>
-__global__ void __launch_bounds__(1024)
-mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, int NV, int F, int src,
-                  int S, float clamp_max, float *__restrict__ depth) {
-  __shared__ uint32_t s_z[SL * TO][SL * TO + 1];   // [SL*dy + sy][SL*dx + sx], +1: bank spread
+// OWNER (shr_mesh_depth_owner_fwd, the differentiable DepthRender's forward): every slot is a 64-bit minimum
+// (key << 32 | face) -- the same depth key in the high word, ties to the smallest face index -- and the epilogue writes
+// the same depth bits plus owner[B,S,S,4] (the face of taps y0x0, y0x1, y1x0, y1x1; -1: background, clamped or zero
+// weight).  Twice the slot bytes: the launcher takes a smaller TO.
+template <int TO, int SL, bool EXACT, bool OWNER>
+__device__ __forceinline__ void
+mesh_depth_tile(const float4 *__restrict__ vertices, const int *__restrict__ faces, int NV, int F, int src,
+                int S, float clamp_max, float *__restrict__ depth, int *__restrict__ owner) {
+  typedef typename std::conditional<OWNER, unsigned long long, uint32_t>::type slot_t;
+  __shared__ slot_t s_z[SL * TO][SL * TO + 1];   // [SL*dy + sy][SL*dx + sx], +1: bank spread
   __shared__ int s_queue[kMeshQueue];
   __shared__ int s_wave_cnt[16], s_wave_rows[16], s_next_item;
   __shared__ FaceRow s_rows[kMeshRows];
@@ -194,7 +200,12 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
   const float4 *verts = vertices + (size_t)b * NV;
   MESH_STAMP(0);
 
+  if constexpr (OWNER) {   // 1000.0f, no face
+    for (int i = tid; i < SL * TO * (SL * TO + 1); i += blockDim.x)
+      (&s_z[0][0])[i] = ((unsigned long long)(0x447A0000u ^ 0x80000000u) << 32) | 0xFFFFFFFFull;
+  } else {
   for (int i = tid; i < SL * TO * (SL * TO + 1); i += blockDim.x) (&s_z[0][0])[i] = 0x447A0000u ^ 0x80000000u;  // 1000.0f
+  }
 
   // source range of the tile's slots (for the face/tile cull)
   const Lin tlx = lin_index(tx0, scale, src), thx = lin_index(min(tx0 + TO, S) - 1, scale, src);
@@ -308,8 +319,16 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
     }
     __syncthreads();
     MESH_STAMP(2);   // the scans are through, the survivors' rows are assigned
-    for (int r = tid; r < min(kMeshRows, total_rows); r += blockDim.x)
+    for (int r = tid; r < min(kMeshRows, total_rows); r += blockDim.x) {
+      if constexpr (OWNER) {   // (the row keeps its face: the slots record it)
+        const int f = s_rows[r].pad[0];
+        FaceRow fr = face_row(face_setup_sorted(verts, faces, f, src));
+        fr.pad[0] = f;
+        s_rows[r] = fr;
+      } else {
       s_rows[r] = face_row(face_setup_sorted(verts, faces, s_rows[r].pad[0], src));
+      }
+    }
     MESH_STAMP(3);   // this wave's face rows stand
     MESH_NOTE(8, total);
     MESH_NOTE(9, total_rows);
@@ -355,6 +374,7 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
         FaceRow r;
         if (item >= 0) r = s_rows[item >> 7];
         else r = face_row(face_setup_sorted(verts, faces, (int)(((unsigned)item & 0x7fffffffu) >> 7), src));
+        const int face = OWNER ? (item >= 0 ? r.pad[0] : (int)(((unsigned)item & 0x7fffffffu) >> 7)) : 0;
         const int xi_min = r.xr & 0xffff, xi_max = r.xr >> 16;
         const int dy_lo = out_lo(r.yr & 0xffff, ty0), dy_hi = out_hi(r.yr >> 16, ty0);
         {
@@ -398,7 +418,12 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
 #pragma unroll
                 for (int k = 0; k < 3; k++) w[k] = w[k] / w_sum;
                 const float zp = 1.0f / ((w[0] / r.z0 + w[1] / r.z1) + w[2] / r.z2);
+                if constexpr (OWNER) {
+                  if (zp == zp)
+                    atomicMin(&s_z[SL * (dy - ty0) + sy][SL * (dx - tx0) + sx], ((unsigned long long)mkey(zp) << 32) | (uint32_t)face);
+                } else {
                 if (zp == zp) atomicMin(&s_z[SL * (dy - ty0) + sy][SL * (dx - tx0) + sx], mkey(zp));
+                }
               }
             }
           }
@@ -411,6 +436,34 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
 
   // ---- clamp + bilinear (mesh/render.py:286, :311; ATen upsample_bilinear2d) ---------------
   float *out = depth + (size_t)b * S * S;
+  if constexpr (OWNER) {   // the same depth arithmetic; a tap's owner survives where its weight is non-zero and its raw
+                           // depth is not above clamp_max (torch's clamp passes the gradient at equality)
+    int4 *own = reinterpret_cast<int4 *>(owner) + (size_t)b * S * S;
+    for (int i = tid; i < TO * TO; i += blockDim.x) {
+      const int oy = i / TO, ox = i - oy * TO;
+      const int y = ty0 + oy, x = tx0 + ox;
+      if (y >= S || x >= S) continue;
+      int o[2][2] = {{-1, -1}, {-1, -1}};
+      auto tap = [&](slot_t k, float weight, int &o_) {
+        const float raw = mkey_inv((uint32_t)(k >> 32));
+        if ((uint32_t)k != 0xFFFFFFFFu && weight != 0.f && !(raw > clamp_max)) o_ = (int)(uint32_t)k;
+        return fminf(raw, clamp_max);
+      };
+      if (SL == 1) {
+        out[(size_t)y * S + x] = tap(s_z[oy][ox], 1.f, o[0][0]);
+      } else {
+        const Lin lx = lin_index(x, scale, src), ly = lin_index(y, scale, src);
+        float v[2][2];
+#pragma unroll
+        for (int sy = 0; sy < 2; sy++)
+#pragma unroll
+          for (int sx = 0; sx < 2; sx++)
+            v[sy][sx] = tap((&s_z[0][0])[(SL * oy + sy) * (SL * TO + 1) + SL * ox + sx], (sy ? ly.l1 : ly.l0) * (sx ? lx.l1 : lx.l0), o[sy][sx]);
+        out[(size_t)y * S + x] = ly.l0 * (lx.l0 * v[0][0] + lx.l1 * v[0][1]) + ly.l1 * (lx.l0 * v[1][0] + lx.l1 * v[1][1]);
+      }
+      own[(size_t)y * S + x] = make_int4(o[0][0], o[0][1], o[1][0], o[1][1]);
+    }
+  } else
   if (SL == 1 && (S & 3) == 0 && (TO & 3) == 0) {
     // four pixels per thread, one 16-byte write-through store (the map is read next by another kernel: left dirty in
     // the L2 it would be flushed by the end-of-kernel write-back, sphere_zbuf.h)
@@ -443,6 +496,20 @@ mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ f
     }
   }
   MESH_STAMP(7);
+}
+
+template <int TO, int SL, bool EXACT>
+__global__ void __launch_bounds__(1024)
+mesh_depth_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, int NV, int F, int src,
+                  int S, float clamp_max, float *__restrict__ depth) {
+  mesh_depth_tile<TO, SL, EXACT, false>(vertices, faces, NV, F, src, S, clamp_max, depth, nullptr);
+}
+
+template <int TO, int SL, bool EXACT>
+__global__ void __launch_bounds__(1024)
+mesh_depth_owner_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, int NV, int F, int src,
+                        int S, float clamp_max, float *__restrict__ depth, int *__restrict__ owner) {
+  mesh_depth_tile<TO, SL, EXACT, true>(vertices, faces, NV, F, src, S, clamp_max, depth, owner);
 }
 
 
@@ -1006,6 +1073,33 @@ extern "C" int shr_mesh_depth_fwd(const float *vertices, const int32_t *faces, i
     if (S > 32) MESH_LAUNCH(64, 2, false); else MESH_LAUNCH(32, 2, false);
   }
 #undef MESH_LAUNCH
+  return (int)hipGetLastError();
+}
+
+/* shr_mesh_depth_fwd's images plus the owner of every bilinear tap, for the differentiable DepthRender: the tile kernel's
+ * OWNER instantiation (64-bit slots, TO = 32 for two slots per axis, 64 for one).  Square S <= src_size / 2 only. */
+extern "C" int shr_mesh_depth_owner_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int src_size,
+                                        int S, float clamp_max, float *depth, int32_t *owner, void *stream) {
+  using namespace shr;
+  if (B == 0) return SHR_OK;
+  if (!vertices || (!faces && F > 0) || !depth || !owner || B < 0 || NV <= 0 || F < 0 || src_size <= 0 || S <= 0)
+    return SHR_EINVAL;
+  if ((((uintptr_t)vertices | (uintptr_t)owner) & 15u) != 0) return SHR_EINVAL;
+  if (B > 65535 || src_size > 32767 || 2 * S > src_size || F > (1 << 24)) return SHR_ETOOLARGE;
+  hipStream_t s = (hipStream_t)stream;
+  const float4 *v4 = reinterpret_cast<const float4 *>(vertices);
+  const bool single = (src_size % S == 0) && (((src_size / S) & 1) == 1);
+  const bool even = (src_size % S == 0) && (((src_size / S) & 1) == 0);
+#define MESH_OWNER_LAUNCH(TO, SL, EX)                                                                            \
+  do {                                                                                                           \
+    const int t = (S + (TO) - 1) / (TO);                                                                         \
+    hipLaunchKernelGGL((mesh_depth_owner_kernel<TO, SL, EX>), dim3((unsigned)(t * t), (unsigned)B), dim3(1024), 0, s, \
+                       v4, faces, NV, F, src_size, S, clamp_max, depth, owner);                                  \
+  } while (0)
+  if (single) MESH_OWNER_LAUNCH(64, 1, true);
+  else if (even) MESH_OWNER_LAUNCH(32, 2, true);
+  else MESH_OWNER_LAUNCH(32, 2, false);
+#undef MESH_OWNER_LAUNCH
   return (int)hipGetLastError();
 }
 

@@ -1,0 +1,356 @@
+// mesh_depth_bwd.hip -- the backward of the differentiable DepthRender / DepthRasterization: owner taps -> vertex
+// gradient -> bone-transform gradient.  The reference defines no backward for the mesh path (mesh/render.py:282-287);
+// the contract is the sphere backward's (ops.SphereDepthRaster): the gradient routes to the owner and holds coverage
+// fixed -- no edge, silhouette or visibility terms.
+//
+// An output pixel of the fused forward (mesh_depth.hip) is clamp(raw, max) -> ATen bilinear over up to four taps of the
+// 640 x 640 raster; a tap's raw depth is, for its owner face (shr_mesh_depth_owner_fwd),
+//     zp = 1 / sum_k (c_k / s) / z_k,   c_k = clamp(w_k, 0, 1),  s = sum_k c_k,  w_k = fi_k . (x, y, 1)
+// over the face's x-sorted corners (depth_rasterization_cuda_kernel.cu:57-110).  With n_k = cross(P_{k+1} - P, P_{k+2} - P)
+// and den = sum_k n_k, w_k = n_k / den, so
+//     d zp / d z_k = zp^2 (c_k / s) / z_k^2,   d zp / d c_k = -zp^2 (1 / z_k - 1 / zp) / s,
+//     d w_k = (d n_k - w_k d den) / den,
+// a weight clamped strictly outside [0, 1] contributing nothing (torch's clamp passes at 0 and 1).  The clamp decisions
+// are the forward's fp32 arithmetic, the derivatives are evaluated in fp64.
+//
+// Sums: every (tap, corner, coordinate) term is a 64-bit FIXED-POINT integer in a per-crop power-of-two unit taken from
+// the crop's largest term (a first pass over the taps, an order-independent maximum), so that the largest term is below
+// 2^41 and any 2^21 of them -- more than three corners x four taps x 320^2 pixels -- below 2^62: no sum can wrap, and a
+// term is clamped to 2^41 besides.  Integer sums do not depend on order: the gradient is bitwise reproducible and
+// independent of the batch and of the launch shape (data_to_model's fixed-point sums, d2m_search.h).  The unit is
+// computed on the device: no host synchronisation, the backward can be captured into a graph.
+#include "common.h"
+
+namespace shr {
+
+constexpr int kBwdThreads = 1024;
+constexpr int kBwdPix = 4;                            // output pixels per thread
+constexpr int kBwdBlockPix = kBwdThreads * kBwdPix;   // output pixels per workgroup
+constexpr int kBwdLdsVerts = 2048;                    // vertices whose accumulators fit LDS (2048 x 3 x 8 = 48 KB)
+constexpr int kFixBits = 41;                          // the crop's largest term -> below 2^41
+
+// One tap's nine partial derivatives, times its upstream gradient: corner k (in the face's ORIGINAL corner order) gets
+// (d/du, d/dv, d/dz) in g[k][0..2]; vid[k] its vertex.  (A degenerate face's NaN terms are dropped by the sums.)
+__device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, const int *__restrict__ faces, int f, int xi,
+                                          int yi, double gw, double (&g)[3][3], int (&vid)[3]) {
+  float fv[9];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    vid[k] = faces[f * 3 + k];
+    const float4 v = verts[vid[k]];
+    fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; k++) asm("" : "+v"(fv[k]));   // (kept in registers: see mesh_depth.hip face_setup_from)
+  // the forward's sort by x (.cu:33-56)
+  int p0, p2;
+  if (fv[0] < fv[3]) { p0 = (fv[6] < fv[0]) ? 2 : 0; p2 = (fv[3] < fv[6]) ? 2 : 1; }
+  else               { p0 = (fv[6] < fv[3]) ? 2 : 1; p2 = (fv[0] < fv[6]) ? 2 : 0; }
+  int p1 = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) if (p0 != k && p2 != k) p1 = k;
+  const int order[3] = {p0, p1, p2};
+  float p[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const int o = order[a];
+      p[a][d] = (o == 0) ? fv[d] : ((o == 1) ? fv[3 + d] : fv[6 + d]);
+    }
+  // the forward's fp32 weights (mesh_depth.hip face_row and the pixel loop): the clamp decisions
+  float fi[9];
+  fi[0] = p[1][1] - p[2][1]; fi[1] = p[2][0] - p[1][0]; fi[2] = p[1][0] * p[2][1] - p[2][0] * p[1][1];
+  fi[3] = p[2][1] - p[0][1]; fi[4] = p[0][0] - p[2][0]; fi[5] = p[2][0] * p[0][1] - p[0][0] * p[2][1];
+  fi[6] = p[0][1] - p[1][1]; fi[7] = p[1][0] - p[0][0]; fi[8] = p[0][0] * p[1][1] - p[1][0] * p[0][1];
+  const float den32 = (p[2][0] * (p[0][1] - p[1][1]) + p[0][0] * (p[1][1] - p[2][1])) + p[1][0] * (p[2][1] - p[0][1]);
+#pragma unroll
+  for (int k = 0; k < 9; k++) fi[k] = fi[k] / den32;
+  const float xf = (float)xi, yf = (float)yi;
+  bool pass[3];
+  float c32[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float w = (fi[3 * k] * xf + fi[3 * k + 1] * yf) + fi[3 * k + 2];
+    pass[k] = w >= 0.f && w <= 1.f;
+    c32[k] = fminf(fmaxf(w, 0.f), 1.f);
+  }
+  // fp64 derivatives
+  double x[3], y[3], z[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) { x[a] = p[a][0]; y[a] = p[a][1]; z[a] = p[a][2]; }
+  const double px = xi, py = yi;
+  const double den = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0]);
+  double c[3], w[3], s = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int b = (a + 1) % 3, e = (a + 2) % 3;
+    w[a] = ((x[b] - px) * (y[e] - py) - (x[e] - px) * (y[b] - py)) / den;
+    c[a] = pass[a] ? w[a] : (double)c32[a];
+    s += c[a];
+  }
+  double q = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) q += c[a] / s / z[a];
+  const double zp = 1.0 / q, zp2 = zp * zp;
+  double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  double kw = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    G[a][2] = gw * zp2 * (c[a] / s) / (z[a] * z[a]);
+    if (!pass[a]) continue;
+    const double k = -gw * zp2 * (1.0 / z[a] - q) / s / den;
+    const int b = (a + 1) % 3, e = (a + 2) % 3;
+    G[b][0] += k * (y[e] - py);
+    G[b][1] -= k * (x[e] - px);
+    G[e][0] -= k * (y[b] - py);
+    G[e][1] += k * (x[b] - px);
+    kw += k * w[a];
+  }
+  // - sum_a k_a w_a d den
+  G[0][0] -= kw * (y[1] - y[2]); G[0][1] -= kw * (x[2] - x[1]);
+  G[1][0] -= kw * (y[2] - y[0]); G[1][1] -= kw * (x[0] - x[2]);
+  G[2][0] -= kw * (y[0] - y[1]); G[2][1] -= kw * (x[1] - x[0]);
+  // sorted corner a is original corner order[a]
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+#pragma unroll
+    for (int d = 0; d < 3; d++) g[k][d] = (order[0] == k) ? G[0][d] : ((order[1] == k) ? G[1][d] : G[2][d]);
+}
+
+// Walks this workgroup's output pixels of crop blockIdx.y and calls fn(g, vid) for every live tap.
+template <typename Fn>
+__device__ __forceinline__ void for_each_tap(const float4 *__restrict__ verts, const int *__restrict__ faces,
+                                             const int4 *__restrict__ owner, const float *__restrict__ grad_depth,
+                                             int src, int S, Fn fn) {
+  const int b = blockIdx.y;
+  const float scale = (float)src / (float)S;
+  for (int k = 0; k < kBwdPix; k++) {
+    const int i = blockIdx.x * kBwdBlockPix + k * kBwdThreads + threadIdx.x;
+    if (i >= S * S) break;
+    const int4 o = owner[(size_t)b * S * S + i];
+    if ((o.x & o.y & o.z & o.w) < 0) continue;   // all four taps without an owner
+    const float gd = grad_depth[(size_t)b * S * S + i];
+    const int y = i / S, x = i - y * S;
+    const Lin lx = lin_index(x, scale, src), ly = lin_index(y, scale, src);
+    const int own[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      if (own[t] < 0) continue;
+      const int sy = t >> 1, sx = t & 1;
+      const double wt = (double)(sy ? ly.l1 : ly.l0) * (double)(sx ? lx.l1 : lx.l0);
+      double g[3][3];
+      int vid[3];
+      tap_terms(verts, faces, own[t], sx ? lx.i1 : lx.i0, sy ? ly.i1 : ly.i0, (double)gd * wt, g, vid);
+      fn(g, vid);
+    }
+  }
+}
+
+__device__ __forceinline__ double fix_unit(uint32_t max_bits) {   // 2^(41 - E), max < 2^E
+  int e = 0;
+  frexp((double)__uint_as_float(max_bits), &e);
+  return ldexp(1.0, kFixBits - e);
+}
+__device__ __forceinline__ long long to_fix(double v, double unit) {
+  double t = v * unit;
+  if (!(t == t)) return 0;
+  t = fmin(fmax(t, -0x1p41), 0x1p41);
+  return __double2ll_rn(t);
+}
+
+// pass 0: clear the workspace (a kernel rather than a memset node: the same launch sequence eager and in a graph)
+__global__ void __launch_bounds__(256)
+mesh_bwd_clear_kernel(uint4 *__restrict__ ws, size_t n16) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x)
+    ws[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// pass 1: the crop's largest |term| (float bits of non-negative numbers order like unsigned integers)
+__global__ void __launch_bounds__(kBwdThreads)
+mesh_bwd_max_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, const int4 *__restrict__ owner,
+                    const float *__restrict__ grad_depth, int NV, int src, int S, uint32_t *__restrict__ crop_max) {
+  __shared__ uint32_t s_max;
+  if (threadIdx.x == 0) s_max = 0u;
+  __syncthreads();
+  const float4 *verts = vertices + (size_t)blockIdx.y * NV;
+  float m = 0.f;
+  for_each_tap(verts, faces, owner, grad_depth, src, S, [&](const double (&g)[3][3], const int (&)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const float a = (float)fabs(g[k][d]);
+        if (a <= 3.0e38f) m = fmaxf(m, a);   // (NaN and inf: clamped / dropped by to_fix)
+      }
+  });
+  if (m > 0.f) atomicMax(&s_max, __float_as_uint(m));
+  __syncthreads();
+  if (threadIdx.x == 0 && s_max != 0u) atomicMax(&crop_max[blockIdx.y], s_max);
+}
+
+// pass 2: the fixed-point sums, staged in LDS when the crop's accumulators fit, then added to acc[B][NV][3]
+template <bool LDS>
+__global__ void __launch_bounds__(kBwdThreads)
+mesh_bwd_sum_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, const int4 *__restrict__ owner,
+                    const float *__restrict__ grad_depth, int NV, int src, int S, const uint32_t *__restrict__ crop_max,
+                    unsigned long long *__restrict__ acc) {
+  __shared__ unsigned long long s_acc[LDS ? kBwdLdsVerts * 3 : 1];
+  const int b = blockIdx.y;
+  const uint32_t mb = crop_max[b];
+  if (mb == 0u) return;   // (uniform: no term in this crop)
+  const double unit = fix_unit(mb);
+  unsigned long long *g_acc = acc + (size_t)b * NV * 3;
+  if (LDS) {
+    for (int i = threadIdx.x; i < NV * 3; i += kBwdThreads) s_acc[i] = 0ull;
+    __syncthreads();
+  }
+  const float4 *verts = vertices + (size_t)b * NV;
+  for_each_tap(verts, faces, owner, grad_depth, src, S, [&](const double (&g)[3][3], const int (&vid)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const long long v = to_fix(g[k][d], unit);
+        if (v == 0) continue;
+        if (LDS) atomicAdd(&s_acc[vid[k] * 3 + d], (unsigned long long)v);
+        else atomicAdd(&g_acc[(size_t)vid[k] * 3 + d], (unsigned long long)v);
+      }
+  });
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < NV * 3; i += kBwdThreads) {
+      const unsigned long long v = s_acc[i];
+      if (v != 0ull) atomicAdd(&g_acc[i], v);
+    }
+  }
+}
+
+// pass 3: fixed point -> grad_vertices[B][NV] = (du, dv, dz, 0)
+__global__ void __launch_bounds__(256)
+mesh_bwd_finish_kernel(const unsigned long long *__restrict__ acc, const uint32_t *__restrict__ crop_max, int B, int NV,
+                       float4 *__restrict__ grad_vertices) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * NV) return;
+  const int b = (int)(i / NV);
+  const uint32_t mb = crop_max[b];
+  float r[3] = {0.f, 0.f, 0.f};
+  if (mb != 0u) {
+    const double inv = 1.0 / fix_unit(mb);   // (a power of two: exact)
+#pragma unroll
+    for (int d = 0; d < 3; d++) r[d] = (float)((double)(long long)acc[i * 3 + d] * inv);
+  }
+  grad_vertices[i] = make_float4(r[0], r[1], r[2], 0.f);
+}
+
+// Skinning + camera backward: grad_T[b][k] = sum over the skin entries e of bone k of dacc_v(e) (x) wv_e.  One workgroup
+// per crop, one wave per bone (bones dealt round robin), lanes striding over the vertices in a fixed assignment, fp64
+// partial sums and a fixed butterfly: the same order whatever the batch -- bitwise reproducible.
+__global__ void __launch_bounds__(1024)
+lbs_project_bwd_kernel(const float4 *__restrict__ grad_vertices, int NB, int NV, const int *__restrict__ vstart,
+                       const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, float cx, float cy,
+                       float fx, float fy, const float *__restrict__ rand_f, float *__restrict__ grad_T) {
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const float4 *gv = grad_vertices + (size_t)b * NV;
+  const double sgn = right_hand ? -1.0 : 1.0;
+  const bool has_rand = rand_f != nullptr;
+  const double rf = has_rand ? (double)rand_f[b] : 1.0;
+  for (int k = wave; k < NB; k += waves) {
+    double a[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) a[j] = 0.0;
+    for (int v = lane; v < NV; v += 64) {
+      const int e0 = vstart[v], e1 = vstart[v + 1];
+      int e = e0;
+      while (e < e1 && sbone[e] != k) e++;
+      if (e == e1) continue;
+      const float4 g = gv[v];
+      // d out / d acc (common.h lbs_finish)
+      double d[4];
+      if (!has_rand) {
+        d[0] = sgn * (double)fx * g.x; d[1] = (double)fy * g.y; d[2] = g.z;
+        d[3] = (double)cx * g.x + (double)cy * g.y + (double)g.w;
+      } else {
+        d[0] = sgn * rf * (double)fx * g.x; d[1] = rf * (double)fy * g.y; d[2] = g.z; d[3] = 0.0;
+      }
+      for (; e < e1; e++) {
+        if (sbone[e] != k) continue;
+        const float4 q = swv[e];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          a[4 * r] += d[r] * q.x; a[4 * r + 1] += d[r] * q.y; a[4 * r + 2] += d[r] * q.z; a[4 * r + 3] += d[r] * q.w;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      double t = a[j];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
+      a[j] = t;
+    }
+    if (lane < 16) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; j++) t = (lane == j) ? a[j] : t;
+      grad_T[((size_t)b * NB + k) * 16 + lane] = (float)t;
+    }
+  }
+}
+
+}  // namespace shr
+
+static size_t mesh_bwd_max_bytes(int B) { return (((size_t)B * 4) + 255) & ~(size_t)255; }
+
+extern "C" long long shr_mesh_depth_bwd_workspace_bytes(int B, int NV) {
+  if (B < 0 || NV < 0) return -1;
+  return (long long)((mesh_bwd_max_bytes(B) + (size_t)B * NV * 3 * 8 + 15) & ~(size_t)15);
+}
+
+extern "C" int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, const int32_t *owner, const float *grad_depth,
+                                  int B, int NV, int F, int src_size, int S, float *grad_vertices, void *workspace,
+                                  void *stream) {
+  using namespace shr;
+  if (B == 0) return SHR_OK;
+  if (!vertices || !faces || !owner || !grad_depth || !grad_vertices || !workspace || B < 0 || NV <= 0 || F <= 0 ||
+      src_size <= 0 || S <= 0)
+    return SHR_EINVAL;
+  if ((((uintptr_t)vertices | (uintptr_t)owner | (uintptr_t)grad_vertices | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if (B > 65535 || src_size > 32767 || 2 * S > src_size || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t *crop_max = reinterpret_cast<uint32_t *>(workspace);
+  unsigned long long *acc = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + mesh_bwd_max_bytes(B));
+  const size_t n16 = (size_t)shr_mesh_depth_bwd_workspace_bytes(B, NV) / 16;
+  const size_t clear_blocks = (n16 + 255) / 256;
+  hipLaunchKernelGGL(mesh_bwd_clear_kernel, dim3((unsigned)(clear_blocks < 4096 ? clear_blocks : 4096)), dim3(256), 0, s,
+                     reinterpret_cast<uint4 *>(workspace), n16);
+  const float4 *v4 = reinterpret_cast<const float4 *>(vertices);
+  const int4 *o4 = reinterpret_cast<const int4 *>(owner);
+  const dim3 grid((unsigned)((S * S + kBwdBlockPix - 1) / kBwdBlockPix), (unsigned)B);
+  hipLaunchKernelGGL(mesh_bwd_max_kernel, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S, crop_max);
+  if (NV <= kBwdLdsVerts)
+    hipLaunchKernelGGL(mesh_bwd_sum_kernel<true>, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S,
+                       crop_max, acc);
+  else
+    hipLaunchKernelGGL(mesh_bwd_sum_kernel<false>, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S,
+                       crop_max, acc);
+  const size_t n = (size_t)B * NV;
+  hipLaunchKernelGGL(mesh_bwd_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, crop_max, B, NV,
+                     reinterpret_cast<float4 *>(grad_vertices));
+  return (int)hipGetLastError();
+}
+
+extern "C" int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
+                                   const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy,
+                                   float fx, float fy, const float *rand_f, float *grad_T, void *stream) {
+  using namespace shr;
+  if (B == 0) return SHR_OK;
+  if (!grad_vertices || !skin_vertex_start || !skin_bone || !skin_wv || !grad_T || B < 0 || NB <= 0 || NV <= 0)
+    return SHR_EINVAL;
+  if ((((uintptr_t)grad_vertices | (uintptr_t)skin_wv) & 15u) != 0) return SHR_EINVAL;
+  if (B > (1 << 30)) return SHR_ETOOLARGE;
+  hipLaunchKernelGGL(lbs_project_bwd_kernel, dim3((unsigned)B), dim3(NB >= 16 ? 1024 : 64 * NB), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4 *>(grad_vertices), NB, NV, skin_vertex_start, skin_bone,
+                     reinterpret_cast<const float4 *>(skin_wv), right_hand, cx, cy, fx, fy, rand_f, grad_T);
+  return (int)hipGetLastError();
+}

@@ -800,6 +800,117 @@ def mesh_render_fwd(T, skin_vertex_start, skin_bone, skin_wv, right_hand, camera
     return depth
 
 
+def mesh_owner_supported(out_size, src_size=640):
+    """True for the sizes the differentiable mesh path takes: square S with 0 < S <= src_size / 2 (S = 32 .. 320)."""
+    return isinstance(out_size, int) and 0 < out_size and 2 * out_size <= src_size
+
+
+def mesh_depth_owner_fwd(vertices, faces, out_size, src_size=640, clamp_max=100.0):
+    """mesh_depth_fwd's depth [B,S,S] (the same bits) + owner [B,S,S,4] int32: the face of each of the output pixel's
+    four bilinear taps (y0x0, y0x1, y1x0, y1x1), -1 for background, zero-weight or clamped taps."""
+    _check_input(vertices, "vertices")
+    _check_input(faces, "faces", torch.int32)
+    if vertices.dim() != 3 or vertices.shape[2] != 4 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("vertices must be [B,NV,4] and faces [F,3]")
+    if not mesh_owner_supported(out_size, src_size):
+        raise RuntimeError("the differentiable mesh path takes square sizes 0 < S <= %d, not %r" % (src_size // 2, out_size))
+    B, NV = vertices.shape[0], vertices.shape[1]
+    with _on(vertices.device):
+        depth = torch.empty((B, out_size, out_size), dtype=torch.float32, device=vertices.device)
+        owner = torch.empty((B, out_size, out_size, 4), dtype=torch.int32, device=vertices.device)
+        _lib.check(_lib.lib().shr_mesh_depth_owner_fwd(_ptr(vertices), _ptr(faces), B, NV, faces.shape[0], src_size,
+                                                       out_size, clamp_max, _ptr(depth), _ptr(owner), _stream()),
+                   "shr_mesh_depth_owner_fwd")
+    return depth, owner
+
+
+def mesh_depth_bwd(vertices, faces, owner, grad_depth, src_size=640):
+    """d<grad_depth, depth>/d vertices [B,NV,4] = (du, dv, dz, 0) through the owner taps (coverage held fixed);
+    deterministic fixed-point sums."""
+    _check_input(vertices, "vertices")
+    _check_input(faces, "faces", torch.int32)
+    _check_input(owner, "owner", torch.int32)
+    _check_input(grad_depth, "grad_depth")
+    B, NV = vertices.shape[0], vertices.shape[1]
+    S = grad_depth.shape[-1]
+    if grad_depth.shape != (B, S, S) or owner.shape != (B, S, S, 4) or vertices.shape != (B, NV, 4):
+        raise RuntimeError("grad_depth [B,S,S], owner [B,S,S,4] and vertices [B,NV,4] do not match")
+    lib = _lib.lib()
+    with _on(vertices.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=vertices.device)
+        ws = torch.empty((max(1, lib.shr_mesh_depth_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
+                         device=vertices.device)
+        _lib.check(lib.shr_mesh_depth_bwd(_ptr(vertices), _ptr(faces), _ptr(owner), _ptr(grad_depth), B, NV,
+                                          faces.shape[0], src_size, S, _ptr(out), _ptr(ws), _stream()),
+                   "shr_mesh_depth_bwd")
+    return out
+
+
+def lbs_project_bwd(grad_vertices, NB, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, rand_f=None):
+    """lbs_project's backward (project = 1): grad_vertices [B,NV,4] -> grad_T [B,NB,4,4] (rand_f gets none)."""
+    _check_input(grad_vertices, "grad_vertices")
+    _check_input(skin_vertex_start, "skin_vertex_start", torch.int32)
+    _check_input(skin_bone, "skin_bone", torch.int32)
+    _check_input(skin_wv, "skin_wv")
+    if rand_f is not None:
+        _check_input(rand_f, "rand_f")
+    B, NV = grad_vertices.shape[0], grad_vertices.shape[1]
+    if NV != skin_vertex_start.numel() - 1 or grad_vertices.shape[2] != 4:
+        raise RuntimeError("grad_vertices must be [B,NV,4] with the skin table's NV")
+    cx, cy, fx, fy = camera
+    with _on(grad_vertices.device):
+        grad_T = torch.empty((B, NB, 4, 4), dtype=torch.float32, device=grad_vertices.device)
+        _lib.check(_lib.lib().shr_lbs_project_bwd(_ptr(grad_vertices), B, NB, NV, _ptr(skin_vertex_start), _ptr(skin_bone),
+                                                  _ptr(skin_wv), int(bool(right_hand)), cx, cy, fx, fy, _ptr(rand_f),
+                                                  _ptr(grad_T), _stream()), "shr_lbs_project_bwd")
+    return grad_T
+
+
+class MeshDepthRaster(torch.autograd.Function):
+    """vertices [B,NV,4] (pixel space) -> depth [B,S,S] of the fused raster + clamp + resize, differentiable w.r.t.
+    (u, v, z) of the vertices.  Same contract as SphereDepthRaster: the gradient routes to each tap's owner face and
+    holds coverage fixed (no edge, silhouette or visibility gradient)."""
+
+    @staticmethod
+    def forward(ctx, vertices, faces, out_size, src_size, clamp_max):
+        vertices = vertices.contiguous()
+        depth, owner = mesh_depth_owner_fwd(vertices, faces, out_size, src_size, clamp_max)
+        ctx.save_for_backward(vertices, faces, owner)
+        ctx.src_size = src_size
+        return depth
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        vertices, faces, owner = ctx.saved_tensors
+        g = mesh_depth_bwd(vertices, faces, owner, grad_depth.contiguous().float(), ctx.src_size)
+        return g, None, None, None, None
+
+
+class MeshDepthRender(torch.autograd.Function):
+    """DepthRender.forward, differentiable w.r.t. T [B,NB,4,4]: skinning + camera into the distinct vertices
+    (lbs_project), then the owner-recording raster + clamp + resize; the depth is bit-identical to mesh_render_fwd.
+    Backward: owner taps -> vertex gradient -> skinning + camera backward.  Same contract as SphereDepthRaster: coverage
+    held fixed, no edge, silhouette or visibility gradient; rand_f (a random draw) gets none."""
+
+    @staticmethod
+    def forward(ctx, T, rand_f, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, faces, out_size,
+                src_size=640, clamp_max=100.0):
+        T = T.contiguous().float()
+        verts = lbs_project(T, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, rand_f)
+        depth, owner = mesh_depth_owner_fwd(verts, faces, out_size, src_size, clamp_max)
+        ctx.save_for_backward(verts, owner, rand_f, skin_vertex_start, skin_bone, skin_wv, faces)
+        ctx.meta = (T.shape[1], right_hand, camera, src_size)
+        return depth
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        verts, owner, rand_f, start, bone, wv, faces = ctx.saved_tensors
+        NB, right_hand, camera, src_size = ctx.meta
+        gv = mesh_depth_bwd(verts, faces, owner, grad_depth.contiguous().float(), src_size)
+        grad_T = lbs_project_bwd(gv, NB, start, bone, wv, right_hand, camera, rand_f)
+        return (grad_T,) + (None,) * 10
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

@@ -133,10 +133,18 @@ class DepthRasterization(nn.Module):
     """mesh/render.py:289-312.  forward(vertices[B,NV,>=3]) -> [B,height,width]:
     rasterize at 640x640, clamp, bilinear-downsample -- by default as ONE fused kernel that
     only rasterizes the source pixels the resize reads (`fused`).  `np_faces` is NOT
-    modified (the reference swaps its columns in place for the right hand, :298-300)."""
+    modified (the reference swaps its columns in place for the right hand, :298-300).
 
-    def __init__(self, width, height, np_faces, right_hand=True):
+    differentiable=True (square sizes up to 320 only, checked here): where grad is enabled and `vertices` requires grad,
+    the depth is differentiable w.r.t. vertices[..., :3] (ops.MeshDepthRaster) -- the same bits as the default path.
+    The sphere renderer's contract: the gradient routes to each tap's owner face and holds coverage fixed; there is no
+    gradient for edge, silhouette or visibility changes.  The reference defines no backward here (:282-287)."""
+
+    def __init__(self, width, height, np_faces, right_hand=True, differentiable=False):
         super().__init__()
+        if differentiable and not (width == height and ops.mesh_owner_supported(width)):
+            raise ValueError("differentiable DepthRasterization takes square sizes up to 320, not %r x %r" % (width, height))
+        self.differentiable = differentiable
         self.width = width
         self.height = height
         faces = np.array(np_faces, dtype=np.int64, copy=True)
@@ -149,6 +157,11 @@ class DepthRasterization(nn.Module):
 
     def forward(self, vertices):
         num_batch = vertices.shape[0]
+        if self.differentiable and vertices.requires_grad and torch.is_grad_enabled():
+            if not (vertices.is_cuda and vertices.dtype == torch.float32 and vertices.shape[-1] in (3, 4)):
+                raise RuntimeError("the differentiable mesh path takes CUDA fp32 vertices [B,NV,3 or 4]")
+            v4 = vertices if vertices.shape[-1] == 4 else torch.nn.functional.pad(vertices, (0, 1))
+            return ops.MeshDepthRaster.apply(v4, self.faces_i32, self.height, 640, 100.0)
         on_kernel = vertices.is_cuda and vertices.shape[-1] == 4 and vertices.dtype == torch.float32
         if on_kernel and self.fused and self.width == self.height and 2 * self.width <= 641:
             # raster + clamp + resize in one pass over the sampled source pixels only
@@ -193,10 +206,19 @@ class SparseSkinning(nn.Module):
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster
-    with the face gather fused (fill, raster, decode), clamp + bilinear resize."""
+    with the face gather fused (fill, raster, decode), clamp + bilinear resize.
 
-    def __init__(self, mesh, image_size):
+    differentiable=True (image sizes up to 320 only, checked here): where grad is enabled and T requires grad, the depth
+    is differentiable w.r.t. T (ops.MeshDepthRender; rand_fx gets no gradient) and bit-identical to the default path.
+    The sphere renderer's contract (ops.SphereDepthRaster): the gradient routes to each tap's owner face and holds
+    coverage fixed; there is no gradient for edge, silhouette or visibility changes.  The reference defines no backward
+    for the mesh (mesh/render.py:282-287)."""
+
+    def __init__(self, mesh, image_size, differentiable=False):
         super().__init__()
+        if differentiable and not ops.mesh_owner_supported(image_size):
+            raise ValueError("differentiable DepthRender takes image sizes up to 320, not %r" % (image_size,))
+        self.differentiable = differentiable
         # the skinned vertices never leave this module: the distinct ones are enough, the faces index them (identical
         # face corners, hence identical images; 16 -> 4 us of skinning and a sixth of the vertex traffic per call)
         self.lbs = SparseSkinning(mesh, distinct=True)
@@ -206,6 +228,12 @@ class DepthRender(nn.Module):
     def forward(self, transformation_mats, rand_fx=None):
         ras = self.rasterizer
         T = transformation_mats
+        if self.differentiable and T.requires_grad and torch.is_grad_enabled():
+            if not T.is_cuda:
+                raise RuntimeError("the differentiable mesh path needs CUDA bone transformations")
+            return ops.MeshDepthRender.apply(T, None if rand_fx is None else rand_fx.detach().contiguous().float(),
+                                             self.lbs.skin_vertex_start, self.lbs.skin_bone, self.lbs.skin_wv,
+                                             self.lbs.right_hand, self.camera, ras.faces_i32, ras.height)
         if T.is_cuda and ras.fused and ras.width == ras.height and 2 * ras.width <= 641:
             # skinning + camera + raster + clamp + resize: one launch where the lattice kernel applies
             # (shr_mesh_render_fwd), the two launches below through a workspace otherwise -- the same bits
