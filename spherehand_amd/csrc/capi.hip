@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "sphere_zbuf.h"
+#include "tri_face.h"
 
 extern "C" int shr_abi_version(void) { return 23; }
 

@@ -9,7 +9,7 @@
 // 25 (S = 128), 4 in 100 (S = 64) or 16 in 25 (S = 256).  Here each workgroup owns a tile
 // of TO x TO OUTPUT pixels; every output pixel has 2 x 2 source "slots" (x0/x1 x y0/y1 of
 // ATen's bilinear source index), kept in LDS as order-preserving integer keys.  Lanes =
-// faces: each lane sets its face up exactly like the reference kernel (tri_raster.hip:
+// faces: each lane sets its face up exactly like the reference kernel (tri_face.h:
 // cull, sort by x, inverse barycentric matrix), finds the output pixels whose slots fall in
 // the face's box, and for those source pixels repeats the reference's per-column span test
 // and per-pixel arithmetic verbatim, finishing with a native LDS integer min (order
@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "fk_rows.h"
+#include "tri_face.h"
 
 namespace shr {
 
@@ -55,61 +56,7 @@ __device__ __forceinline__ uint32_t mkey(float d) {
 __device__ __forceinline__ float mkey_inv(uint32_t k) {
   return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
 }
-__device__ __forceinline__ int m_cvt_rz_sat(float d) {
-  if (d != d) return 0;
-  if (d >= 2147483648.0f) return 2147483647;
-  if (d <= -2147483648.0f) return (int)0x80000000;
-  return (int)d;
-}
-
-// A face set up like the reference kernel (.cu:33-69): culled, vertices sorted by x, pixel
-// box.  `live` = front-facing, non-degenerate and its box meets the image.
-struct FaceSetup {
-  float p[3][3];
-  int xi_min, xi_max, r_lo, r_hi;
-  bool live;
-};
-
-__device__ __forceinline__ FaceSetup face_setup_from(const float (&fv_)[9], int src) {
-  // (opaque copies: see tri_raster.hip face_setup -- without them the sort's selects become loads from a scratch array)
-  float fv[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) { fv[k] = fv_[k]; asm("" : "+v"(fv[k])); }
-  FaceSetup s;
-  s.live = false;
-  if ((fv[7] - fv[1]) * (fv[3] - fv[0]) < (fv[4] - fv[1]) * (fv[6] - fv[0])) return s;
-  int p0, p2;
-  if (fv[0] < fv[3]) { p0 = (fv[6] < fv[0]) ? 2 : 0; p2 = (fv[3] < fv[6]) ? 2 : 1; }
-  else               { p0 = (fv[6] < fv[3]) ? 2 : 1; p2 = (fv[0] < fv[6]) ? 2 : 0; }
-  int p1 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) if (p0 != k && p2 != k) p1 = k;
-  const int order[3] = {p0, p1, p2};
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      const int o = order[a];
-      s.p[a][d] = (o == 0) ? fv[d] : ((o == 1) ? fv[3 + d] : fv[6 + d]);
-    }
-  if (s.p[0][0] == s.p[2][0]) return s;
-  s.xi_min = m_cvt_rz_sat(fmaxf(ceilf(s.p[0][0]), 0.f));
-  s.xi_max = m_cvt_rz_sat(fminf(s.p[2][0], (float)src - 1.f));
-  if (s.xi_min > s.xi_max) return s;
-  const float ylo = fminf(fminf(s.p[0][1], s.p[1][1]), s.p[2][1]), yhi = fmaxf(fmaxf(s.p[0][1], s.p[1][1]), s.p[2][1]);
-  // (a face whose largest x lies in (-1, 0) still reaches column 0 -- the reference truncates x2 towards zero,
-  // .cu:69 -- and the span there is an EXTRApolation of the edges: any row)
-  const bool wild = !(fabsf(ylo) < 1e9f) || !(fabsf(yhi) < 1e9f) || s.p[2][0] < 0.f;
-  // A column's span ends are edge interpolations slope * (x - xa) + ya at an x inside the edge:
-  // convex combinations of the vertices' y up to 4 roundings (<= 2.4e-7 * |y|); rows
-  // [ceil(min), trunc(max)] (.cu:89-90; a span end in (-1, 0) truncates to row 0).
-  const float yeps = 1e-5f * (fabsf(ylo) + fabsf(yhi)) + 1e-4f;
-  s.r_lo = wild ? 0 : max(0, (int)ceilf(ylo - yeps));
-  s.r_hi = wild ? src - 1 : min(src - 1, max(0, (int)floorf(yhi + yeps)));
-  s.live = true;
-  return s;
-}
-
+// face f's corners gathered and set up for a src x src image (tri_face.h face_setup)
 __device__ __forceinline__ FaceSetup face_setup_sorted(const float4 *__restrict__ verts, const int *__restrict__ faces,
                                                        int f, int src) {
   float fv[9];
@@ -118,7 +65,7 @@ __device__ __forceinline__ FaceSetup face_setup_sorted(const float4 *__restrict_
     const float4 v = verts[faces[f * 3 + k]];
     fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
   }
-  return face_setup_from(fv, src);
+  return face_setup(fv, src, src);
 }
 
 constexpr int kMeshQueue = 3584;   // work items per round (14 KB next to the 66-KB slot array)
@@ -145,21 +92,14 @@ static_assert(sizeof(FaceRow) == 96, "six 16-byte reads per work item");
 __device__ __forceinline__ FaceRow face_row(const FaceSetup &fs) {
   const float (&p)[3][3] = fs.p;
   FaceRow r;
-  r.fi[0] = p[1][1] - p[2][1]; r.fi[1] = p[2][0] - p[1][0]; r.fi[2] = p[1][0] * p[2][1] - p[2][0] * p[1][1];
-  r.fi[3] = p[2][1] - p[0][1]; r.fi[4] = p[0][0] - p[2][0]; r.fi[5] = p[2][0] * p[0][1] - p[0][0] * p[2][1];
-  r.fi[6] = p[0][1] - p[1][1]; r.fi[7] = p[1][0] - p[0][0]; r.fi[8] = p[0][0] * p[1][1] - p[1][0] * p[0][1];
-  const float den = (p[2][0] * (p[0][1] - p[1][1]) + p[0][0] * (p[1][1] - p[2][1])) + p[1][0] * (p[2][1] - p[0][1]);
-#pragma unroll
-  for (int k = 0; k < 9; k++) r.fi[k] = r.fi[k] / den;
-  const bool d01 = p[1][0] - p[0][0] != 0.f, d12 = p[2][0] - p[1][0] != 0.f;
-  r.s01 = d01 ? (p[1][1] - p[0][1]) / (p[1][0] - p[0][0]) : 0.f;
-  r.s12 = d12 ? (p[2][1] - p[1][1]) / (p[2][0] - p[1][0]) : 0.f;
-  r.s02 = (p[2][1] - p[0][1]) / (p[2][0] - p[0][0]);
+  face_matrix(p, r.fi);
+  const EdgeSlopes e = edge_slopes(p);
+  r.s01 = e.s01; r.s12 = e.s12; r.s02 = e.s02;
   r.x0 = p[0][0]; r.y0 = p[0][1]; r.x1 = p[1][0]; r.y1 = p[1][1];
   r.z0 = p[0][2]; r.z1 = p[1][2]; r.z2 = p[2][2];
   r.xr = fs.xi_min | (fs.xi_max << 16);   // (source sizes up to 32767: the launcher checks)
   r.yr = fs.r_lo | (fs.r_hi << 16);
-  r.flags = (d01 ? 1 : 0) | (d12 ? 2 : 0);
+  r.flags = e.flags;
   r.pad[0] = r.pad[1] = 0;
   return r;
 }
@@ -387,13 +327,8 @@ mesh_depth_tile(const float4 *__restrict__ vertices, const int *__restrict__ fac
             const int xi = sx ? lx.i1 : lx.i0;
             if (SL != 1 && ((!EXACT && (sx ? lx.l1 : lx.l0) == 0.f) || xi < xi_min || xi > xi_max)) continue;
             // ---- column span (.cu:72-90; the slopes are the face's) --------------------------
-            const float xf = (float)xi;
-            float yi1;
-            if (xf <= r.x1) yi1 = (r.flags & 1) ? r.s01 * (xf - r.x0) + r.y0 : r.y1;
-            else yi1 = (r.flags & 2) ? r.s12 * (xf - r.x1) + r.y1 : r.y1;
-            const float yi2 = r.s02 * (xf - r.x0) + r.y0;
-            const int yi_min = m_cvt_rz_sat(fmaxf(0.f, ceilf(fminf(yi1, yi2))));
-            const int yi_max = m_cvt_rz_sat(fminf(fmaxf(yi1, yi2), (float)src - 1.f));
+            int yi_min, yi_max;
+            span_rows(r.x0, r.y0, r.x1, r.y1, r.s01, r.s12, r.s02, r.flags, xi, src, yi_min, yi_max);
             // (only the output rows whose slots can fall inside the column's span; SL == 1: exactly the rows that
             // sample it, by the closed form -- the span lies inside the face's rows)
             const int ry_lo = yi_min > yi_max ? 1 : (EXACT ? first_out(yi_min, ty0) : max(dy_lo, out_lo(yi_min, ty0)));
@@ -407,17 +342,8 @@ mesh_depth_tile(const float4 *__restrict__ vertices, const int *__restrict__ fac
                 const int yi = sy ? ly.i1 : ly.i0;
                 if (SL != 1 && ((!EXACT && (sy ? ly.l1 : ly.l0) == 0.f) || yi < yi_min || yi > yi_max)) continue;
                 // ---- pixel (.cu:97-110) ----------------------------------------------------
-                const float yf = (float)yi;
-                float w[3], w_sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                  w[k] = (r.fi[3 * k] * xf + r.fi[3 * k + 1] * yf) + r.fi[3 * k + 2];
-                  w[k] = fminf(fmaxf(w[k], 0.f), 1.f);
-                  w_sum += w[k];
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) w[k] = w[k] / w_sum;
-                const float zp = 1.0f / ((w[0] / r.z0 + w[1] / r.z1) + w[2] / r.z2);
+                const float pz[3] = {r.z0, r.z1, r.z2}, rz[3] = {0.f, 0.f, 0.f};   // (no shared reciprocals here)
+                const float zp = pixel_depth(r.fi, (float)xi, (float)yi, pz, rz, false);
                 if constexpr (OWNER) {
                   if (zp == zp)
                     atomicMin(&s_z[SL * (dy - ty0) + sy][SL * (dx - tx0) + sx], ((unsigned long long)mkey(zp) << 32) | (uint32_t)face);
@@ -730,7 +656,7 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
         if (SKIN && f0 == 0) {   // (corners requested at the kernel's start, vertices in LDS)
           const float4 a = verts[corner[k][0]], bq = verts[corner[k][1]], c = verts[corner[k][2]];
           const float fv[9] = {a.x, a.y, a.z, bq.x, bq.y, bq.z, c.x, c.y, c.z};
-          fs = face_setup_from(fv, src);
+          fs = face_setup(fv, src, src);
         } else {
           fs = face_setup_sorted(verts, faces, f, src);
         }
@@ -782,7 +708,7 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
       const int ncols = __builtin_amdgcn_readlane(fincl, 63);
       if (lane < count) {
         row.pad[0] = c_lo - (fincl - ncol);                    // column item k of the face is lattice column k + this
-        // the corners' z: their refined reciprocals for the pixels' divisions (common.h tri_pixel_depth) in the words this
+        // the corners' z: their refined reciprocals for the pixels' divisions (tri_face.h tri_pixel_depth) in the words this
         // kernel does not read (xr, yr, pad[1]), flags bit 2: all three tame
         const bool tame = div_tame_z(row.z0) && div_tame_z(row.z1) && div_tame_z(row.z2);
         row.xr = __float_as_int(tame ? div_rcp_refined(row.z0) : 0.f);
@@ -804,16 +730,8 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
           const float4 f0v = r4[0], f1v = r4[1], f2v = r4[2], zv = r4[4], iv = r4[5];   // . | z0 z1 z2 rz0 | rz1 flags pad0 rz2
           const float fi[9] = {f0v.x, f0v.y, f0v.z, f0v.w, f1v.x, f1v.y, f1v.z, f1v.w, f2v.x};
           // ---- pixel (.cu:97-110) ----------------------------------------------------
-          const float xf = (float)src_of(cx), yf = (float)src_of(cy);
-          float w[3], w_sum = 0.f;
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            w[k] = (fi[3 * k] * xf + fi[3 * k + 1] * yf) + fi[3 * k + 2];
-            w[k] = fminf(fmaxf(w[k], 0.f), 1.f);
-            w_sum += w[k];
-          }
           const float pz[3] = {zv.x, zv.y, zv.z}, rz[3] = {zv.w, iv.x, iv.w};
-          const float zp = tri_pixel_depth(w[0], w[1], w[2], w_sum, pz, rz, (__float_as_int(iv.y) & 4) != 0);
+          const float zp = pixel_depth(fi, (float)src_of(cx), (float)src_of(cy), pz, rz, (__float_as_int(iv.y) & 4) != 0);
           if (zp == zp) atomicMin(&s_z[cy * LP + cx], mkey(zp));
         }
         qn -= take;
@@ -851,13 +769,8 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
         const int flags = __float_as_int(iv.y);
         const int cx = k + __float_as_int(iv.z);
         // ---- column span (.cu:72-90; the slopes are the face's) --------------------------
-        const float xf = (float)src_of(cx);
-        float yi1;
-        if (xf <= pv.z) yi1 = (flags & 1) ? sl.y * (xf - pv.x) + pv.y : pv.w;
-        else yi1 = (flags & 2) ? sl.z * (xf - pv.z) + pv.w : pv.w;
-        const float yi2 = sl.w * (xf - pv.x) + pv.y;
-        const int yi_min = m_cvt_rz_sat(fmaxf(0.f, ceilf(fminf(yi1, yi2))));
-        const int yi_max = m_cvt_rz_sat(fminf(fmaxf(yi1, yi2), (float)src - 1.f));
+        int yi_min, yi_max;
+        span_rows(pv.x, pv.y, pv.z, pv.w, sl.y, sl.z, sl.w, flags, src_of(cx), src, yi_min, yi_max);
         int cy_lo = 0, cnt = 0;
         if (colv && yi_min <= yi_max) {
           cy_lo = first_lat(yi_min);

@@ -19,7 +19,7 @@
 // term is clamped to 2^41 besides.  Integer sums do not depend on order: the gradient is bitwise reproducible and
 // independent of the batch and of the launch shape (data_to_model's fixed-point sums, d2m_search.h).  The unit is
 // computed on the device: no host synchronisation, the backward can be captured into a graph.
-#include "common.h"
+#include "tri_face.h"
 
 namespace shr {
 
@@ -40,41 +40,15 @@ __device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, cons
     const float4 v = verts[vid[k]];
     fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
   }
-#pragma unroll
-  for (int k = 0; k < 9; k++) asm("" : "+v"(fv[k]));   // (kept in registers: see mesh_depth.hip face_setup_from)
-  // the forward's sort by x (.cu:33-56)
-  int p0, p2;
-  if (fv[0] < fv[3]) { p0 = (fv[6] < fv[0]) ? 2 : 0; p2 = (fv[3] < fv[6]) ? 2 : 1; }
-  else               { p0 = (fv[6] < fv[3]) ? 2 : 1; p2 = (fv[0] < fv[6]) ? 2 : 0; }
-  int p1 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) if (p0 != k && p2 != k) p1 = k;
-  const int order[3] = {p0, p1, p2};
-  float p[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      const int o = order[a];
-      p[a][d] = (o == 0) ? fv[d] : ((o == 1) ? fv[3 + d] : fv[6 + d]);
-    }
-  // the forward's fp32 weights (mesh_depth.hip face_row and the pixel loop): the clamp decisions
-  float fi[9];
-  fi[0] = p[1][1] - p[2][1]; fi[1] = p[2][0] - p[1][0]; fi[2] = p[1][0] * p[2][1] - p[2][0] * p[1][1];
-  fi[3] = p[2][1] - p[0][1]; fi[4] = p[0][0] - p[2][0]; fi[5] = p[2][0] * p[0][1] - p[0][0] * p[2][1];
-  fi[6] = p[0][1] - p[1][1]; fi[7] = p[1][0] - p[0][0]; fi[8] = p[0][0] * p[1][1] - p[1][0] * p[0][1];
-  const float den32 = (p[2][0] * (p[0][1] - p[1][1]) + p[0][0] * (p[1][1] - p[2][1])) + p[1][0] * (p[2][1] - p[0][1]);
-#pragma unroll
-  for (int k = 0; k < 9; k++) fi[k] = fi[k] / den32;
-  const float xf = (float)xi, yf = (float)yi;
+  // the forward's sort by x and fp32 weights (tri_face.h): the clamp decisions
+  float p[3][3], fi[9], w32[3], c32[3];
+  int order[3];
+  face_sort(fv, p, order);
+  face_matrix(p, fi);
+  pixel_weights(fi, (float)xi, (float)yi, w32, c32);
   bool pass[3];
-  float c32[3];
 #pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float w = (fi[3 * k] * xf + fi[3 * k + 1] * yf) + fi[3 * k + 2];
-    pass[k] = w >= 0.f && w <= 1.f;
-    c32[k] = fminf(fmaxf(w, 0.f), 1.f);
-  }
+  for (int k = 0; k < 3; k++) pass[k] = w32[k] >= 0.f && w32[k] <= 1.f;
   // fp64 derivatives
   double x[3], y[3], z[3];
 #pragma unroll

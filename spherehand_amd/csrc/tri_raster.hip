@@ -18,97 +18,11 @@
 // atomic on the fp32 bits (signed min / unsigned max by sign: order independent,
 // hence deterministic); the image holds plain floats throughout: one fill pass,
 // one raster pass.
-#include "common.h"
+#include "tri_face.h"
 
 namespace shr {
 
 typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
-
-// CUDA double -> int32 conversion (cvt.rzi.s32.f64): truncate, saturate, NaN -> 0.
-// The operands here are fp32 values promoted to double, so fp32 compares suffice.
-__device__ __forceinline__ int cvt_rz_sat(float d) {
-  if (d != d) return 0;
-  if (d >= 2147483648.0f) return 2147483647;
-  if (d <= -2147483648.0f) return (int)0x80000000;
-  return (int)d;
-}
-
-struct FaceSetup {
-  float p[3][3];   // vertices sorted by x
-  float fi[9];     // inverse barycentric matrix / denominator
-  // the three edge slopes (.cu:75-85): the reference divides per COLUMN, but the quotients depend on the face only --
-  // one IEEE division each here, in the set-up (lanes = faces), instead of two per box pixel in the span test
-  float s01, s12, s02;
-  int sflags;      // bit 0: x1 - x0 != 0, bit 1: x2 - x1 != 0 (else the span end is y1, .cu:77, :83)
-  int xi_min, xi_max, r_lo, r_hi;
-  int live;
-};
-
-// .cu:25-69 for one face
-__device__ __forceinline__ FaceSetup face_setup(const float f_[9], int width, int height) {
-  // (opaque copies: the compiler turns the selects of the sort below -- "vertex order[a] of three" -- into ONE load from a
-  // select of addresses, which pins the nine values to a scratch array: 3 scratch stores and 9 dependent scratch loads per
-  // set-up, ScratchSize 48, in every kernel that sets faces up; values that are no longer loads stay in registers)
-  float f[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) { f[k] = f_[k]; asm("" : "+v"(f[k])); }
-  FaceSetup s;
-  s.live = 1;
-  if ((f[7] - f[1]) * (f[3] - f[0]) < (f[4] - f[1]) * (f[6] - f[0])) s.live = 0;  // :33 back face
-  int p0, p2;
-  if (f[0] < f[3]) {
-    p0 = (f[6] < f[0]) ? 2 : 0;
-    p2 = (f[3] < f[6]) ? 2 : 1;
-  } else {
-    p0 = (f[6] < f[3]) ? 2 : 1;
-    p2 = (f[0] < f[6]) ? 2 : 0;
-  }
-  int p1 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-    if (p0 != k && p2 != k) p1 = k;
-  const int order[3] = {p0, p1, p2};
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      // select without dynamic indexing (keeps everything in registers)
-      const int o = order[a];
-      s.p[a][d] = (o == 0) ? f[d] : ((o == 1) ? f[3 + d] : f[6 + d]);
-    }
-  if (s.p[0][0] == s.p[2][0]) s.live = 0;  // :54
-  float (*p)[3] = s.p;
-  s.fi[0] = p[1][1] - p[2][1]; s.fi[1] = p[2][0] - p[1][0]; s.fi[2] = p[1][0] * p[2][1] - p[2][0] * p[1][1];
-  s.fi[3] = p[2][1] - p[0][1]; s.fi[4] = p[0][0] - p[2][0]; s.fi[5] = p[2][0] * p[0][1] - p[0][0] * p[2][1];
-  s.fi[6] = p[0][1] - p[1][1]; s.fi[7] = p[1][0] - p[0][0]; s.fi[8] = p[0][0] * p[1][1] - p[1][0] * p[0][1];
-  const float den = (p[2][0] * (p[0][1] - p[1][1]) + p[0][0] * (p[1][1] - p[2][1])) + p[1][0] * (p[2][1] - p[0][1]);
-#pragma unroll
-  for (int k = 0; k < 9; k++) s.fi[k] = s.fi[k] / den;
-  {
-    const bool d01 = p[1][0] - p[0][0] != 0.f, d12 = p[2][0] - p[1][0] != 0.f;
-    s.s01 = d01 ? (p[1][1] - p[0][1]) / (p[1][0] - p[0][0]) : 0.f;
-    s.s12 = d12 ? (p[2][1] - p[1][1]) / (p[2][0] - p[1][0]) : 0.f;
-    s.s02 = (p[2][1] - p[0][1]) / (p[2][0] - p[0][0]);
-    s.sflags = (d01 ? 1 : 0) | (d12 ? 2 : 0);
-  }
-  // :68-69  max(ceil(x0), 0.) / min(x2, width - 1.)  (fmax/fmin drop a NaN operand)
-  s.xi_min = cvt_rz_sat(fmaxf(ceilf(p[0][0]), 0.f));
-  s.xi_max = cvt_rz_sat(fminf(p[2][0], (float)width - 1.f));
-  // conservative row range of the columns' spans
-  const float ylo = fminf(fminf(p[0][1], p[1][1]), p[2][1]);
-  const float yhi = fmaxf(fmaxf(p[0][1], p[1][1]), p[2][1]);
-  // (a face whose largest x lies in (-1, 0) still reaches column 0 -- the reference truncates x2 towards zero,
-  // .cu:69 -- and the span there is an EXTRApolation of the edges: any row)
-  const bool wild = !(fabsf(ylo) < 1e9f) || !(fabsf(yhi) < 1e9f) || p[2][0] < 0.f;
-  // A column's span ends are edge interpolations slope * (x - xa) + ya at an x inside the edge:
-  // convex combinations of the vertices' y up to 4 roundings (<= 2.4e-7 * |y|); rows
-  // [ceil(min), trunc(max)] (.cu:89-90; a span end in (-1, 0) truncates to row 0).
-  const float yeps = 1e-5f * (fabsf(ylo) + fabsf(yhi)) + 1e-4f;
-  s.r_lo = wild ? 0 : max(0, (int)ceilf(ylo - yeps));
-  s.r_hi = wild ? height - 1 : min(height - 1, max(0, (int)floorf(yhi + yeps)));
-  if (s.xi_min > s.xi_max) s.live = 0;
-  return s;
-}
 
 // Float min on the fp32 bits themselves, with native integer atomics: among non-negative
 // floats the bits order like signed integers, among negative ones like unsigned integers
@@ -120,41 +34,6 @@ __device__ __forceinline__ void zmin(float *cell, float v) {
   const uint32_t b = __float_as_uint(v);
   if (b >> 31) atomicMax(reinterpret_cast<unsigned int *>(cell), b);
   else atomicMin(reinterpret_cast<int *>(cell), (int)b);
-}
-
-// .cu:72-90: the rows [yi_min, yi_max] of column xi's span of the face.  (x0, y0), (x1, y1): the first two vertices
-// sorted by x; the slopes and their flags from face_setup.
-__device__ __forceinline__ void span_rows(float x0, float y0, float x1, float y1, float s01, float s12, float s02,
-                                          int sflags, int xi, int height, int &yi_min, int &yi_max) {
-  const float xf = (float)xi;
-  float yi1;
-  if (xf <= x1) yi1 = (sflags & 1) ? s01 * (xf - x0) + y0 : y1;
-  else yi1 = (sflags & 2) ? s12 * (xf - x1) + y1 : y1;
-  const float yi2 = s02 * (xf - x0) + y0;
-  yi_min = cvt_rz_sat(fmaxf(0.f, ceilf(fminf(yi1, yi2))));
-  yi_max = cvt_rz_sat(fminf(fmaxf(yi1, yi2), (float)height - 1.f));
-}
-// ... and whether row yi is inside it
-__device__ __forceinline__ bool span_inside(float x0, float y0, float x1, float y1, float s01, float s12, float s02,
-                                            int sflags, int xi, int yi, int height) {
-  int yi_min, yi_max;
-  span_rows(x0, y0, x1, y1, s01, s12, s02, sflags, xi, height, yi_min, yi_max);
-  return yi >= yi_min && yi <= yi_max;
-}
-
-// .cu:97-110 for a pixel inside its column's span: the depth the reference offers to its atomicMin (NaN: none)
-__device__ __forceinline__ float span_depth(const float (&pz)[3], const float (&rz)[3], bool tame, const float (&fi)[9], int xi,
-                                            int yi) {
-  const float xf = (float)xi, yf = (float)yi;
-  float w[3];
-  float w_sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    w[k] = (fi[3 * k + 0] * xf + fi[3 * k + 1] * yf) + fi[3 * k + 2];
-    w[k] = fminf(fmaxf(w[k], 0.f), 1.f);
-    w_sum += w[k];
-  }
-  return tri_pixel_depth(w[0], w[1], w[2], w_sum, pz, rz, tame);   // (the seven divisions of .cu:104-110)
 }
 
 // A wave sets up to 32 faces up with lanes = faces and parks each face's values in an LDS row (raster_batch below).
@@ -200,6 +79,9 @@ __device__ __forceinline__ void raster_batch(const FaceSetup &s, bool have, int 
   float (*s_face)[kFaceRow] = reinterpret_cast<float (*)[kFaceRow]>(scratch);
   uint2 *s_queue = reinterpret_cast<uint2 *>(scratch + NF * kFaceRow * 4);
   unsigned char *s_mark = scratch + NF * kFaceRow * 4 + kScratchQueueBytes;
+  float fi[9];
+  face_matrix(s.p, fi);
+  const EdgeSlopes e = edge_slopes(s.p);
   const int bw = s.xi_max - s.xi_min + 1, bh = s.r_hi - s.r_lo + 1;
   const bool alive = have && s.live && bh > 0 && bw > 0;
   const int ncol = alive ? bw : 0;                     // (<= 65535 columns each, 32 faces: 32 bits)
@@ -210,15 +92,15 @@ __device__ __forceinline__ void raster_batch(const FaceSetup &s, bool have, int 
 #pragma unroll
     for (int a = 0; a < 3; a++) { r[2 * a] = s.p[a][0]; r[2 * a + 1] = s.p[a][1]; r[8 + a] = s.p[a][2]; }
 #pragma unroll
-    for (int k = 0; k < 9; k++) r[11 + k] = s.fi[k];
-    r[6] = s.s01; r[7] = s.s12;
+    for (int k = 0; k < 9; k++) r[11 + k] = fi[k];
+    r[6] = e.s01; r[7] = e.s12;
     r[20] = __int_as_float(s.xi_min - (fincl - ncol));   // column item k of the face is pixel column k + this
-    r[21] = __int_as_float(s.r_lo); r[22] = __int_as_float(s.r_hi); r[23] = s.s02;
-    {   // the corners' z: their refined reciprocals for the pixels' divisions (common.h tri_pixel_depth), bit 2: all tame
+    r[21] = __int_as_float(s.r_lo); r[22] = __int_as_float(s.r_hi); r[23] = e.s02;
+    {   // the corners' z: their refined reciprocals for the pixels' divisions (tri_face.h tri_pixel_depth), bit 2: all tame
       const bool tame = div_tame_z(s.p[0][2]) && div_tame_z(s.p[1][2]) && div_tame_z(s.p[2][2]);
 #pragma unroll
       for (int a = 0; a < 3; a++) r[25 + a] = tame ? div_rcp_refined(s.p[a][2]) : 0.f;
-      r[24] = __int_as_float(s.sflags | (tame ? 4 : 0));
+      r[24] = __int_as_float(e.flags | (tame ? 4 : 0));
     }
   }
   __builtin_amdgcn_s_waitcnt(0xc07f);   // this wave's LDS writes (rows and queue are private to the wave)
@@ -234,7 +116,7 @@ __device__ __forceinline__ void raster_batch(const FaceSetup &s, bool have, int 
       const float fi[9] = {b2.w, b3.x, b3.y, b3.z, b3.w, b4.x, b4.y, b4.z, b4.w};
       const float rz[3] = {b6.y, b6.z, b6.w};                                  // (row words 25 .. 27; word 24: the flags)
       const int xi = (int)(e.y & 0xffffu), yi = (int)(e.y >> 16);
-      const float zp = span_depth(pz, rz, (__float_as_int(b6.x) & 4) != 0, fi, xi, yi);
+      const float zp = pixel_depth(fi, (float)xi, (float)yi, pz, rz, (__float_as_int(b6.x) & 4) != 0);
       if (zp == zp) sink(xi, yi, zp);  // fminf(NaN, old) = old
     }
     qn -= take;
@@ -378,29 +260,14 @@ constexpr int kBandScratchBytes = wave_scratch_bytes(kBandFaces);
 constexpr int kBandMaxBands = 512;        // per-band face counters in LDS
 constexpr uint32_t kFillBits = 0x447A0000u;   // 1000.0f, .cu:122
 
-// the culls and the row range of face_setup without its twelve divisions (same comparisons, same values)
-__device__ __forceinline__ uint32_t face_row_range(const float f[9], int width, int height) {
-  bool live = !((f[7] - f[1]) * (f[3] - f[0]) < (f[4] - f[1]) * (f[6] - f[0]));   // :33 back face
-  int p0, p2;
-  if (f[0] < f[3]) {
-    p0 = (f[6] < f[0]) ? 2 : 0;
-    p2 = (f[3] < f[6]) ? 2 : 1;
-  } else {
-    p0 = (f[6] < f[3]) ? 2 : 1;
-    p2 = (f[0] < f[6]) ? 2 : 0;
-  }
-  const float x0 = p0 == 0 ? f[0] : (p0 == 1 ? f[3] : f[6]), x2 = p2 == 0 ? f[0] : (p2 == 1 ? f[3] : f[6]);
-  if (x0 == x2) live = false;                                                       // :54
-  const int xi_min = cvt_rz_sat(fmaxf(ceilf(x0), 0.f));
-  const int xi_max = cvt_rz_sat(fminf(x2, (float)width - 1.f));
-  if (xi_min > xi_max) live = false;
-  const float ylo = fminf(fminf(f[1], f[4]), f[7]), yhi = fmaxf(fmaxf(f[1], f[4]), f[7]);
-  const bool wild = !(fabsf(ylo) < 1e9f) || !(fabsf(yhi) < 1e9f) || x2 < 0.f;
-  const float yeps = 1e-5f * (fabsf(ylo) + fabsf(yhi)) + 1e-4f;
-  const int r_lo = wild ? 0 : max(0, (int)ceilf(ylo - yeps));
-  const int r_hi = wild ? height - 1 : min(height - 1, max(0, (int)floorf(yhi + yeps)));
-  if (r_hi < r_lo) live = false;
-  return live ? ((uint32_t)r_lo | ((uint32_t)r_hi << 16)) : 0xFFFFu;
+// the culls and the row range of face_setup without its divisions (face_matrix, edge_slopes) and without sorting the
+// corners' y (face_ranges takes them in any order)
+__device__ __forceinline__ uint32_t face_row_range(const float (&f)[9], int width, int height) {
+  float p[3][3];
+  int order[3], xi_min, xi_max, r_lo, r_hi;
+  bool live = face_sort(f, p, order);
+  live &= face_ranges(p[0][0], p[2][0], f[1], f[4], f[7], width, height, xi_min, xi_max, r_lo, r_hi);
+  return live && r_hi >= r_lo ? ((uint32_t)r_lo | ((uint32_t)r_hi << 16)) : 0xFFFFu;
 }
 
 // RESIZE (DepthRasterization.forward's tail, mesh/render.py:286, :311, for sizes the lattice kernel does not take -- S = 256

@@ -396,7 +396,7 @@ def test_mesh_render_one_launch_equals_skinning_then_raster(S):
 
 
 def test_shared_reciprocal_divisions_equal_the_plain_ones():
-    """The triangle kernels' pixel depth (common.h tri_pixel_depth: three divisions by the weights' sum share one refined
+    """The triangle kernels' pixel depth (tri_face.h tri_pixel_depth: three divisions by the weights' sum share one refined
     reciprocal, the three by the corners' z bring theirs from the face's set-up) against the reference's seven plain
     IEEE divisions (.cu:104-110) on 2 x 10^9 pseudo-random (weights, depths) cases on both sides of every guard: not one
     bit of difference."""
