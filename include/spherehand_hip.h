@@ -472,6 +472,35 @@ int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const
                         const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy, float fx,
                         float fy, const float *rand_f, float *grad_T, void *stream);
 
+/* Differentiable triangle raster at its own resolution: depth_rasterization.forward(width, height, face_vertices)
+ * (mesh/cuda_kernel/depth_rasterization_cuda.cpp:15-25 -> depth_rasterization_cuda_kernel.cu:115-134, kernel :18-113),
+ * which the reference ships forward-only, with a backward at any W x H.  The contract is shr_mesh_depth_bwd's: each
+ * pixel's gradient goes to the face that OWNS its raw depth, coverage held fixed (no edge, silhouette or visibility
+ * terms).  Callers clamp in torch (mesh/render.py:286-287).
+ *   shr_tri_raster_owner_fwd / shr_tri_raster_indexed_owner_fwd
+ *       shr_tri_raster_fwd's / shr_tri_raster_indexed_fwd's arguments, limits and depth[B,H,W] bits, plus owner[B,H,W]
+ *       int32 (16-byte aligned): the face with the smallest offered depth at the pixel (.cu:97-110), ties to the smaller
+ *       face index; -1 where no face offered a depth (the background, 1000).
+ *   shr_tri_raster_bwd            grad_depth[B,H,W] + the owners + face_vertices[B,F,3,3] (the forward's) ->
+ *                                 grad_face_vertices[B,F,3,3]: d/d(x, y, z) of every corner.
+ *   shr_tri_raster_indexed_bwd    the same for vertices[B,NV,4] + faces[F,3] -> grad_vertices[B,NV,4] = (d/du, d/dv, d/dz, 0).
+ *       Per owned pixel, d zp / d (the owner's three corners) of .cu:57-110 at the integer pixel (a weight clamped strictly
+ *       outside [0, 1] contributes nothing), shr_mesh_depth_bwd's arithmetic with one tap of weight 1.  64-bit fixed-point
+ *       sums in a per-crop unit computed on the device: bitwise reproducible, independent of the batch, no host
+ *       synchronisation.  workspace: 16-byte aligned, shr_tri_raster_bwd_workspace_bytes(B, F) /
+ *       shr_tri_raster_indexed_bwd_workspace_bytes(B, NV) bytes, cleared by the call itself.  Owners outside [0, F) are
+ *       skipped.  B <= 65535 (SHR_ETOOLARGE beyond). */
+int shr_tri_raster_owner_fwd(const float *face_vertices, int B, int F, int W, int H, float *depth, int32_t *owner,
+                             void *stream);
+int shr_tri_raster_indexed_owner_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int W, int H,
+                                     float *depth, int32_t *owner, void *stream);
+long long shr_tri_raster_bwd_workspace_bytes(int B, int F);
+long long shr_tri_raster_indexed_bwd_workspace_bytes(int B, int NV);
+int shr_tri_raster_bwd(const float *face_vertices, const int32_t *owner, const float *grad_depth, int B, int F, int W,
+                       int H, float *grad_face_vertices, void *workspace, void *stream);
+int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *faces, const int32_t *owner, const float *grad_depth,
+                               int B, int NV, int F, int W, int H, float *grad_vertices, void *workspace, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -80,6 +80,12 @@ SIGNATURES = {
     "shr_mesh_depth_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "shr_mesh_depth_bwd": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "shr_lbs_project_bwd": ([_vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp], _i),
+    "shr_tri_raster_owner_fwd": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "shr_tri_raster_indexed_owner_fwd": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "shr_tri_raster_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_tri_raster_indexed_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_tri_raster_bwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "shr_tri_raster_indexed_bwd": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "shr_fk_fwd": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -49,13 +49,6 @@ __device__ unsigned long long mesh_tl[256 * 16 * 16];
 #define MESH_NOTE(slot, value) do {} while (0)
 #endif
 
-__device__ __forceinline__ uint32_t mkey(float d) {
-  const uint32_t b = __float_as_uint(d);
-  return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ float mkey_inv(uint32_t k) {
-  return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
-}
 // face f's corners gathered and set up for a src x src image (tri_face.h face_setup)
 __device__ __forceinline__ FaceSetup face_setup_sorted(const float4 *__restrict__ verts, const int *__restrict__ faces,
                                                        int f, int src) {

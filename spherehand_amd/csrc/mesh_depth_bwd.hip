@@ -1,5 +1,6 @@
 // mesh_depth_bwd.hip -- the backward of the differentiable DepthRender / DepthRasterization: owner taps -> vertex
-// gradient -> bone-transform gradient.  The reference defines no backward for the mesh path (mesh/render.py:282-287);
+// gradient -> bone-transform gradient; and of the owner raster at its own resolution (shr_tri_raster_owner_fwd): one
+// tap of weight 1 per owned pixel -> face-corner or vertex gradient (PixelTaps below).  The reference defines no backward for the mesh path (mesh/render.py:282-287);
 // the contract is the sphere backward's (ops.SphereDepthRaster): the gradient routes to the owner and holds coverage
 // fixed -- no edge, silhouette or visibility terms.
 //
@@ -27,19 +28,11 @@ constexpr int kBwdThreads = 1024;
 constexpr int kBwdPix = 4;                            // output pixels per thread
 constexpr int kBwdBlockPix = kBwdThreads * kBwdPix;   // output pixels per workgroup
 constexpr int kBwdLdsVerts = 2048;                    // vertices whose accumulators fit LDS (2048 x 3 x 8 = 48 KB)
-constexpr int kFixBits = 41;                          // the crop's largest term -> below 2^41
+constexpr int kFixBits = 41;                          // the crop's largest term -> below 2^41 (fewer: raster_fix_bits)
 
-// One tap's nine partial derivatives, times its upstream gradient: corner k (in the face's ORIGINAL corner order) gets
-// (d/du, d/dv, d/dz) in g[k][0..2]; vid[k] its vertex.  (A degenerate face's NaN terms are dropped by the sums.)
-__device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, const int *__restrict__ faces, int f, int xi,
-                                          int yi, double gw, double (&g)[3][3], int (&vid)[3]) {
-  float fv[9];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    vid[k] = faces[f * 3 + k];
-    const float4 v = verts[vid[k]];
-    fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
-  }
+// One tap's nine partial derivatives, times its upstream gradient: corner k of the face fv (x, y, z of its corners in
+// their ORIGINAL order) gets (d/du, d/dv, d/dz) in g[k][0..2].  (A degenerate face's NaN terms are dropped by the sums.)
+__device__ __forceinline__ void tap_terms(const float (&fv)[9], int xi, int yi, double gw, double (&g)[3][3]) {
   // the forward's sort by x and fp32 weights (tri_face.h): the clamp decisions
   float p[3][3], fi[9], w32[3], c32[3];
   int order[3];
@@ -91,45 +84,128 @@ __device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, cons
 #pragma unroll
     for (int d = 0; d < 3; d++) g[k][d] = (order[0] == k) ? G[0][d] : ((order[1] == k) ? G[1][d] : G[2][d]);
 }
-
-// Walks this workgroup's output pixels of crop blockIdx.y and calls fn(g, vid) for every live tap.
-template <typename Fn>
-__device__ __forceinline__ void for_each_tap(const float4 *__restrict__ verts, const int *__restrict__ faces,
-                                             const int4 *__restrict__ owner, const float *__restrict__ grad_depth,
-                                             int src, int S, Fn fn) {
-  const int b = blockIdx.y;
-  const float scale = (float)src / (float)S;
-  for (int k = 0; k < kBwdPix; k++) {
-    const int i = blockIdx.x * kBwdBlockPix + k * kBwdThreads + threadIdx.x;
-    if (i >= S * S) break;
-    const int4 o = owner[(size_t)b * S * S + i];
-    if ((o.x & o.y & o.z & o.w) < 0) continue;   // all four taps without an owner
-    const float gd = grad_depth[(size_t)b * S * S + i];
-    const int y = i / S, x = i - y * S;
-    const Lin lx = lin_index(x, scale, src), ly = lin_index(y, scale, src);
-    const int own[4] = {o.x, o.y, o.z, o.w};
+// the same for face f of an indexed mesh; vid[k] the vertex of corner k
+__device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, const int *__restrict__ faces, int f, int xi,
+                                          int yi, double gw, double (&g)[3][3], int (&vid)[3]) {
+  float fv[9];
 #pragma unroll
-    for (int t = 0; t < 4; t++) {
-      if (own[t] < 0) continue;
-      const int sy = t >> 1, sx = t & 1;
-      const double wt = (double)(sy ? ly.l1 : ly.l0) * (double)(sx ? lx.l1 : lx.l0);
-      double g[3][3];
-      int vid[3];
-      tap_terms(verts, faces, own[t], sx ? lx.i1 : lx.i0, sy ? ly.i1 : ly.i0, (double)gd * wt, g, vid);
-      fn(g, vid);
+  for (int k = 0; k < 3; k++) {
+    vid[k] = faces[f * 3 + k];
+    const float4 v = verts[vid[k]];
+    fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
+  }
+  tap_terms(fv, xi, yi, gw, g);
+}
+
+// The taps a backward sums over, crop blockIdx.y, this workgroup's pixels: walk(fn) calls fn(g, pid) for every live tap,
+// g its nine terms, pid[k] the accumulator point of corner k; points(): the accumulator points of a crop; kThreads,
+// kBlockPix: the threads and pixels of a workgroup; kRuns: a thread's taps come in runs of one face (the sums merge a run
+// in registers first).
+// MeshTaps: shr_mesh_depth_bwd's output pixels of the resampled depth, up to four bilinear owner taps each.
+struct MeshTaps {
+  const float4 *vertices;
+  const int *faces;
+  const int4 *owner;
+  const float *grad_depth;
+  int NV, src, S;
+  static constexpr int kThreads = kBwdThreads, kBlockPix = kBwdBlockPix;
+  static constexpr bool kRuns = false;
+  __device__ __forceinline__ int points() const { return NV; }
+  template <typename Fn>
+  __device__ __forceinline__ void walk(Fn fn) const {
+    const int b = blockIdx.y;
+    const float4 *verts = vertices + (size_t)b * NV;
+    const float scale = (float)src / (float)S;
+    for (int k = 0; k < kBwdPix; k++) {
+      const int i = blockIdx.x * kBwdBlockPix + k * kBwdThreads + threadIdx.x;
+      if (i >= S * S) break;
+      const int4 o = owner[(size_t)b * S * S + i];
+      if ((o.x & o.y & o.z & o.w) < 0) continue;   // all four taps without an owner
+      const float gd = grad_depth[(size_t)b * S * S + i];
+      const int y = i / S, x = i - y * S;
+      const Lin lx = lin_index(x, scale, src), ly = lin_index(y, scale, src);
+      const int own[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        if (own[t] < 0) continue;
+        const int sy = t >> 1, sx = t & 1;
+        const double wt = (double)(sy ? ly.l1 : ly.l0) * (double)(sx ? lx.l1 : lx.l0);
+        double g[3][3];
+        int vid[3];
+        tap_terms(verts, faces, own[t], sx ? lx.i1 : lx.i0, sy ? ly.i1 : ly.i0, (double)gd * wt, g, vid);
+        fn(g, vid);
+      }
     }
   }
-}
+};
 
-__device__ __forceinline__ double fix_unit(uint32_t max_bits) {   // 2^(41 - E), max < 2^E
+// PixelTaps: the owner raster's W x H pixels (shr_tri_raster_bwd, shr_tri_raster_indexed_bwd), ONE tap of weight 1 at the
+// integer pixel each -- the raster's own depth, no resampling.  The points: a face soup's corners (point 3 f + k of
+// face_vertices[B][F][3][3], its gradient's own layout) or an indexed mesh's vertices[B][NV][4].  An owner outside
+// [0, F) or a vertex index outside [0, NV) is skipped.  RUNS (the accumulators in global memory: more than kBwdLdsVerts
+// points, every hand-sized soup): a thread takes kPixRun CONSECUTIVE pixels of a row -- the hand's faces own runs of ~5
+// pixels of a row at 640 x 640, and a run's terms go to the same nine accumulators: summed in registers first, they cost
+// one L2 atomic each instead of one per pixel (256 soups @640^2: 10.1 -> 4.1 ms); 512 threads, so that the run's eighteen
+// registers fit without spilling.  Without RUNS (LDS accumulators): MeshTaps' layout, 1024 threads, kBwdPix pixels each
+// a workgroup's width apart (2.3 ms against 3.6 for consecutive pixels, 256 indexed hands @640^2).
+constexpr int kPixRun = 8;
+template <bool INDEXED, bool RUNS>
+struct PixelTaps {
+  const float *src;
+  const int *faces;
+  const int *owner;
+  const float *grad_depth;
+  int F, NV, W, H;
+  static constexpr int kThreads = RUNS ? 512 : kBwdThreads, kPix = RUNS ? kPixRun : kBwdPix, kBlockPix = kThreads * kPix;
+  static constexpr bool kRuns = RUNS;
+  __device__ __forceinline__ int points() const { return INDEXED ? NV : 3 * F; }
+  template <typename Fn>
+  __device__ __forceinline__ void walk(Fn fn) const {
+    const int b = blockIdx.y;
+    const size_t npix = (size_t)W * H;
+    for (int k = 0; k < kPix; k++) {
+      const size_t i = RUNS ? ((size_t)blockIdx.x * kThreads + threadIdx.x) * kPix + k
+                            : (size_t)blockIdx.x * kBlockPix + k * kThreads + threadIdx.x;
+      if (i >= npix) break;
+      const int f = owner[(size_t)b * npix + i];
+      if ((unsigned)f >= (unsigned)F) continue;   // (background: -1)
+      const float gd = grad_depth[(size_t)b * npix + i];
+      if (gd == 0.f) continue;                    // (its terms are zeros or NaN: nothing to sum)
+      const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+      float fv[9];
+      int pid[3];
+      bool ok = true;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        if (INDEXED) {
+          pid[c] = faces[f * 3 + c];
+          ok = ok && (unsigned)pid[c] < (unsigned)NV;
+          const float4 v = reinterpret_cast<const float4 *>(src)[(size_t)b * NV + (ok ? pid[c] : 0)];
+          fv[3 * c] = v.x; fv[3 * c + 1] = v.y; fv[3 * c + 2] = v.z;
+        } else {
+          pid[c] = 3 * f + c;
+          const float *fp = src + ((size_t)b * F + f) * 9 + 3 * c;
+          fv[3 * c] = fp[0]; fv[3 * c + 1] = fp[1]; fv[3 * c + 2] = fp[2];
+        }
+      }
+      if (!ok) continue;
+      double g[3][3];
+      tap_terms(fv, x, y, (double)gd, g);
+      fn(g, pid);
+    }
+  }
+};
+
+__device__ __forceinline__ double fix_unit(uint32_t max_bits, int bits) {   // 2^(bits - E), max < 2^E
   int e = 0;
   frexp((double)__uint_as_float(max_bits), &e);
-  return ldexp(1.0, kFixBits - e);
+  return ldexp(1.0, bits - e);
 }
-__device__ __forceinline__ long long to_fix(double v, double unit) {
+__device__ __forceinline__ long long to_fix(double v, double unit, int bits) {
   double t = v * unit;
   if (!(t == t)) return 0;
-  t = fmin(fmax(t, -0x1p41), 0x1p41);
+  const double lim = ldexp(1.0, bits);
+  t = fmin(fmax(t, -lim), lim);
   return __double2ll_rn(t);
 }
 
@@ -141,15 +217,14 @@ mesh_bwd_clear_kernel(uint4 *__restrict__ ws, size_t n16) {
 }
 
 // pass 1: the crop's largest |term| (float bits of non-negative numbers order like unsigned integers)
-__global__ void __launch_bounds__(kBwdThreads)
-mesh_bwd_max_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, const int4 *__restrict__ owner,
-                    const float *__restrict__ grad_depth, int NV, int src, int S, uint32_t *__restrict__ crop_max) {
+template <typename Taps>
+__global__ void __launch_bounds__(Taps::kThreads)
+mesh_bwd_max_kernel(Taps taps, uint32_t *__restrict__ crop_max) {
   __shared__ uint32_t s_max;
   if (threadIdx.x == 0) s_max = 0u;
   __syncthreads();
-  const float4 *verts = vertices + (size_t)blockIdx.y * NV;
   float m = 0.f;
-  for_each_tap(verts, faces, owner, grad_depth, src, S, [&](const double (&g)[3][3], const int (&)[3]) {
+  taps.walk([&](const double (&g)[3][3], const int (&)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
@@ -163,58 +238,81 @@ mesh_bwd_max_kernel(const float4 *__restrict__ vertices, const int *__restrict__
   if (threadIdx.x == 0 && s_max != 0u) atomicMax(&crop_max[blockIdx.y], s_max);
 }
 
-// pass 2: the fixed-point sums, staged in LDS when the crop's accumulators fit, then added to acc[B][NV][3]
-template <bool LDS>
-__global__ void __launch_bounds__(kBwdThreads)
-mesh_bwd_sum_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, const int4 *__restrict__ owner,
-                    const float *__restrict__ grad_depth, int NV, int src, int S, const uint32_t *__restrict__ crop_max,
-                    unsigned long long *__restrict__ acc) {
+// pass 2: the fixed-point sums, staged in LDS when the crop's accumulators fit, then added to acc[B][points][3]
+template <typename Taps, bool LDS>
+__global__ void __launch_bounds__(Taps::kThreads)
+mesh_bwd_sum_kernel(Taps taps, const uint32_t *__restrict__ crop_max, int fix_bits, unsigned long long *__restrict__ acc) {
   __shared__ unsigned long long s_acc[LDS ? kBwdLdsVerts * 3 : 1];
-  const int b = blockIdx.y;
+  const int b = blockIdx.y, NP = taps.points();
   const uint32_t mb = crop_max[b];
   if (mb == 0u) return;   // (uniform: no term in this crop)
-  const double unit = fix_unit(mb);
-  unsigned long long *g_acc = acc + (size_t)b * NV * 3;
+  const double unit = fix_unit(mb, fix_bits);
+  unsigned long long *g_acc = acc + (size_t)b * NP * 3;
   if (LDS) {
-    for (int i = threadIdx.x; i < NV * 3; i += kBwdThreads) s_acc[i] = 0ull;
+    for (int i = threadIdx.x; i < NP * 3; i += Taps::kThreads) s_acc[i] = 0ull;
     __syncthreads();
   }
-  const float4 *verts = vertices + (size_t)b * NV;
-  for_each_tap(verts, faces, owner, grad_depth, src, S, [&](const double (&g)[3][3], const int (&vid)[3]) {
+  auto add = [&](int p, int d, long long v) {
+    if (v == 0) return;
+    if (LDS) atomicAdd(&s_acc[p * 3 + d], (unsigned long long)v);
+    else atomicAdd(&g_acc[(size_t)p * 3 + d], (unsigned long long)v);
+  };
+  // kRuns: the current run's points and sums (integers: merging first changes no bit of the result)
+  int run_pid[3] = {-1, -1, -1};
+  long long run[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  auto flush = [&]() {
+    if (run_pid[0] < 0) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+      for (int d = 0; d < 3; d++) add(run_pid[k], d, run[k][d]);
+  };
+  taps.walk([&](const double (&g)[3][3], const int (&pid)[3]) {
+    if (Taps::kRuns && (pid[0] != run_pid[0] || pid[1] != run_pid[1] || pid[2] != run_pid[2])) {
+      flush();
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        run_pid[k] = pid[k];
+#pragma unroll
+        for (int d = 0; d < 3; d++) run[k][d] = 0;
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
       for (int d = 0; d < 3; d++) {
-        const long long v = to_fix(g[k][d], unit);
-        if (v == 0) continue;
-        if (LDS) atomicAdd(&s_acc[vid[k] * 3 + d], (unsigned long long)v);
-        else atomicAdd(&g_acc[(size_t)vid[k] * 3 + d], (unsigned long long)v);
+        const long long v = to_fix(g[k][d], unit, fix_bits);
+        if (Taps::kRuns) run[k][d] += v;
+        else add(pid[k], d, v);
       }
   });
+  if (Taps::kRuns) flush();
   if (LDS) {
     __syncthreads();
-    for (int i = threadIdx.x; i < NV * 3; i += kBwdThreads) {
+    for (int i = threadIdx.x; i < NP * 3; i += Taps::kThreads) {
       const unsigned long long v = s_acc[i];
       if (v != 0ull) atomicAdd(&g_acc[i], v);
     }
   }
 }
 
-// pass 3: fixed point -> grad_vertices[B][NV] = (du, dv, dz, 0)
+// pass 3: fixed point -> out[B][NP] = (du, dv, dz, 0) (STRIDE 4: vertices) or (du, dv, dz) (STRIDE 3: face corners)
+template <int STRIDE>
 __global__ void __launch_bounds__(256)
-mesh_bwd_finish_kernel(const unsigned long long *__restrict__ acc, const uint32_t *__restrict__ crop_max, int B, int NV,
-                       float4 *__restrict__ grad_vertices) {
+mesh_bwd_finish_kernel(const unsigned long long *__restrict__ acc, const uint32_t *__restrict__ crop_max, int B, int NP,
+                       int fix_bits, float *__restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)B * NV) return;
-  const int b = (int)(i / NV);
+  if (i >= (size_t)B * NP) return;
+  const int b = (int)(i / NP);
   const uint32_t mb = crop_max[b];
   float r[3] = {0.f, 0.f, 0.f};
   if (mb != 0u) {
-    const double inv = 1.0 / fix_unit(mb);   // (a power of two: exact)
+    const double inv = 1.0 / fix_unit(mb, fix_bits);   // (a power of two: exact)
 #pragma unroll
     for (int d = 0; d < 3; d++) r[d] = (float)((double)(long long)acc[i * 3 + d] * inv);
   }
-  grad_vertices[i] = make_float4(r[0], r[1], r[2], 0.f);
+  if (STRIDE == 4) reinterpret_cast<float4 *>(out)[i] = make_float4(r[0], r[1], r[2], 0.f);
+  else { out[i * 3] = r[0]; out[i * 3 + 1] = r[1]; out[i * 3 + 2] = r[2]; }
 }
 
 // Skinning + camera backward: grad_T[b][k] = sum over the skin entries e of bone k of dacc_v(e) (x) wv_e.  One workgroup
@@ -275,11 +373,37 @@ lbs_project_bwd_kernel(const float4 *__restrict__ grad_vertices, int NB, int NV,
 }  // namespace shr
 
 static size_t mesh_bwd_max_bytes(int B) { return (((size_t)B * 4) + 255) & ~(size_t)255; }
-
-extern "C" long long shr_mesh_depth_bwd_workspace_bytes(int B, int NV) {
-  if (B < 0 || NV < 0) return -1;
-  return (long long)((mesh_bwd_max_bytes(B) + (size_t)B * NV * 3 * 8 + 15) & ~(size_t)15);
+// crop maxima [B] u32 | accumulators [B][NP][3] i64
+static long long fix_workspace_bytes(int B, long long NP) {
+  if (B < 0 || NP < 0) return -1;
+  return (long long)((mesh_bwd_max_bytes(B) + (size_t)B * NP * 3 * 8 + 15) & ~(size_t)15);
 }
+
+// The four passes of a fixed-point backward over `taps` (clear, crop maxima, sums, conversion to out[B][NP][STRIDE]).
+template <int STRIDE, typename Taps>
+static int fixed_point_bwd(const Taps &taps, int B, int NP, size_t npix, int fix_bits, float *out, void *workspace,
+                           hipStream_t s) {
+  using namespace shr;
+  uint32_t *crop_max = reinterpret_cast<uint32_t *>(workspace);
+  unsigned long long *acc = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + mesh_bwd_max_bytes(B));
+  const size_t n16 = (size_t)fix_workspace_bytes(B, NP) / 16;
+  const size_t clear_blocks = (n16 + 255) / 256;
+  hipLaunchKernelGGL(mesh_bwd_clear_kernel, dim3((unsigned)(clear_blocks < 4096 ? clear_blocks : 4096)), dim3(256), 0, s,
+                     reinterpret_cast<uint4 *>(workspace), n16);
+  const dim3 grid((unsigned)((npix + Taps::kBlockPix - 1) / Taps::kBlockPix), (unsigned)B);
+  hipLaunchKernelGGL(mesh_bwd_max_kernel<Taps>, grid, dim3(Taps::kThreads), 0, s, taps, crop_max);
+  if (NP <= kBwdLdsVerts && !Taps::kRuns)
+    hipLaunchKernelGGL((mesh_bwd_sum_kernel<Taps, !Taps::kRuns>), grid, dim3(Taps::kThreads), 0, s, taps, crop_max, fix_bits, acc);
+  else
+    hipLaunchKernelGGL((mesh_bwd_sum_kernel<Taps, false>), grid, dim3(Taps::kThreads), 0, s, taps, crop_max, fix_bits, acc);
+  const size_t n = (size_t)B * NP;
+  if (n > 0)
+    hipLaunchKernelGGL(mesh_bwd_finish_kernel<STRIDE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, crop_max, B,
+                       NP, fix_bits, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" long long shr_mesh_depth_bwd_workspace_bytes(int B, int NV) { return fix_workspace_bytes(B, NV); }
 
 extern "C" int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, const int32_t *owner, const float *grad_depth,
                                   int B, int NV, int F, int src_size, int S, float *grad_vertices, void *workspace,
@@ -291,27 +415,54 @@ extern "C" int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, c
     return SHR_EINVAL;
   if ((((uintptr_t)vertices | (uintptr_t)owner | (uintptr_t)grad_vertices | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   if (B > 65535 || src_size > 32767 || 2 * S > src_size || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t *crop_max = reinterpret_cast<uint32_t *>(workspace);
-  unsigned long long *acc = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(workspace) + mesh_bwd_max_bytes(B));
-  const size_t n16 = (size_t)shr_mesh_depth_bwd_workspace_bytes(B, NV) / 16;
-  const size_t clear_blocks = (n16 + 255) / 256;
-  hipLaunchKernelGGL(mesh_bwd_clear_kernel, dim3((unsigned)(clear_blocks < 4096 ? clear_blocks : 4096)), dim3(256), 0, s,
-                     reinterpret_cast<uint4 *>(workspace), n16);
-  const float4 *v4 = reinterpret_cast<const float4 *>(vertices);
-  const int4 *o4 = reinterpret_cast<const int4 *>(owner);
-  const dim3 grid((unsigned)((S * S + kBwdBlockPix - 1) / kBwdBlockPix), (unsigned)B);
-  hipLaunchKernelGGL(mesh_bwd_max_kernel, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S, crop_max);
+  const MeshTaps taps{reinterpret_cast<const float4 *>(vertices), faces, reinterpret_cast<const int4 *>(owner), grad_depth, NV,
+                      src_size, S};
+  return fixed_point_bwd<4>(taps, B, NV, (size_t)S * S, kFixBits, grad_vertices, workspace, (hipStream_t)stream);
+}
+
+// The owner raster's backward.  A point's accumulator takes at most three terms per pixel (a face's three corners, one
+// vertex each unless the face repeats one): with N = 3 W H terms the crop's largest term goes below 2^(62 - ceil(log2 N)),
+// 2^41 at most -- 41 bits up to 640 x 640, no sum can wrap at any size.
+static int raster_fix_bits(int W, int H) {
+  const unsigned long long n = 3ull * (unsigned long long)W * (unsigned long long)H;
+  int lg = 0;
+  while ((1ull << lg) < n) lg++;
+  return 62 - lg < shr::kFixBits ? 62 - lg : shr::kFixBits;
+}
+
+extern "C" long long shr_tri_raster_bwd_workspace_bytes(int B, int F) { return fix_workspace_bytes(B, 3LL * F); }
+extern "C" long long shr_tri_raster_indexed_bwd_workspace_bytes(int B, int NV) { return fix_workspace_bytes(B, NV); }
+
+extern "C" int shr_tri_raster_bwd(const float *face_vertices, const int32_t *owner, const float *grad_depth, int B, int F,
+                                  int W, int H, float *grad_face_vertices, void *workspace, void *stream) {
+  using namespace shr;
+  if (B == 0 || F == 0) return SHR_OK;   // (no face: an empty gradient)
+  if (!face_vertices || !owner || !grad_depth || !grad_face_vertices || !workspace || B < 0 || F < 0 || W <= 0 || H <= 0)
+    return SHR_EINVAL;
+  if (((uintptr_t)workspace & 15u) != 0) return SHR_EINVAL;
+  if (B > 65535 || W > 65535 || H > 65535 || 3LL * F * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
+  if (3 * F <= kBwdLdsVerts)
+    return fixed_point_bwd<3>(PixelTaps<false, false>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
+                              (size_t)W * H, raster_fix_bits(W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+  return fixed_point_bwd<3>(PixelTaps<false, true>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
+                            (size_t)W * H, raster_fix_bits(W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+}
+
+extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *faces, const int32_t *owner,
+                                          const float *grad_depth, int B, int NV, int F, int W, int H, float *grad_vertices,
+                                          void *workspace, void *stream) {
+  using namespace shr;
+  if (B == 0) return SHR_OK;
+  if (!vertices || (!faces && F > 0) || !owner || !grad_depth || !grad_vertices || !workspace || B < 0 || NV <= 0 || F < 0 ||
+      W <= 0 || H <= 0)
+    return SHR_EINVAL;
+  if ((((uintptr_t)vertices | (uintptr_t)grad_vertices | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if (B > 65535 || W > 65535 || H > 65535 || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
   if (NV <= kBwdLdsVerts)
-    hipLaunchKernelGGL(mesh_bwd_sum_kernel<true>, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S,
-                       crop_max, acc);
-  else
-    hipLaunchKernelGGL(mesh_bwd_sum_kernel<false>, grid, dim3(kBwdThreads), 0, s, v4, faces, o4, grad_depth, NV, src_size, S,
-                       crop_max, acc);
-  const size_t n = (size_t)B * NV;
-  hipLaunchKernelGGL(mesh_bwd_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, crop_max, B, NV,
-                     reinterpret_cast<float4 *>(grad_vertices));
-  return (int)hipGetLastError();
+    return fixed_point_bwd<4>(PixelTaps<true, false>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
+                              raster_fix_bits(W, H), grad_vertices, workspace, (hipStream_t)stream);
+  return fixed_point_bwd<4>(PixelTaps<true, true>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
+                            raster_fix_bits(W, H), grad_vertices, workspace, (hipStream_t)stream);
 }
 
 extern "C" int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,

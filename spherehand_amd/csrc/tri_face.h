@@ -72,6 +72,16 @@ __device__ __forceinline__ bool face_ranges(float x0, float x2, float ya, float 
   return xi_min <= xi_max;
 }
 
+// Order-preserving integer key of an fp32 depth (negative depths included, -0 below +0) and its inverse: the 32-bit
+// slots of mesh_depth.hip and the high word of the 64-bit (key << 32 | face) owner slots.
+__device__ __forceinline__ uint32_t mkey(float d) {
+  const uint32_t b = __float_as_uint(d);
+  return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ float mkey_inv(uint32_t k) {
+  return __uint_as_float(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
 // .cu:25-69 for one face.  Every field is computed for every face; a caller reads the ranges and corners of a live one only.
 struct FaceSetup {
   float p[3][3];                    // corners sorted by x

@@ -1,8 +1,9 @@
-// tri_raster.hip -- triangle-mesh depth rasterizer (forward only) + skinning.
+// tri_raster.hip -- triangle-mesh depth rasterizer (forward; the owner raster its backward needs) + skinning.
 //
 // Replaces (reference file:line):
 //   mesh/cuda_kernel/depth_rasterization_cuda_kernel.cu:18-113 `kernel` and :6-16
 //   `atomicMin`, :115-134 depth_rasterization_cuda_forward  -> shr_tri_raster_fwd
+//   the same plus the face that made each pixel's depth       -> shr_tri_raster_owner_fwd (backward: mesh_depth_bwd.hip)
 //   mesh/pointTransformation.py:39-46 LinearBlendSkinning.forward and :84-99
 //   OthographicalProjection.forward                           -> shr_lbs_project
 //
@@ -46,7 +47,8 @@ constexpr int wave_scratch_bytes(int nf) { return nf * kFaceRow * 4 + kScratchQu
 constexpr int kWaveScratchBytes = wave_scratch_bytes(kFacesPerWave);               // 3584 + 1024
 
 // One batch: lane l < 32 brings face set-up `s` (`have`: the lane holds a face; rows [s.r_lo, s.r_hi] already clipped
-// to what the caller wants rasterized); every pixel inside its column's span goes to sink(xi, yi, depth) once.
+// to what the caller wants rasterized); every pixel inside its column's span goes to sink(xi, yi, depth, l) once, l the
+// lane that brought its face.
 // `scratch`: this wave's kWaveScratchBytes of LDS (16-byte aligned); nothing of it is live between two batches.
 // One batch, the reference's own loop structure spread over a wave (.cu:70-111: for each column of the face its span
 // of rows, for each row of the span a pixel):
@@ -117,7 +119,7 @@ __device__ __forceinline__ void raster_batch(const FaceSetup &s, bool have, int 
       const float rz[3] = {b6.y, b6.z, b6.w};                                  // (row words 25 .. 27; word 24: the flags)
       const int xi = (int)(e.y & 0xffffu), yi = (int)(e.y >> 16);
       const float zp = pixel_depth(fi, (float)xi, (float)yi, pz, rz, (__float_as_int(b6.x) & 4) != 0);
-      if (zp == zp) sink(xi, yi, zp);  // fminf(NaN, old) = old
+      if (zp == zp) sink(xi, yi, zp, (int)e.x);  // fminf(NaN, old) = old
     }
     qn -= take;
   };
@@ -215,16 +217,19 @@ __device__ __forceinline__ void load_face(const float *__restrict__ src, const i
 // A wave takes 32 faces and offers every covered pixel to the image with a native integer atomic on the fp32 bits
 // (zmin), after one fill pass: 256 hand crops @640x640 (a 419-MB image) 630 us in rounds 1-4, 440-480 us since
 // raster_batch walks column spans instead of boxes.
-template <bool INDEXED>
+// OWNER (the owner raster's second pass where the band kernel does not fit): zbuf holds the finished depth image; a face
+// whose offered depth has the pixel's bits takes an unsigned minimum of its index on owner (all -1 before): the smallest
+// of the faces that tie -- the 64-bit (key << 32 | face) minimum of the band kernel, in two passes.
+template <bool INDEXED, bool OWNER = false>
 __global__ void __launch_bounds__(256)
 tri_raster_kernel(const float *__restrict__ src, const int *__restrict__ faces, int B, int F, int NV, int width,
-                  int height, float *__restrict__ zbuf) {
+                  int height, float *__restrict__ zbuf, int *__restrict__ owner = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave_global = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int groups = (F + kFacesPerWave - 1) / kFacesPerWave;
   const int b = wave_global / groups;
   if (b >= B) return;
-  const int fidx = (wave_global - b * groups) * kFacesPerWave + lane;
+  const int fbase = (wave_global - b * groups) * kFacesPerWave, fidx = fbase + lane;
   float f[9];
   const bool have = lane < kFacesPerWave && fidx < F;
   if (have) {
@@ -236,8 +241,14 @@ tri_raster_kernel(const float *__restrict__ src, const int *__restrict__ faces, 
   const FaceSetup s = face_setup(f, width, height);
   float *zimg = zbuf + (size_t)b * width * height;
   __shared__ __attribute__((aligned(16))) unsigned char s_scratch[4][kWaveScratchBytes];
+  int *oimg = OWNER ? owner + (size_t)b * width * height : nullptr;
   raster_batch<kFacesPerWave, SHR_TRI_ATOMIC_LEVELS != 0>(s, have, lane, s_scratch[threadIdx.x >> 6], height,
-               [&](int xi, int yi, float zp) { zmin(zimg + (size_t)yi * width + xi, zp); });
+               [&](int xi, int yi, float zp, int slot) {
+                 const size_t i = (size_t)yi * width + xi;
+                 if (!OWNER) zmin(zimg + i, zp);
+                 else if (__float_as_uint(zp) == __float_as_uint(zimg[i]))
+                   atomicMin(reinterpret_cast<unsigned int *>(oimg + i), (unsigned)(fbase + slot));
+               });
 }
 
 // ---- the band kernel (round 5) ----------------------------------------------------------------------------------
@@ -276,17 +287,25 @@ __device__ __forceinline__ uint32_t face_row_range(const float (&f)[9], int widt
 // from [k p_src, (k + 1) p_src) (down-sampling: scale > 1), so bands of a multiple of p_src rows hold every tap of their
 // own output rows: zbuf = out [B][S][S], R % p_src == 0, square images.  The rasterized values are the full-resolution
 // kernel's (same code), the epilogue is mesh_depth_kernel's formula: the same bits as raster -> clamp -> F.interpolate.
-template <bool INDEXED, bool RESIZE = false>
+// OWNER (shr_tri_raster_owner_fwd): the band's cells are 64-bit minima (mkey(depth) << 32 | face), mesh_depth_tile's
+// OWNER slots: the same depth bits, plus owner[B][H][W] = the face of the smallest offered depth, ties to the smaller
+// face index, -1 where no face offered one (the fill's face word is 0xFFFFFFFF).  Twice the LDS per band row.
+template <bool INDEXED, bool RESIZE = false, bool OWNER = false>
 __global__ void __launch_bounds__(kBandWaves * 64)
 tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, int B, int F, int NV, int width, int height,
-                float *__restrict__ zbuf, int R, int nbands, int S = 0, int p_src = 1, int p_out = 1, float clamp_max = 0.f) {
+                float *__restrict__ zbuf, int R, int nbands, int S = 0, int p_src = 1, int p_out = 1, float clamp_max = 0.f,
+                int *__restrict__ owner = nullptr) {
+  static_assert(!(RESIZE && OWNER), "the owner raster is full-size");
+  constexpr int kCell = OWNER ? 8 : 4;
+  constexpr unsigned long long kFillSlot = ((unsigned long long)(kFillBits ^ 0x80000000u) << 32) | 0xFFFFFFFFull;   // mkey(1000), no face
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int Fpad = (F + 7) & ~7;
   uint32_t *s_range = reinterpret_cast<uint32_t *>(smem);
   uint16_t *s_pend = reinterpret_cast<uint16_t *>(smem + (size_t)Fpad * 4);          // the faces that reach the current band
   float *s_band = reinterpret_cast<float *>(smem + (size_t)Fpad * 6);
+  unsigned long long *s_band64 = reinterpret_cast<unsigned long long *>(smem + (size_t)Fpad * 6);   // (OWNER; Fpad * 6 % 16 == 0)
   // (the band rounded up to 16 bytes: the scratch is read through float4 / uint2 -- odd widths would leave it 4-byte aligned)
-  unsigned char *s_scr = smem + (size_t)Fpad * 6 + (((size_t)R * width * 4 + 15) & ~(size_t)15);
+  unsigned char *s_scr = smem + (size_t)Fpad * 6 + (((size_t)R * width * kCell + 15) & ~(size_t)15);
   __shared__ int s_bandcnt[kBandMaxBands];
   __shared__ int s_npend;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -294,6 +313,7 @@ tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, in
   // share of the hand's rows and of the empty ones (consecutive bands: the top and bottom segments were nearly free)
   const int band_first = blockIdx.y, band_step = gridDim.y;
   float *zimg = RESIZE ? zbuf + (size_t)b * S * S : zbuf + (size_t)b * width * height;
+  int *oimg = OWNER ? owner + (size_t)b * width * height : nullptr;
   const bool counted = nbands <= kBandMaxBands;
   for (int i = tid; i < min(nbands, kBandMaxBands); i += kBandWaves * 64) s_bandcnt[i] = 0;
   __syncthreads();
@@ -322,7 +342,11 @@ tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, in
     // RESIZE: the band's output rows [oy_lo, oy_lo + orows)
     const int oy_lo = RESIZE ? (lo / p_src) * p_out : 0, orows = RESIZE ? (rows / p_src) * p_out : 0;
     float *gout = RESIZE ? zimg + (size_t)oy_lo * S : zimg + (size_t)lo * width;
+    int *oout = OWNER ? oimg + (size_t)lo * width : nullptr;
     if (counted && s_bandcnt[band] == 0) {          // no face reaches the band (workgroup-uniform)
+      if (OWNER) {
+        for (int i = tid; i < npix; i += kBandWaves * 64) { gout[i] = __uint_as_float(kFillBits); oout[i] = -1; }
+      } else
       if (RESIZE) {                                 // every tap is the clamped background: min(1000, clamp_max) exactly
         const float bgv = fminf(__uint_as_float(kFillBits), clamp_max);
         for (int i = tid; i < orows * S; i += kBandWaves * 64) gout[i] = bgv;
@@ -339,6 +363,9 @@ tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, in
     // the faces that reach the band, collected by ALL waves into one list (face numbers cluster: a wave's own chunks
     // hold all of a band's faces or none), then dealt out in equal shares
     if (tid == 0) s_npend = 0;
+    if (OWNER) {
+      for (int i = tid; i < npix; i += kBandWaves * 64) s_band64[i] = kFillSlot;
+    } else
     if (vec4) {
       const float4 fv = make_float4(__uint_as_float(kFillBits), __uint_as_float(kFillBits), __uint_as_float(kFillBits),
                                     __uint_as_float(kFillBits));
@@ -361,12 +388,7 @@ tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, in
     }
     __syncthreads();
     float *cells = s_band - (size_t)lo * width;      // cell of pixel (yi, xi) = cells[yi * width + xi]
-    auto sink = [&](int xi, int yi, float zp) {
-      float *cell = cells + yi * width + xi;
-      const uint32_t bits = __float_as_uint(zp);
-      if (bits >> 31) atomicMax(reinterpret_cast<unsigned int *>(cell), bits);   // (zmin's rule on an LDS cell)
-      else atomicMin(reinterpret_cast<int *>(cell), (int)bits);
-    };
+    unsigned long long *cells64 = s_band64 - (size_t)lo * width;
     {
       // equal shares of the list, 16 faces at a time.  (Drawing batches of 16 from a counter instead -- a face costs what
       // its box holds -- measured 1022 us against 634 for 256 crops: a batch costs its LATENCY, the gather of its
@@ -389,11 +411,29 @@ tri_band_kernel(const float *__restrict__ src, const int *__restrict__ faces, in
         FaceSetup fs = face_setup(f, width, height);
         fs.r_lo = max(fs.r_lo, lo);
         fs.r_hi = min(fs.r_hi, hi);
+        auto sink = [&](int xi, int yi, float zp, int slot) {
+          if (OWNER) {   // (the face that lane `slot` brought: entry wave + 16 (at + slot) of the list)
+            const uint32_t face = s_pend[wave + kBandWaves * (at + slot)];
+            atomicMin(cells64 + yi * width + xi, ((unsigned long long)mkey(zp) << 32) | face);
+            return;
+          }
+          float *cell = cells + yi * width + xi;
+          const uint32_t bits = __float_as_uint(zp);
+          if (bits >> 31) atomicMax(reinterpret_cast<unsigned int *>(cell), bits);   // (zmin's rule on an LDS cell)
+          else atomicMin(reinterpret_cast<int *>(cell), (int)bits);
+        };
         raster_batch<kBandFaces, SHR_TRI_BAND_LEVELS != 0>(fs, have, lane, scratch, height, sink);
       }
     }
     __syncthreads();
     // stream the band out
+    if (OWNER) {
+      for (int i = tid; i < npix; i += kBandWaves * 64) {
+        const unsigned long long v = s_band64[i];
+        gout[i] = mkey_inv((uint32_t)(v >> 32));
+        oout[i] = (int)(uint32_t)v;
+      }
+    } else
     if (RESIZE) {
       const float scale = (float)height / (float)S;
       for (int i = tid; i < orows * S; i += kBandWaves * 64) {
@@ -478,9 +518,10 @@ using namespace shr;
 static int g_tri_band = -1;   // SHR_TUNE_TRI_BAND: -1 = by batch size (below), 0 = never (the global-atomic kernel), n > 0 = always, bands of <= n rows
 int shr::tri_set_band(int v) { g_tri_band = v; return SHR_OK; }
 
-// resize_S > 0: the band kernel with the clamp + resize epilogue (RESIZE above; depth = [B][S][S]); -1 when it does not fit
+// resize_S > 0: the band kernel with the clamp + resize epilogue (RESIZE above; depth = [B][S][S]); -1 when it does not fit.
+// owner != nullptr: the owner raster (OWNER above; owner = [B][H][W]).
 static int tri_raster_common(bool indexed, const float *src, const int *faces, int B, int F, int NV, int W, int H,
-                             float *depth, hipStream_t s, int resize_S = 0, float clamp_max = 0.f) {
+                             float *depth, hipStream_t s, int resize_S = 0, float clamp_max = 0.f, int *owner = nullptr) {
   int p_src = 1, p_out = 1;
   if (resize_S > 0) {
     if (W != H || resize_S >= H) return -1;   // (scale 1: the second tap, weight 0, is the NEXT period's first row)
@@ -489,10 +530,11 @@ static int tri_raster_common(bool indexed, const float *src, const int *faces, i
     p_src = H / a; p_out = resize_S / a;
   }
   // The band kernel: the row ranges of all faces (4 F bytes) + sixteen wave scratches + a band of at least 8 rows
-  // in one CU's LDS, 16-bit face numbers and row numbers.
+  // in one CU's LDS, 16-bit face numbers and row numbers.  (The owner raster's cells are 8 bytes: half the rows.)
   constexpr int kLds = 160 * 1024;
+  const int cell = owner ? 8 : 4;
   const long long fixed = (long long)((F + 7) & ~7) * 6 + (long long)kBandWaves * kBandScratchBytes + 4096 + 16;   // (+ the static arrays: band counters, pending faces; + the band's rounding to 16 bytes)
-  long long Rmax = (kLds - fixed) / (4LL * W);
+  long long Rmax = (kLds - fixed) / ((long long)cell * W);
   if (Rmax > H) Rmax = H;
   Rmax -= Rmax % p_src;                                  // (resize: whole periods of source rows per band)
   if (resize_S > 0 && (Rmax < p_src || g_tri_band == 0 || !(F > 0 && F <= 65535 && H <= 65535))) return -1;
@@ -541,16 +583,17 @@ static int tri_raster_common(bool indexed, const float *src, const int *faces, i
     const int nbands = (H + R - 1) / R;
     if (segs > nbands) segs = nbands;
     if (segs > 65535) segs = 65535;
-    const size_t lds = (size_t)((F + 7) & ~7) * 6 + (((size_t)R * W * 4 + 15) & ~(size_t)15) + (size_t)kBandWaves * kBandScratchBytes;
-    static AttrDone attr_done[4];   // per (kernel, device)
+    const size_t lds = (size_t)((F + 7) & ~7) * 6 + (((size_t)R * W * cell + 15) & ~(size_t)15) + (size_t)kBandWaves * kBandScratchBytes;
+    static AttrDone attr_done[6];   // per (kernel, device)
     auto launch = [&](auto kernel, int which) -> int {
       const hipError_t e = allow_dynamic_lds(kernel, kLds - 4096, &attr_done[which]);   // (the static arrays take the rest)
       if (e != hipSuccess) return (int)e;
       hipLaunchKernelGGL(kernel, dim3((unsigned)B, (unsigned)segs), dim3(kBandWaves * 64), lds, s, src, faces, B, F, NV, W, H,
-                         depth, R, nbands, resize_S, p_src, p_out, clamp_max);
+                         depth, R, nbands, resize_S, p_src, p_out, clamp_max, owner);
       return (int)hipGetLastError();
     };
     if (resize_S > 0) return indexed ? launch(tri_band_kernel<true, true>, 2) : launch(tri_band_kernel<false, true>, 3);
+    if (owner) return indexed ? launch(tri_band_kernel<true, false, true>, 4) : launch(tri_band_kernel<false, false, true>, 5);
     return indexed ? launch(tri_band_kernel<true>, 0) : launch(tri_band_kernel<false>, 1);
   }
   if (resize_S > 0) return -1;
@@ -564,13 +607,22 @@ static int tri_raster_common(bool indexed, const float *src, const int *faces, i
   const unsigned fill_blocks = (unsigned)(want_blocks > 16384 ? 16384 : (want_blocks ? want_blocks : 1));
   hipLaunchKernelGGL(zbuf_fill_kernel, dim3(fill_blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(z), n4,
                      0x447A0000u /* 1000.0f, .cu:122 */, z + n4 * 4, ntail);
+  if (owner) {   // (-1: no face; the depth's layout, 16-byte aligned)
+    uint32_t *o = reinterpret_cast<uint32_t *>(owner);
+    hipLaunchKernelGGL(zbuf_fill_kernel, dim3(fill_blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(o), n4, 0xFFFFFFFFu,
+                       o + n4 * 4, ntail);
+  }
   if (F > 0) {
     const long long waves = (long long)B * ((F + kFacesPerWave - 1) / kFacesPerWave);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
     if (indexed)
-      hipLaunchKernelGGL(tri_raster_kernel<true>, dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth);
+      hipLaunchKernelGGL(tri_raster_kernel<true>, dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth, nullptr);
     else
-      hipLaunchKernelGGL(tri_raster_kernel<false>, dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth);
+      hipLaunchKernelGGL(tri_raster_kernel<false>, dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth, nullptr);
+    if (owner && indexed)   // the second pass: the finished depth -> the faces that offered it
+      hipLaunchKernelGGL((tri_raster_kernel<true, true>), dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth, owner);
+    else if (owner)
+      hipLaunchKernelGGL((tri_raster_kernel<false, true>), dim3(blocks), dim3(256), 0, s, src, faces, B, F, NV, W, H, depth, owner);
   }
   return (int)hipGetLastError();
 }
@@ -600,6 +652,26 @@ extern "C" int shr_tri_raster_indexed_fwd(const float *vertices, const int32_t *
     return SHR_ETOOLARGE;
   if ((((uintptr_t)depth | (uintptr_t)vertices) & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(true, vertices, faces, B, F, NV, W, H, depth, (hipStream_t)stream);
+}
+
+extern "C" int shr_tri_raster_owner_fwd(const float *face_vertices, int B, int F, int W, int H, float *depth, int32_t *owner,
+                                        void *stream) {
+  if (B == 0) return SHR_OK;
+  if (!depth || !owner || (!face_vertices && F > 0) || B < 0 || F < 0 || W <= 0 || H <= 0) return SHR_EINVAL;
+  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
+    return SHR_ETOOLARGE;
+  if ((((uintptr_t)depth | (uintptr_t)owner) & 15u) != 0) return SHR_EINVAL;
+  return tri_raster_common(false, face_vertices, nullptr, B, F, 0, W, H, depth, (hipStream_t)stream, 0, 0.f, owner);
+}
+
+extern "C" int shr_tri_raster_indexed_owner_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int W,
+                                                int H, float *depth, int32_t *owner, void *stream) {
+  if (B == 0) return SHR_OK;
+  if (!depth || !owner || !vertices || (!faces && F > 0) || B < 0 || F < 0 || NV <= 0 || W <= 0 || H <= 0) return SHR_EINVAL;
+  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
+    return SHR_ETOOLARGE;
+  if ((((uintptr_t)depth | (uintptr_t)owner | (uintptr_t)vertices) & 15u) != 0) return SHR_EINVAL;
+  return tri_raster_common(true, vertices, faces, B, F, NV, W, H, depth, (hipStream_t)stream, 0, 0.f, owner);
 }
 
 extern "C" int shr_lbs_project(const float *T, int B, int NB, int NV, const int32_t *skin_vertex_start,

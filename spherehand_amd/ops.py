@@ -911,6 +911,122 @@ class MeshDepthRender(torch.autograd.Function):
         return (grad_T,) + (None,) * 10
 
 
+def _soup_shape(face_vertices):
+    _check_input(face_vertices, "face_vertices")
+    if face_vertices.dim() != 4 or tuple(face_vertices.shape[2:]) != (3, 3):
+        raise RuntimeError("face_vertices must be [B,F,3,3]")
+    return face_vertices.shape[0], face_vertices.shape[1]
+
+
+def _indexed_shape(vertices, faces):
+    _check_input(vertices, "vertices")
+    _check_input(faces, "faces", torch.int32)
+    if vertices.dim() != 3 or vertices.shape[2] != 4 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("vertices must be [B,NV,4] and faces [F,3]")
+    return vertices.shape[0], vertices.shape[1], faces.shape[0]
+
+
+def tri_raster_owner_fwd(width, height, face_vertices):
+    """tri_raster_fwd's depth [B,height,width] (the same bits) + owner [B,height,width] int32: the face whose offered
+    depth is the pixel's (ties to the smaller index), -1 for background."""
+    B, F = _soup_shape(face_vertices)
+    with _on(face_vertices.device):
+        depth = torch.empty((B, height, width), dtype=torch.float32, device=face_vertices.device)
+        owner = torch.empty((B, height, width), dtype=torch.int32, device=face_vertices.device)
+        _lib.check(_lib.lib().shr_tri_raster_owner_fwd(_ptr(face_vertices), B, F, width, height, _ptr(depth), _ptr(owner),
+                                                       _stream()), "shr_tri_raster_owner_fwd")
+    return depth, owner
+
+
+def tri_raster_indexed_owner_fwd(width, height, vertices, faces):
+    """tri_raster_indexed_fwd's depth [B,height,width] (the same bits) + owner [B,height,width] int32 (as above)."""
+    B, NV, F = _indexed_shape(vertices, faces)
+    with _on(vertices.device):
+        depth = torch.empty((B, height, width), dtype=torch.float32, device=vertices.device)
+        owner = torch.empty((B, height, width), dtype=torch.int32, device=vertices.device)
+        _lib.check(_lib.lib().shr_tri_raster_indexed_owner_fwd(_ptr(vertices), _ptr(faces), B, NV, F, width, height,
+                                                               _ptr(depth), _ptr(owner), _stream()),
+                   "shr_tri_raster_indexed_owner_fwd")
+    return depth, owner
+
+
+def _check_pixel_grad(owner, grad_depth, B):
+    _check_input(owner, "owner", torch.int32)
+    _check_input(grad_depth, "grad_depth")
+    if grad_depth.dim() != 3 or grad_depth.shape[0] != B or owner.shape != grad_depth.shape:
+        raise RuntimeError("grad_depth and owner must both be [B,H,W] with the vertices' B")
+    return grad_depth.shape[2], grad_depth.shape[1]
+
+
+def tri_raster_bwd(face_vertices, owner, grad_depth):
+    """d<grad_depth, depth>/d face_vertices [B,F,3,3] through each pixel's owner face (coverage held fixed);
+    deterministic fixed-point sums."""
+    B, F = _soup_shape(face_vertices)
+    W, H = _check_pixel_grad(owner, grad_depth, B)
+    lib = _lib.lib()
+    with _on(face_vertices.device):
+        out = torch.empty((B, F, 3, 3), dtype=torch.float32, device=face_vertices.device)
+        ws = torch.empty((max(16, lib.shr_tri_raster_bwd_workspace_bytes(B, F)),), dtype=torch.uint8,
+                         device=face_vertices.device)
+        _lib.check(lib.shr_tri_raster_bwd(_ptr(face_vertices), _ptr(owner), _ptr(grad_depth), B, F, W, H, _ptr(out), _ptr(ws),
+                                          _stream()), "shr_tri_raster_bwd")
+    return out
+
+
+def tri_raster_indexed_bwd(vertices, faces, owner, grad_depth):
+    """d<grad_depth, depth>/d vertices [B,NV,4] = (du, dv, dz, 0) through each pixel's owner face (coverage held
+    fixed); deterministic fixed-point sums."""
+    B, NV, F = _indexed_shape(vertices, faces)
+    W, H = _check_pixel_grad(owner, grad_depth, B)
+    lib = _lib.lib()
+    with _on(vertices.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=vertices.device)
+        ws = torch.empty((max(16, lib.shr_tri_raster_indexed_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
+                         device=vertices.device)
+        _lib.check(lib.shr_tri_raster_indexed_bwd(_ptr(vertices), _ptr(faces), _ptr(owner), _ptr(grad_depth), B, NV, F, W, H,
+                                                  _ptr(out), _ptr(ws), _stream()), "shr_tri_raster_indexed_bwd")
+    return out
+
+
+class TriRaster(torch.autograd.Function):
+    """depth_rasterization.forward with a backward: face_vertices [B,F,3,3] (pixel-space x, y, z) -> raw depth
+    [B,height,width], background 1000, the same bits.  Differentiable w.r.t. face_vertices: each pixel's gradient goes
+    to the face that owns its depth, coverage held fixed (no edge, silhouette or visibility gradient)."""
+
+    @staticmethod
+    def forward(ctx, face_vertices, width, height):
+        face_vertices = face_vertices.contiguous()
+        depth, owner = tri_raster_owner_fwd(width, height, face_vertices)
+        ctx.save_for_backward(face_vertices, owner)
+        return depth
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        face_vertices, owner = ctx.saved_tensors
+        return tri_raster_bwd(face_vertices, owner, grad_depth.contiguous().float()), None, None
+
+
+class TriRasterIndexed(torch.autograd.Function):
+    """TriRaster on an indexed mesh: vertices [B,NV,3 or 4] (pixel space) + faces [F,3] int32 -> raw depth
+    [B,height,width], the bits of tri_raster_indexed_fwd; differentiable w.r.t. vertices[..., :3]."""
+
+    @staticmethod
+    def forward(ctx, vertices, faces, width, height):
+        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+        ctx.width4 = vertices.shape[-1] == 4
+        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        depth, owner = tri_raster_indexed_owner_fwd(width, height, v4, faces)
+        ctx.save_for_backward(v4, faces, owner)
+        return depth
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        v4, faces, owner = ctx.saved_tensors
+        g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
+        return (g if ctx.width4 else g[..., :3]), None, None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

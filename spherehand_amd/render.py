@@ -6,6 +6,7 @@ signatures and return values), running on the hand-written HIP kernels.
     HandBallPrimitiveRender  mesh/render.py:56-90
     DataToModelLoss          mesh/render.py:93-142
     DepthRasterizationFunction / DepthRasterization / DepthRender  mesh/render.py:282-331
+    TriangleDepthRaster      depth_rasterization.forward, differentiable at any width x height
 """
 import numpy as np
 import torch
@@ -175,6 +176,37 @@ class DepthRasterization(nn.Module):
             rendered_dm = DepthRasterizationFunction.apply(640, 640, face_vertices).unsqueeze(1)
         return torch.nn.functional.interpolate(rendered_dm, size=(self.height, self.width), mode='bilinear',
                                                align_corners=False).squeeze(1)
+
+
+class TriangleDepthRaster(nn.Module):
+    """depth_rasterization.forward (mesh/cuda_kernel/depth_rasterization_cuda_kernel.cu:18-134) on an indexed mesh, at
+    its own resolution and differentiable.  forward(vertices[B,NV,>=3], pixel-space x, y, z) -> the RAW depth
+    [B,height,width], background 1000, with no clamp and no resize, bit-identical to the forward-only raster.  Any
+    width x height the raster takes.  `np_faces` gets the right hand's winding swap that DepthRasterization applies
+    (mesh/render.py:298-300) and is not modified.
+
+    Where grad is enabled and `vertices` requires grad, the depth is differentiable w.r.t. vertices[..., :3]
+    (ops.TriRasterIndexed; ops.TriRaster takes face soups [B,F,3,3]).  Each pixel's gradient goes to the face that owns
+    its depth and coverage is held fixed: there is no edge, silhouette or visibility gradient.  Clamp the result in torch
+    as the reference does (torch.clamp(depth, max=100.0) passes the gradient at equality)."""
+
+    def __init__(self, width, height, np_faces, right_hand=True):
+        super().__init__()
+        self.width = width
+        self.height = height
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+
+    def forward(self, vertices):
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("TriangleDepthRaster takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        if v.requires_grad and torch.is_grad_enabled():
+            return ops.TriRasterIndexed.apply(v, self.faces_i32, self.width, self.height)
+        v4 = v if v.shape[-1] == 4 else torch.nn.functional.pad(v, (0, 1))
+        return ops.tri_raster_indexed_fwd(self.width, self.height, v4.contiguous(), self.faces_i32)
 
 
 class SparseSkinning(nn.Module):
