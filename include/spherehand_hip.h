@@ -501,6 +501,50 @@ int shr_tri_raster_bwd(const float *face_vertices, const int32_t *owner, const f
 int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *faces, const int32_t *owner, const float *grad_depth,
                                int B, int NV, int F, int W, int H, float *grad_vertices, void *workspace, void *stream);
 
+/* Antialias pass of the triangle raster (a capability the reference does not have; the edge-blending step of modular
+ * differentiable rasterizers): a crop's values blended across the silhouette edges of the faces that own its pixels, so
+ * that the output is continuous in the vertices' x, y and has a gradient at the outline.  The hard raster is unchanged.
+ * Pixel (x, y) is sampled at integer (x, y), x = column, y = row; smaller depth is nearer.  Per crop b:
+ *   values c[B,H,W]       what is antialiased (e.g. clamp(raw, max=100) or a 0/1 coverage mask)
+ *   depth d[B,H,W], owner[B,H,W]   the raw depth and owners of shr_tri_raster_indexed_owner_fwd (-1: background)
+ *   vertices[B,NV,4]      pixel-space (x, y, z, -), 16-byte aligned; faces[F,3] as the raster took them
+ *   edges[F,3]            edge k of face f joins corners k and (k + 1) % 3; edges[f,k] is the other face that shares this
+ *                         undirected edge (corners matched on welded ids), -1 when none or when three or more share it.
+ *                         Values outside [0, F) count as -1.  (ops.tri_edge_table builds it on the host.)
+ * A face is DRAWN when face_sort accepts it: front-facing by the reference's cull (.cu:33) and x0 != x2 (.cu:54), its
+ * vertex ids inside [0, NV).  Edge k of a drawn face t is a SILHOUETTE edge when edges[t,k] == -1 or the face across it
+ * is not drawn.
+ * PAIRS: every 4-neighbour pair inside the image, (p, p + (1, 0)) and (p, p + (0, 1)), with owner(p) != owner(q):
+ *   1. the front pixel f is the one with owner >= 0 and the smaller raw depth (equal depth bits: p); o is the other,
+ *      sigma = +-1 the sign of the step from f to o along the pair's axis, t = owner(f) (outside [0, F): no blend).
+ *   2. edge A -> B of t qualifies when it is a silhouette edge, and, for a horizontal pair at row y:
+ *      |y_B - y_A| >= |x_B - x_A|, y_A != y_B, min(y_A, y_B) <= y <= max(y_A, y_B), and the crossing
+ *          x_c = x_A + ((y - y_A) * (x_B - x_A)) / (y_B - y_A)            (fp32, in this order)
+ *      gives s = sigma (x_c - x_f) with 0 <= s <= 1.  A vertical pair at column x: the same with x and y swapped and the
+ *      strict |x_B - x_A| > |y_B - y_A|, so that each edge blends along one axis only.  The smallest qualifying k wins.
+ *   3. with a qualifying edge: s >= 1/2: o gains (s - 1/2)(c_f - c_o); s < 1/2: f gains (1/2 - s)(c_o - c_f).  Gains
+ *      are computed from the input values only.
+ *   out[p] = (((c[p] + gain_left) + gain_right) + gain_up) + gain_down in fp32, over the pairs (p - (1, 0), p),
+ *   (p, p + (1, 0)), (p - (0, 1), p), (p, p + (0, 1)) in which p gains; a pixel that gains nothing is a bitwise copy.
+ *   shr_tri_antialias_fwd   -> out[B,H,W] (not aliasing values)
+ *   shr_tri_antialias_bwd   grad_out[B,H,W] -> grad_values[B,H,W] and grad_vertices[B,NV,4] = (d/dx, d/dy, 0, 0); either
+ *       output may be NULL (not both).  Both branches of 3. give d gain / d s = c_f - c_o; for a horizontal pair, with
+ *       u = (y - y_A) / (y_B - y_A) and m = (x_B - x_A) / (y_B - y_A), ds/dx_A = sigma (1 - u), ds/dx_B = sigma u,
+ *       ds/dy_A = -sigma m (1 - u), ds/dy_B = -sigma m u (vertical pairs: x and y swapped); no gradient to depth, owner
+ *       or z.  grad_values is a per-pixel gather in the forward's order: grad_out[p] + sum over p's qualifying pairs of
+ *       grad_out[gaining pixel] * (p == f ? s - 1/2 : 1/2 - s).  The vertex terms go to faces[t,k] and faces[t,(k+1)%3]
+ *       in shr_tri_raster_indexed_bwd's 64-bit fixed point (a per-crop unit computed on the device): bitwise
+ *       reproducible, independent of the batch, no host synchronisation.  workspace: 16-byte aligned,
+ *       shr_tri_antialias_bwd_workspace_bytes(B, NV) bytes (only with grad_vertices), cleared by the call itself.
+ *   B, W, H <= 65535 (SHR_ETOOLARGE beyond). */
+int shr_tri_antialias_fwd(const float *values, const float *depth, const int32_t *owner, const float *vertices,
+                          const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H, float *out,
+                          void *stream);
+long long shr_tri_antialias_bwd_workspace_bytes(int B, int NV);
+int shr_tri_antialias_bwd(const float *values, const float *depth, const int32_t *owner, const float *vertices,
+                          const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H,
+                          const float *grad_out, float *grad_values, float *grad_vertices, void *workspace, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

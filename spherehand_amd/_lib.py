@@ -86,6 +86,9 @@ SIGNATURES = {
     "shr_tri_raster_indexed_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "shr_tri_raster_bwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "shr_tri_raster_indexed_bwd": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "shr_tri_antialias_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "shr_tri_antialias_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_tri_antialias_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_fk_fwd": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -6,6 +6,7 @@ Preconditions mirror the reference extension's CHECK_INPUT
 (mesh/cuda_kernel/depth_rasterization_cuda.cpp:11-19): a violation raises
 RuntimeError.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -1025,6 +1026,134 @@ class TriRasterIndexed(torch.autograd.Function):
         v4, faces, owner = ctx.saved_tensors
         g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
         return (g if ctx.width4 else g[..., :3]), None, None, None
+
+
+class TriRasterIndexedOwner(torch.autograd.Function):
+    """TriRasterIndexed that also returns the owners: (raw depth [B,height,width], differentiable w.r.t.
+    vertices[..., :3] exactly as TriRasterIndexed, owner [B,height,width] int32, not differentiable) -- one owner forward
+    for both the raster's backward and the antialias pass (TriAntialias)."""
+
+    @staticmethod
+    def forward(ctx, vertices, faces, width, height):
+        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+        ctx.width4 = vertices.shape[-1] == 4
+        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        depth, owner = tri_raster_indexed_owner_fwd(width, height, v4, faces)
+        ctx.save_for_backward(v4, faces, owner)
+        ctx.mark_non_differentiable(owner)
+        return depth, owner
+
+    @staticmethod
+    def backward(ctx, grad_depth, _grad_owner):
+        v4, faces, owner = ctx.saved_tensors
+        g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
+        return (g if ctx.width4 else g[..., :3]), None, None, None
+
+
+def tri_edge_table(faces, weld=None):
+    """The antialias pass's edge table (host, numpy): faces [F,3] (as the raster takes them: after the right hand's
+    winding swap) -> edges [F,3] int32.  Edge k of face f joins corners k and (k + 1) % 3; edges[f,k] is the other face
+    that shares this undirected edge, -1 when no other face shares it or when three or more do (a boundary).  Corners
+    are matched on welded ids: `weld` None (the faces' own ids), an integer array [NV] (vertex -> point id), or a float
+    array [NV,C] of positions (vertices with bit-identical rows are one point)."""
+    f = np.asarray(faces.cpu().numpy() if isinstance(faces, torch.Tensor) else faces).astype(np.int64)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise RuntimeError("faces must be [F,3]")
+    if weld is not None:
+        w = np.asarray(weld.cpu().numpy() if isinstance(weld, torch.Tensor) else weld)
+        if w.dtype.kind == "f":
+            rows = np.ascontiguousarray(w.reshape(len(w), -1))
+            _, w = np.unique(rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).ravel(),
+                             return_inverse=True)
+        w = np.asarray(w, np.int64).ravel()
+        if len(f) and (f.min() < 0 or f.max() >= len(w)):
+            raise RuntimeError("faces index outside the welded vertices")
+        f = w[f]
+    F = len(f)
+    a, b = f, f[:, [1, 2, 0]]
+    key = np.stack([np.minimum(a, b), np.maximum(a, b)], -1).reshape(-1, 2)      # row 3 f + k: edge k of face f
+    _, grp, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    grp = grp.ravel()
+    edges = np.full(3 * F, -1, np.int64)
+    two = np.nonzero(cnt[grp] == 2)[0]
+    order = two[np.argsort(grp[two], kind="stable")]                         # the two rows of each group, adjacent
+    first, second = order[0::2], order[1::2]
+    edges[first], edges[second] = second // 3, first // 3
+    return edges.reshape(F, 3).astype(np.int32)
+
+
+def _aa_shape(values, depth, owner, vertices, faces, edges):
+    _check_input(values, "values")
+    _check_input(depth, "depth")
+    _check_input(owner, "owner", torch.int32)
+    B, NV, F = _indexed_shape(vertices, faces)
+    _check_input(edges, "edges", torch.int32)
+    if values.dim() != 3 or values.shape[0] != B or depth.shape != values.shape or owner.shape != values.shape:
+        raise RuntimeError("values, depth and owner must all be [B,H,W] with the vertices' B")
+    if tuple(edges.shape) != (F, 3):
+        raise RuntimeError("edges must be [F,3]")
+    return B, NV, F, values.shape[2], values.shape[1]
+
+
+def tri_antialias(values, depth, owner, vertices, faces, edges):
+    """The antialias pass (include/spherehand_hip.h, shr_tri_antialias_fwd): values [B,H,W] blended across the
+    silhouette edges of the owner faces -> [B,H,W]; depth, owner from tri_raster_indexed_owner_fwd, vertices [B,NV,4]
+    pixel space, faces [F,3] int32, edges [F,3] int32 (tri_edge_table)."""
+    B, NV, F, W, H = _aa_shape(values, depth, owner, vertices, faces, edges)
+    with _on(values.device):
+        out = torch.empty_like(values)
+        _lib.check(_lib.lib().shr_tri_antialias_fwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
+                                                    _ptr(edges), B, NV, F, W, H, _ptr(out), _stream()),
+                   "shr_tri_antialias_fwd")
+    return out
+
+
+def tri_antialias_bwd(values, depth, owner, vertices, faces, edges, grad_out, want_values=True, want_vertices=True):
+    """tri_antialias's backward: (grad_values [B,H,W] or None, grad_vertices [B,NV,4] = (d/dx, d/dy, 0, 0) or None);
+    the vertex sums are deterministic fixed point."""
+    B, NV, F, W, H = _aa_shape(values, depth, owner, vertices, faces, edges)
+    _check_input(grad_out, "grad_out")
+    if grad_out.shape != values.shape:
+        raise RuntimeError("grad_out must be [B,H,W] as values")
+    if not (want_values or want_vertices):
+        return None, None
+    lib = _lib.lib()
+    with _on(values.device):
+        gvals = torch.empty_like(values) if want_values else None
+        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=values.device) if want_vertices else None
+        ws = torch.empty((max(16, lib.shr_tri_antialias_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
+                         device=values.device) if want_vertices else None
+        _lib.check(lib.shr_tri_antialias_bwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
+                                             _ptr(edges), B, NV, F, W, H, _ptr(grad_out), _ptr(gvals), _ptr(gverts),
+                                             _ptr(ws), _stream()), "shr_tri_antialias_bwd")
+    return gvals, gverts
+
+
+class TriAntialias(torch.autograd.Function):
+    """tri_antialias with a backward: (values [B,H,W], depth, owner, vertices [B,NV,3 or 4] pixel space, faces, edges)
+    -> the antialiased values.  Differentiable w.r.t. values and vertices[..., :2] (the z gradient is zero); depth and
+    owner get none."""
+
+    @staticmethod
+    def forward(ctx, values, depth, owner, vertices, faces, edges):
+        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+        ctx.width4 = vertices.shape[-1] == 4
+        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        values, depth, owner = values.contiguous(), depth.contiguous(), owner.contiguous()
+        out = tri_antialias(values, depth, owner, v4, faces, edges)
+        ctx.save_for_backward(values, depth, owner, v4, faces, edges)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        values, depth, owner, v4, faces, edges = ctx.saved_tensors
+        gvals, gverts = tri_antialias_bwd(values, depth, owner, v4, faces, edges, grad_out.contiguous().float(),
+                                          ctx.needs_input_grad[0], ctx.needs_input_grad[3])
+        if gverts is not None and not ctx.width4:
+            gverts = gverts[..., :3]
+        return gvals, None, None, gverts, None, None
 
 
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,

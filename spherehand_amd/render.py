@@ -7,6 +7,7 @@ signatures and return values), running on the hand-written HIP kernels.
     DataToModelLoss          mesh/render.py:93-142
     DepthRasterizationFunction / DepthRasterization / DepthRender  mesh/render.py:282-331
     TriangleDepthRaster      depth_rasterization.forward, differentiable at any width x height
+    AntialiasedDepthRaster   the same, clamped and antialiased: gradients at the silhouette too
 """
 import numpy as np
 import torch
@@ -207,6 +208,48 @@ class TriangleDepthRaster(nn.Module):
             return ops.TriRasterIndexed.apply(v, self.faces_i32, self.width, self.height)
         v4 = v if v.shape[-1] == 4 else torch.nn.functional.pad(v, (0, 1))
         return ops.tri_raster_indexed_fwd(self.width, self.height, v4.contiguous(), self.faces_i32)
+
+
+class AntialiasedDepthRaster(nn.Module):
+    """TriangleDepthRaster's depth, clamped and then antialiased across the silhouette (ops.TriAntialias;
+    include/spherehand_hip.h states the pass): forward(vertices[B,NV,>=3], pixel-space x, y, z) returns
+    clamp(raw, max=clamp_max) [B,height,width] with the pixel pairs that straddle a silhouette edge blended by where the
+    edge crosses between their centres.  Differentiable w.r.t. vertices[..., :3]: interior gradients through the faces
+    that own the pixels (TriangleDepthRaster's contract), outline gradients in x, y through the pass.
+    silhouette(vertices) is the antialiased 0/1 coverage: a mask differentiable in x, y.
+
+    `np_faces` gets the right hand's winding swap (mesh/render.py:298-300) and is not modified.  The edge table
+    (ops.tri_edge_table) is built once from the swapped faces; `np_vertices` (rest positions [NV,C]) welds corners with
+    bit-identical rows, which a mesh that stores every face's corners separately needs -- without it, every edge of such
+    a mesh is a silhouette edge."""
+
+    def __init__(self, width, height, np_faces, right_hand=True, np_vertices=None, clamp_max=100.0):
+        super().__init__()
+        self.width = width
+        self.height = height
+        self.clamp_max = clamp_max
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+        self.register_buffer('edges_i32', torch.from_numpy(ops.tri_edge_table(faces, np_vertices)).contiguous())
+
+    def _raster(self, vertices):
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("AntialiasedDepthRaster takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
+        return v, depth, owner
+
+    def forward(self, vertices):
+        v, depth, owner = self._raster(vertices)
+        c = torch.clamp(depth, max=self.clamp_max)
+        return ops.TriAntialias.apply(c, depth.detach(), owner, v, self.faces_i32, self.edges_i32)
+
+    def silhouette(self, vertices):
+        v, depth, owner = self._raster(vertices)
+        cover = (owner >= 0).float()
+        return ops.TriAntialias.apply(cover, depth.detach(), owner, v, self.faces_i32, self.edges_i32)
 
 
 class SparseSkinning(nn.Module):
