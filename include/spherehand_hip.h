@@ -545,6 +545,45 @@ int shr_tri_antialias_bwd(const float *values, const float *depth, const int32_t
                           const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H,
                           const float *grad_out, float *grad_values, float *grad_vertices, void *workspace, void *stream);
 
+/* Vertex-attribute interpolation over the owner map (a capability the reference does not have; the interpolation step
+ * of modular differentiable rasterizers): per-vertex attributes -> per-pixel maps through the faces that own the
+ * pixels, with the weights the raster's depth used there.  Per crop b:
+ *   owner[B,H,W]        shr_tri_raster_indexed_owner_fwd's owners (-1: background)
+ *   vertices[B,NV,4]    pixel-space (x, y, z, -), 16-byte aligned; faces[F,3] as the raster took them
+ *   attr                [B,NV,C] with attr_batch_stride = NV * C, or [NV,C] shared by all crops with
+ *                       attr_batch_stride = 0 (any other stride: SHR_EINVAL).  1 <= C <= 64 (SHR_ETOOLARGE beyond).
+ * Pixel (x, y), sampled at integer (x, y), with t = owner >= 0, t < F and face t's vertex ids inside [0, NV) (anything
+ * else counts as background), in fp32 with one rounding per written operator:
+ *   1. the reference's set-up on face t's corners in the faces' own order (.cu:33-66, :97-103): the corners sorted by
+ *      x -> p[0..2], sorted corner k being corner order[k] of the face; fi = the inverse barycentric matrix of p (nine
+ *      IEEE divisions by den); w_k = (fi[3k] * x + fi[3k+1] * y) + fi[3k+2]; c_k = min(max(w_k, 0), 1) (a NaN clamps
+ *      to 0); s = (c_0 + c_1) + c_2 -- exactly the values the raster's depth used at this pixel.
+ *   2. wh_k = c_k / s (IEEE division, the raster's w / w_sum).
+ *   3. out[b,ch,y,x] = (wh_0 * a_0[ch] + wh_1 * a_1[ch]) + wh_2 * a_2[ch], a_k the attribute row of vertex
+ *      faces[t, order[k]].  Background pixels, and pixels where s is 0 or not finite, get 0.
+ * These are the screen-linear weights, not the raster's 1 / sum_k wh_k / z_k form: the camera is orthographic.
+ *   shr_tri_interp_fwd   -> out[B,C,H,W]; no workspace.
+ *   shr_tri_interp_bwd   grad_out[B,C,H,W] -> grad_attr[B,NV,C] (per crop also for shared attributes: the caller sums
+ *       over b) and grad_vertices[B,NV,4] = (d/dx, d/dy, 0, 0); either output may be NULL (not both).
+ *       shr_mesh_depth_bwd's rule: the clamp decisions are step 1's fp32 values, a weight strictly outside [0, 1] is a
+ *       constant, coverage and owner are held fixed; no gradient to z or owner.  With the weights re-evaluated in fp64
+ *       from the fp32 corners (c_k = w_k where the fp32 w_k lies inside [0, 1], else the fp32 c_k):
+ *         grad_attr[b, faces[t,order[k]], ch] += wh_k * grad_out[b,ch,y,x];
+ *         grad_vertices: with g_k = sum_ch grad_out[ch] * a_k[ch] (ch ascending), the derivative of sum_k g_k wh_k with
+ *         respect to the three corners' x, y:  d / d c_a = (g_a - sum_k g_k wh_k) / s,  d w_a = (d n_a - w_a d den) / den.
+ *       Both sums are 64-bit fixed point in a per-crop unit computed on the device from the crop's largest term (one
+ *       unit for the vertex part, one for the attribute part; at most 3 W H terms per accumulator): bitwise
+ *       reproducible, independent of the batch and of the launch shape, no host synchronisation.  workspace: 16-byte
+ *       aligned, shr_tri_interp_bwd_workspace_bytes(B, NV, C, want_attr, want_vertices) bytes for the requested parts
+ *       (-1 on a negative size), cleared by the call itself.
+ *   B, W, H <= 65535 and, for the backward, B * ceil(C / 3) <= 65535 (SHR_ETOOLARGE beyond). */
+int shr_tri_interp_fwd(const int32_t *owner, const float *vertices, const int32_t *faces, const float *attr,
+                       long long attr_batch_stride, int B, int NV, int F, int W, int H, int C, float *out, void *stream);
+long long shr_tri_interp_bwd_workspace_bytes(int B, int NV, int C, int want_attr, int want_vertices);
+int shr_tri_interp_bwd(const int32_t *owner, const float *vertices, const int32_t *faces, const float *attr,
+                       long long attr_batch_stride, int B, int NV, int F, int W, int H, int C, const float *grad_out,
+                       float *grad_attr, float *grad_vertices, void *workspace, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

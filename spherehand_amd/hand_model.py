@@ -104,6 +104,17 @@ def sparse_skin(mesh):
     return start, bid.astype(np.int32), np.ascontiguousarray(wv, np.float32)
 
 
+def dense_skin_weights(mesh):
+    """The skin weights as a dense per-vertex table [NV, number of bones] float32: entry (v, b) is bone b's
+    `weight_coeff` of vertex v (the sum, should a bone list a vertex twice), 0 where the bone does not move the vertex.
+    Interpolated over the faces (render.MeshAttributeRaster) the columns are a soft part segmentation of the depth image."""
+    NV = np.asarray(mesh["vertices"]).shape[0]
+    w = np.zeros((NV, len(mesh["bones"])), np.float64)
+    for b, bone in enumerate(mesh["bones"]):
+        np.add.at(w[:, b], np.asarray(bone["weight_vertexid"], np.int64), np.asarray(bone["weight_coeff"], np.float64))
+    return np.ascontiguousarray(w, np.float32)
+
+
 def unique_skin(mesh):
     """The skin table of the DISTINCT vertices of the triangle mesh, and where each of the mesh's vertices went.
 

@@ -1156,6 +1156,86 @@ class TriAntialias(torch.autograd.Function):
         return gvals, None, None, gverts, None, None
 
 
+TRI_INTERP_MAX_CHANNELS = 64   # include/spherehand_hip.h, shr_tri_interp_fwd
+
+
+def _interp_shape(attr, owner, vertices, faces):
+    _check_input(attr, "attr")
+    _check_input(owner, "owner", torch.int32)
+    B, NV, F = _indexed_shape(vertices, faces)
+    if owner.dim() != 3 or owner.shape[0] != B:
+        raise RuntimeError("owner must be [B,H,W] with the vertices' B")
+    if attr.dim() not in (2, 3) or attr.shape[-2] != NV or (attr.dim() == 3 and attr.shape[0] != B):
+        raise RuntimeError("attr must be [B,NV,C] or [NV,C] with the vertices' B and NV")
+    C = attr.shape[-1]
+    if not 1 <= C <= TRI_INTERP_MAX_CHANNELS:
+        raise RuntimeError("attr must have 1 .. %d channels" % TRI_INTERP_MAX_CHANNELS)
+    if not (attr.device == owner.device == vertices.device == faces.device):
+        raise RuntimeError("attr, owner, vertices and faces must be on one device")
+    return B, NV, F, owner.shape[2], owner.shape[1], C, (NV * C if attr.dim() == 3 else 0)
+
+
+def tri_interpolate(attr, owner, vertices, faces):
+    """Vertex attributes interpolated over the owner map (include/spherehand_hip.h, shr_tri_interp_fwd): attr [B,NV,C]
+    or [NV,C] (shared by all crops), owner [B,H,W] int32 from tri_raster_indexed_owner_fwd, vertices [B,NV,4] pixel
+    space and faces [F,3] int32 as the raster took them -> maps [B,C,H,W], 0 at background pixels."""
+    B, NV, F, W, H, C, stride = _interp_shape(attr, owner, vertices, faces)
+    with _on(owner.device):
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=owner.device)
+        _lib.check(_lib.lib().shr_tri_interp_fwd(_ptr(owner), _ptr(vertices), _ptr(faces), _ptr(attr), stride, B, NV, F, W,
+                                                 H, C, _ptr(out), _stream()), "shr_tri_interp_fwd")
+    return out
+
+
+def tri_interpolate_bwd(attr, owner, vertices, faces, grad_out, want_attr=True, want_vertices=True):
+    """tri_interpolate's backward: (grad_attr [B,NV,C] -- per crop, also for shared attributes -- or None,
+    grad_vertices [B,NV,4] = (d/dx, d/dy, 0, 0) or None); deterministic fixed-point sums."""
+    B, NV, F, W, H, C, stride = _interp_shape(attr, owner, vertices, faces)
+    _check_input(grad_out, "grad_out")
+    if tuple(grad_out.shape) != (B, C, H, W):
+        raise RuntimeError("grad_out must be [B,C,H,W]")
+    if not (want_attr or want_vertices):
+        return None, None
+    lib = _lib.lib()
+    with _on(owner.device):
+        gattr = torch.empty((B, NV, C), dtype=torch.float32, device=owner.device) if want_attr else None
+        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=owner.device) if want_vertices else None
+        nbytes = lib.shr_tri_interp_bwd_workspace_bytes(B, NV, C, int(want_attr), int(want_vertices))
+        ws = torch.empty((max(16, nbytes),), dtype=torch.uint8, device=owner.device)
+        _lib.check(lib.shr_tri_interp_bwd(_ptr(owner), _ptr(vertices), _ptr(faces), _ptr(attr), stride, B, NV, F, W, H, C,
+                                          _ptr(grad_out), _ptr(gattr), _ptr(gverts), _ptr(ws), _stream()),
+                   "shr_tri_interp_bwd")
+    return gattr, gverts
+
+
+class TriInterpolate(torch.autograd.Function):
+    """tri_interpolate with a backward: (attr [B,NV,C] or [NV,C], owner, vertices [B,NV,3 or 4] pixel space, faces) ->
+    maps [B,C,H,W].  Differentiable w.r.t. attr (shared attributes get the sum over the crops) and vertices[..., :2]
+    (the z gradient is zero); coverage and owner are held fixed."""
+
+    @staticmethod
+    def forward(ctx, attr, owner, vertices, faces):
+        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+        ctx.width4 = vertices.shape[-1] == 4
+        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        attr, owner = attr.contiguous(), owner.contiguous()
+        out = tri_interpolate(attr, owner, v4, faces)
+        ctx.save_for_backward(attr, owner, v4, faces)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        attr, owner, v4, faces = ctx.saved_tensors
+        gattr, gverts = tri_interpolate_bwd(attr, owner, v4, faces, grad_out.contiguous().float(),
+                                            ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        if gattr is not None and attr.dim() == 2:
+            gattr = gattr.sum(0)
+        if gverts is not None and not ctx.width4:
+            gverts = gverts[..., :3]
+        return gattr, None, gverts, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

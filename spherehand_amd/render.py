@@ -8,6 +8,7 @@ signatures and return values), running on the hand-written HIP kernels.
     DepthRasterizationFunction / DepthRasterization / DepthRender  mesh/render.py:282-331
     TriangleDepthRaster      depth_rasterization.forward, differentiable at any width x height
     AntialiasedDepthRaster   the same, clamped and antialiased: gradients at the silhouette too
+    MeshAttributeRaster      TriangleDepthRaster + per-pixel maps of per-vertex attributes (part maps, correspondences)
 """
 import numpy as np
 import torch
@@ -250,6 +251,33 @@ class AntialiasedDepthRaster(nn.Module):
         v, depth, owner = self._raster(vertices)
         cover = (owner >= 0).float()
         return ops.TriAntialias.apply(cover, depth.detach(), owner, v, self.faces_i32, self.edges_i32)
+
+
+class MeshAttributeRaster(nn.Module):
+    """TriangleDepthRaster plus per-pixel maps of per-vertex attributes (ops.TriInterpolate; include/spherehand_hip.h
+    states the interpolation): forward(vertices[B,NV,>=3] pixel-space x, y, z, attributes [B,NV,C] or [NV,C]) ->
+    (maps [B,C,height,width], depth [B,height,width]).  `depth` is TriangleDepthRaster's raw depth, the same bits and
+    differentiable as there.  A map pixel is its owner face's three attribute rows weighted by the clamped, normalised
+    barycentric weights the depth used (screen-linear: the camera is orthographic), 0 at background pixels; the maps are
+    differentiable w.r.t. the attributes and vertices[..., :2], coverage held fixed.  With
+    hand_model.dense_skin_weights as attributes the maps are a soft part segmentation, with the rest positions a dense
+    correspondence map.  `np_faces` gets the right hand's winding swap (mesh/render.py:298-300) and is not modified."""
+
+    def __init__(self, width, height, np_faces, right_hand=True):
+        super().__init__()
+        self.width = width
+        self.height = height
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+
+    def forward(self, vertices, attributes):
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("MeshAttributeRaster takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
+        return ops.TriInterpolate.apply(attributes, owner, v, self.faces_i32), depth
 
 
 class SparseSkinning(nn.Module):
