@@ -545,6 +545,33 @@ int shr_tri_antialias_bwd(const float *values, const float *depth, const int32_t
                           const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H,
                           const float *grad_out, float *grad_values, float *grad_vertices, void *workspace, void *stream);
 
+/* The antialias pass over multi-channel maps: values[B,C,H,W] (shr_tri_interp_fwd's maps) -> out[B,C,H,W], every channel
+ * plane blended as shr_tri_antialias_fwd blends one plane.  depth, owner, vertices, faces and edges as there.  The
+ * PAIRS, the front pixel, the silhouette edges, the qualifying edge and s are word for word shr_tri_antialias_fwd's:
+ * they do not depend on the values, so there is one decision per pair, shared by all channels.
+ *   shr_tri_antialias_maps_fwd   for every channel ch, out[b,ch] is shr_tri_antialias_fwd's output for values[b,ch]:
+ *       the same fp32 expression in the same order (left, right, up, down), gains computed from the input values only
+ *       (out must not overlap values: SHR_EINVAL); a pixel that gains nothing is a bitwise copy in every channel.
+ *   shr_tri_antialias_maps_bwd   grad_out[B,C,H,W] -> grad_values[B,C,H,W] and grad_vertices[B,NV,4] = (d/dx, d/dy, 0,
+ *       0); either output may be NULL (not both).  grad_values[b,ch] is shr_tri_antialias_bwd's gather of grad_out[b,ch].
+ *       The vertex terms are shr_tri_antialias_bwd's with
+ *           gw = sum_ch grad_out[b,ch,gaining pixel] * (c_f[ch] - c_o[ch])        (fp64, ch ascending)
+ *       in place of the single plane's product (at C = 1 the same bits): one term per coordinate per pair to
+ *       faces[t,k] and faces[t,(k+1)%3], in the same 64-bit fixed point with the same bit bound -- bitwise
+ *       reproducible, independent of the batch, no host synchronisation.  No gradient to depth, owner or z.
+ *       workspace: 16-byte aligned, shr_tri_antialias_maps_bwd_workspace_bytes(B, NV) bytes (only with grad_vertices;
+ *       equal to shr_tri_antialias_bwd_workspace_bytes(B, NV)), cleared by the call itself.
+ *   1 <= C <= 64 as shr_tri_interp_fwd (C <= 0: SHR_EINVAL; beyond 64: SHR_ETOOLARGE); B, W, H <= 65535
+ *   (SHR_ETOOLARGE beyond); B == 0 is a no-op; NULLs and misaligned vertices / grad_vertices / workspace: SHR_EINVAL. */
+int shr_tri_antialias_maps_fwd(const float *values, const float *depth, const int32_t *owner, const float *vertices,
+                               const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H, int C,
+                               float *out, void *stream);
+long long shr_tri_antialias_maps_bwd_workspace_bytes(int B, int NV);
+int shr_tri_antialias_maps_bwd(const float *values, const float *depth, const int32_t *owner, const float *vertices,
+                               const int32_t *faces, const int32_t *edges, int B, int NV, int F, int W, int H, int C,
+                               const float *grad_out, float *grad_values, float *grad_vertices, void *workspace,
+                               void *stream);
+
 /* Vertex-attribute interpolation over the owner map (a capability the reference does not have; the interpolation step
  * of modular differentiable rasterizers): per-vertex attributes -> per-pixel maps through the faces that own the
  * pixels, with the weights the raster's depth used there.  Per crop b:

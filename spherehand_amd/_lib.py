@@ -89,6 +89,9 @@ SIGNATURES = {
     "shr_tri_antialias_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "shr_tri_antialias_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "shr_tri_antialias_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "shr_tri_antialias_maps_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "shr_tri_antialias_maps_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_tri_antialias_maps_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_tri_interp_fwd": ([_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "shr_tri_interp_bwd_workspace_bytes": ([_i, _i, _i, _i, _i], ctypes.c_longlong),
     "shr_tri_interp_bwd": ([_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),

@@ -1236,6 +1236,96 @@ class TriInterpolate(torch.autograd.Function):
         return gattr, None, gverts, None
 
 
+def _aa_maps_shape(values, depth, owner, vertices, faces, edges):
+    # shapes and types first, then where the tensors live: the messages name what is wrong with the call
+    for t, name, dtype in ((values, "values", torch.float32), (depth, "depth", torch.float32),
+                           (owner, "owner", torch.int32), (vertices, "vertices", torch.float32),
+                           (faces, "faces", torch.int32), (edges, "edges", torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("%s must be a torch.Tensor" % name)
+        if t.dtype != dtype:
+            raise RuntimeError("%s must be %s" % (name, dtype))
+    if values.dim() != 4:
+        raise RuntimeError("values must be [B,C,H,W] (tri_antialias takes one plane [B,H,W])")
+    if vertices.dim() != 3 or vertices.shape[2] != 4 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("vertices must be [B,NV,4] and faces [F,3]")
+    B, C, H, W = values.shape
+    NV, F = vertices.shape[1], faces.shape[0]
+    if not 1 <= C <= TRI_INTERP_MAX_CHANNELS:
+        raise RuntimeError("values must have 1 .. %d channels" % TRI_INTERP_MAX_CHANNELS)
+    if vertices.shape[0] != B or tuple(depth.shape) != (B, H, W) or tuple(owner.shape) != (B, H, W):
+        raise RuntimeError("depth and owner must be [B,H,W] of values [B,C,H,W], with the vertices' B")
+    if tuple(edges.shape) != (F, 3):
+        raise RuntimeError("edges must be [F,3]")
+    for t, name, dtype in ((values, "values", torch.float32), (depth, "depth", torch.float32),
+                           (owner, "owner", torch.int32), (edges, "edges", torch.int32)):
+        _check_input(t, name, dtype)
+    _indexed_shape(vertices, faces)
+    if not (values.device == depth.device == owner.device == vertices.device == faces.device == edges.device):
+        raise RuntimeError("values, depth, owner, vertices, faces and edges must be on one device")
+    return B, NV, F, W, H, C
+
+
+def tri_antialias_maps(values, depth, owner, vertices, faces, edges):
+    """The antialias pass over multi-channel maps (include/spherehand_hip.h, shr_tri_antialias_maps_fwd): values
+    [B,C,H,W] (tri_interpolate's maps, 1 <= C <= 64) -> [B,C,H,W], every channel the bits of tri_antialias on that plane,
+    with each pair decided once for all channels; the other arguments as tri_antialias takes them."""
+    B, NV, F, W, H, C = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
+    with _on(values.device):
+        out = torch.empty_like(values)
+        _lib.check(_lib.lib().shr_tri_antialias_maps_fwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices),
+                                                         _ptr(faces), _ptr(edges), B, NV, F, W, H, C, _ptr(out),
+                                                         _stream()), "shr_tri_antialias_maps_fwd")
+    return out
+
+
+def tri_antialias_maps_bwd(values, depth, owner, vertices, faces, edges, grad_out, want_values=True, want_vertices=True):
+    """tri_antialias_maps's backward: (grad_values [B,C,H,W] or None, grad_vertices [B,NV,4] = (d/dx, d/dy, 0, 0) or
+    None); the vertex sums are deterministic fixed point."""
+    B, NV, F, W, H, C = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
+    _check_input(grad_out, "grad_out")
+    if grad_out.shape != values.shape or grad_out.device != values.device:
+        raise RuntimeError("grad_out must be [B,C,H,W] as values, on their device")
+    if not (want_values or want_vertices):
+        return None, None
+    lib = _lib.lib()
+    with _on(values.device):
+        gvals = torch.empty_like(values) if want_values else None
+        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=values.device) if want_vertices else None
+        ws = torch.empty((max(16, lib.shr_tri_antialias_maps_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
+                         device=values.device) if want_vertices else None
+        _lib.check(lib.shr_tri_antialias_maps_bwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
+                                                  _ptr(edges), B, NV, F, W, H, C, _ptr(grad_out), _ptr(gvals),
+                                                  _ptr(gverts), _ptr(ws), _stream()), "shr_tri_antialias_maps_bwd")
+    return gvals, gverts
+
+
+class TriAntialiasMaps(torch.autograd.Function):
+    """tri_antialias_maps with a backward: (values [B,C,H,W], depth, owner, vertices [B,NV,3 or 4] pixel space, faces,
+    edges) -> the antialiased maps.  Differentiable w.r.t. values and vertices[..., :2] (the z gradient is zero); depth
+    and owner get none."""
+
+    @staticmethod
+    def forward(ctx, values, depth, owner, vertices, faces, edges):
+        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+        ctx.width4 = vertices.shape[-1] == 4
+        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        values, depth, owner = values.contiguous(), depth.contiguous(), owner.contiguous()
+        out = tri_antialias_maps(values, depth, owner, v4, faces, edges)
+        ctx.save_for_backward(values, depth, owner, v4, faces, edges)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        values, depth, owner, v4, faces, edges = ctx.saved_tensors
+        gvals, gverts = tri_antialias_maps_bwd(values, depth, owner, v4, faces, edges, grad_out.contiguous().float(),
+                                               ctx.needs_input_grad[0], ctx.needs_input_grad[3])
+        if gverts is not None and not ctx.width4:
+            gverts = gverts[..., :3]
+        return gvals, None, None, gverts, None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

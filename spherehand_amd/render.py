@@ -9,6 +9,7 @@ signatures and return values), running on the hand-written HIP kernels.
     TriangleDepthRaster      depth_rasterization.forward, differentiable at any width x height
     AntialiasedDepthRaster   the same, clamped and antialiased: gradients at the silhouette too
     MeshAttributeRaster      TriangleDepthRaster + per-pixel maps of per-vertex attributes (part maps, correspondences)
+    AntialiasedAttributeRaster  the maps and the clamped depth, both antialiased: outline gradients for the maps too
 """
 import numpy as np
 import torch
@@ -278,6 +279,42 @@ class MeshAttributeRaster(nn.Module):
         v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
         depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
         return ops.TriInterpolate.apply(attributes, owner, v, self.faces_i32), depth
+
+
+class AntialiasedAttributeRaster(nn.Module):
+    """MeshAttributeRaster's maps and AntialiasedDepthRaster's depth from one raster, both antialiased across the
+    silhouette: forward(vertices[B,NV,>=3] pixel-space x, y, z, attributes [B,NV,C] or [NV,C], 1 <= C <= 64) ->
+    (maps [B,C,height,width], depth [B,height,width]).  One owner forward, ops.TriInterpolate, ops.TriAntialiasMaps on
+    the maps (every pair decided once for all channels; include/spherehand_hip.h states the pass) and ops.TriAntialias on
+    clamp(raw, max=clamp_max).  `depth` has AntialiasedDepthRaster's bits.  The maps are differentiable w.r.t. the
+    attributes and vertices[..., :2]: inside the faces as MeshAttributeRaster's, and at the outline through the pass, so
+    a part map, a correspondence map or any per-vertex signal can be fitted in x, y by render-and-compare.  With
+    attributes ones [NV,1] the map is AntialiasedDepthRaster.silhouette() wherever the interpolated value is exactly 1.
+
+    `np_faces` gets the right hand's winding swap (mesh/render.py:298-300) and is not modified; the edge table and
+    `np_vertices` are AntialiasedDepthRaster's."""
+
+    def __init__(self, width, height, np_faces, right_hand=True, np_vertices=None, clamp_max=100.0):
+        super().__init__()
+        self.width = width
+        self.height = height
+        self.clamp_max = clamp_max
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+        self.register_buffer('edges_i32', torch.from_numpy(ops.tri_edge_table(faces, np_vertices)).contiguous())
+
+    def forward(self, vertices, attributes):
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("AntialiasedAttributeRaster takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
+        raw = depth.detach()
+        maps = ops.TriInterpolate.apply(attributes, owner, v, self.faces_i32)
+        maps = ops.TriAntialiasMaps.apply(maps, raw, owner, v, self.faces_i32, self.edges_i32)
+        c = torch.clamp(depth, max=self.clamp_max)
+        return maps, ops.TriAntialias.apply(c, raw, owner, v, self.faces_i32, self.edges_i32)
 
 
 class SparseSkinning(nn.Module):
