@@ -23,7 +23,23 @@ constexpr int kBwdThreads = 1024;
 constexpr int kBwdPix = 4;                            // output pixels per thread
 constexpr int kBwdBlockPix = kBwdThreads * kBwdPix;   // output pixels per workgroup
 constexpr int kBwdLdsVerts = 2048;                    // vertices whose accumulators fit LDS (2048 x 3 x 8 = 48 KB)
-constexpr int kFixBits = 41;                          // the crop's largest term -> below 2^41 (fewer: raster_fix_bits)
+constexpr int kFixBits = 41;                          // the crop's largest term -> below 2^41 (fewer: fix_term_bits)
+
+// The pixels of a tap walker over a W x H image, pixel(k) for k < kPix.  RUNS (the accumulators in global memory: more
+// than kBwdLdsVerts points): a thread takes kPixRun CONSECUTIVE pixels of a row -- the hand's faces own runs of ~5 pixels
+// of a row at 640 x 640, and a run's terms go to the same nine accumulators: summed in registers first, they cost one L2
+// atomic each instead of one per pixel (256 soups @640^2: 10.1 -> 4.1 ms); 512 threads, so that the run's eighteen
+// registers fit without spilling.  Without RUNS (LDS accumulators): 1024 threads, kBwdPix pixels each a workgroup's width
+// apart (2.3 ms against 3.6 for consecutive pixels, 256 indexed hands @640^2).
+constexpr int kPixRun = 8;
+template <bool RUNS>
+struct PixelWalk {
+  static constexpr int kThreads = RUNS ? 512 : kBwdThreads, kPix = RUNS ? kPixRun : kBwdPix, kBlockPix = kThreads * kPix;
+  static __device__ __forceinline__ size_t pixel(int k) {
+    return RUNS ? ((size_t)blockIdx.x * kThreads + threadIdx.x) * kPix + k
+                : (size_t)blockIdx.x * kBlockPix + k * kThreads + threadIdx.x;
+  }
+};
 
 __device__ __forceinline__ double fix_unit(uint32_t max_bits, int bits) {   // 2^(bits - E), max < 2^E
   int e = 0;
@@ -150,6 +166,16 @@ static size_t mesh_bwd_max_bytes(int B) { return (((size_t)B * 4) + 255) & ~(siz
 static long long fix_workspace_bytes(int B, long long NP) {
   if (B < 0 || NP < 0) return -1;
   return (long long)((mesh_bwd_max_bytes(B) + (size_t)B * NP * 3 * 8 + 15) & ~(size_t)15);
+}
+
+// The bits of a backward over a W x H image whose accumulators take at most `terms_per_pixel` terms per pixel: with
+// N = terms_per_pixel W H terms the crop's largest term goes below 2^(62 - ceil(log2 N)), 2^41 at most -- no sum can wrap
+// at any size.
+static int fix_term_bits(int terms_per_pixel, int W, int H) {
+  const unsigned long long n = (unsigned long long)terms_per_pixel * (unsigned long long)W * (unsigned long long)H;
+  int lg = 0;
+  while ((1ull << lg) < n) lg++;
+  return 62 - lg < shr::kFixBits ? 62 - lg : shr::kFixBits;
 }
 
 // The four passes of a fixed-point backward over `taps` (clear, crop maxima, sums, conversion to out[B][NP][STRIDE]).

@@ -130,13 +130,8 @@ struct MeshTaps {
 // PixelTaps: the owner raster's W x H pixels (shr_tri_raster_bwd, shr_tri_raster_indexed_bwd), ONE tap of weight 1 at the
 // integer pixel each -- the raster's own depth, no resampling.  The points: a face soup's corners (point 3 f + k of
 // face_vertices[B][F][3][3], its gradient's own layout) or an indexed mesh's vertices[B][NV][4].  An owner outside
-// [0, F) or a vertex index outside [0, NV) is skipped.  RUNS (the accumulators in global memory: more than kBwdLdsVerts
-// points, every hand-sized soup): a thread takes kPixRun CONSECUTIVE pixels of a row -- the hand's faces own runs of ~5
-// pixels of a row at 640 x 640, and a run's terms go to the same nine accumulators: summed in registers first, they cost
-// one L2 atomic each instead of one per pixel (256 soups @640^2: 10.1 -> 4.1 ms); 512 threads, so that the run's eighteen
-// registers fit without spilling.  Without RUNS (LDS accumulators): MeshTaps' layout, 1024 threads, kBwdPix pixels each
-// a workgroup's width apart (2.3 ms against 3.6 for consecutive pixels, 256 indexed hands @640^2).
-constexpr int kPixRun = 8;
+// [0, F) or a vertex index outside [0, NV) is skipped.  RUNS: fixed_point.h's PixelWalk (the accumulators in global
+// memory: more than kBwdLdsVerts points, every hand-sized soup).
 template <bool INDEXED, bool RUNS>
 struct PixelTaps {
   const float *src;
@@ -144,16 +139,15 @@ struct PixelTaps {
   const int *owner;
   const float *grad_depth;
   int F, NV, W, H;
-  static constexpr int kThreads = RUNS ? 512 : kBwdThreads, kPix = RUNS ? kPixRun : kBwdPix, kBlockPix = kThreads * kPix;
+  static constexpr int kThreads = PixelWalk<RUNS>::kThreads, kBlockPix = PixelWalk<RUNS>::kBlockPix;
   static constexpr bool kRuns = RUNS;
   __device__ __forceinline__ int points() const { return INDEXED ? NV : 3 * F; }
   template <typename Fn>
   __device__ __forceinline__ void walk(Fn fn) const {
     const int b = blockIdx.y;
     const size_t npix = (size_t)W * H;
-    for (int k = 0; k < kPix; k++) {
-      const size_t i = RUNS ? ((size_t)blockIdx.x * kThreads + threadIdx.x) * kPix + k
-                            : (size_t)blockIdx.x * kBlockPix + k * kThreads + threadIdx.x;
+    for (int k = 0; k < PixelWalk<RUNS>::kPix; k++) {
+      const size_t i = PixelWalk<RUNS>::pixel(k);
       if (i >= npix) break;
       const int f = owner[(size_t)b * npix + i];
       if ((unsigned)f >= (unsigned)F) continue;   // (background: -1)
@@ -260,14 +254,7 @@ extern "C" int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, c
 }
 
 // The owner raster's backward.  A point's accumulator takes at most three terms per pixel (a face's three corners, one
-// vertex each unless the face repeats one): with N = 3 W H terms the crop's largest term goes below 2^(62 - ceil(log2 N)),
-// 2^41 at most -- 41 bits up to 640 x 640, no sum can wrap at any size.
-static int raster_fix_bits(int W, int H) {
-  const unsigned long long n = 3ull * (unsigned long long)W * (unsigned long long)H;
-  int lg = 0;
-  while ((1ull << lg) < n) lg++;
-  return 62 - lg < shr::kFixBits ? 62 - lg : shr::kFixBits;
-}
+// vertex each unless the face repeats one): fix_term_bits(3, W, H) -- 41 bits up to 640 x 640.
 
 extern "C" long long shr_tri_raster_bwd_workspace_bytes(int B, int F) { return fix_workspace_bytes(B, 3LL * F); }
 extern "C" long long shr_tri_raster_indexed_bwd_workspace_bytes(int B, int NV) { return fix_workspace_bytes(B, NV); }
@@ -282,9 +269,9 @@ extern "C" int shr_tri_raster_bwd(const float *face_vertices, const int32_t *own
   if (B > 65535 || W > 65535 || H > 65535 || 3LL * F * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
   if (3 * F <= kBwdLdsVerts)
     return fixed_point_bwd<3>(PixelTaps<false, false>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
-                              (size_t)W * H, raster_fix_bits(W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+                              (size_t)W * H, fix_term_bits(3, W, H), grad_face_vertices, workspace, (hipStream_t)stream);
   return fixed_point_bwd<3>(PixelTaps<false, true>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
-                            (size_t)W * H, raster_fix_bits(W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+                            (size_t)W * H, fix_term_bits(3, W, H), grad_face_vertices, workspace, (hipStream_t)stream);
 }
 
 extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *faces, const int32_t *owner,
@@ -299,9 +286,9 @@ extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *
   if (B > 65535 || W > 65535 || H > 65535 || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
   if (NV <= kBwdLdsVerts)
     return fixed_point_bwd<4>(PixelTaps<true, false>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
-                              raster_fix_bits(W, H), grad_vertices, workspace, (hipStream_t)stream);
+                              fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
   return fixed_point_bwd<4>(PixelTaps<true, true>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
-                            raster_fix_bits(W, H), grad_vertices, workspace, (hipStream_t)stream);
+                            fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
 }
 
 extern "C" int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,

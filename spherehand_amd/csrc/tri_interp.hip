@@ -137,31 +137,21 @@ __device__ __forceinline__ bool interp_tap(const InterpArgs &A, int bi, int t, i
   return true;
 }
 
-// the pixel of a walker: RUNS -- kPixRun consecutive pixels of a row per thread (mesh_depth_bwd.hip's PixelTaps)
-template <bool RUNS>
-struct InterpWalk {
-  static constexpr int kThreads = RUNS ? 512 : kBwdThreads, kPix = RUNS ? 8 : kBwdPix, kBlockPix = kThreads * kPix;
-  static __device__ __forceinline__ size_t pixel(int k) {
-    return RUNS ? ((size_t)blockIdx.x * kThreads + threadIdx.x) * kPix + k
-                : (size_t)blockIdx.x * kBlockPix + k * kThreads + threadIdx.x;
-  }
-};
-
 // grad_vertices: with g_k = sum_ch grad_out[ch] a_k[ch], d (sum_k g_k c_k / s) / d c_a = (g_a - sum_k g_k wh_k) / s, and
 // d w_a = (d n_a - w_a d den) / den for the weights that pass.
 template <bool RUNS>
 struct InterpVertexTaps {
   InterpArgs A;
   const float *grad_out;
-  static constexpr int kThreads = InterpWalk<RUNS>::kThreads, kBlockPix = InterpWalk<RUNS>::kBlockPix;
+  static constexpr int kThreads = PixelWalk<RUNS>::kThreads, kBlockPix = PixelWalk<RUNS>::kBlockPix;
   static constexpr bool kRuns = RUNS;
   __device__ __forceinline__ int points() const { return A.NV; }
   template <typename Fn>
   __device__ __forceinline__ void walk(Fn fn) const {
     const int bi = blockIdx.y;
     const size_t npix = (size_t)A.W * A.H;
-    for (int k = 0; k < InterpWalk<RUNS>::kPix; k++) {
-      const size_t i = InterpWalk<RUNS>::pixel(k);
+    for (int k = 0; k < PixelWalk<RUNS>::kPix; k++) {
+      const size_t i = PixelWalk<RUNS>::pixel(k);
       if (i >= npix) break;
       const int t = A.owner[(size_t)bi * npix + i];
       if (t < 0) continue;
@@ -206,15 +196,15 @@ struct InterpAttrTaps {
   InterpArgs A;
   const float *grad_out;
   int G;
-  static constexpr int kThreads = InterpWalk<RUNS>::kThreads, kBlockPix = InterpWalk<RUNS>::kBlockPix;
+  static constexpr int kThreads = PixelWalk<RUNS>::kThreads, kBlockPix = PixelWalk<RUNS>::kBlockPix;
   static constexpr bool kRuns = RUNS;
   __device__ __forceinline__ int points() const { return A.NV; }
   template <typename Fn>
   __device__ __forceinline__ void walk(Fn fn) const {
     const int bi = blockIdx.y / G, ch0 = 3 * (blockIdx.y - bi * G);
     const size_t npix = (size_t)A.W * A.H;
-    for (int k = 0; k < InterpWalk<RUNS>::kPix; k++) {
-      const size_t i = InterpWalk<RUNS>::pixel(k);
+    for (int k = 0; k < PixelWalk<RUNS>::kPix; k++) {
+      const size_t i = PixelWalk<RUNS>::pixel(k);
       if (i >= npix) break;
       const int t = A.owner[(size_t)bi * npix + i];
       if (t < 0) continue;
@@ -247,7 +237,7 @@ interp_attr_max_kernel(InterpArgs A, const float *__restrict__ grad_out, int G, 
   const size_t npix = (size_t)A.W * A.H;
   float m = 0.f;
   for (int k = 0; k < kBwdPix; k++) {
-    const size_t i = InterpWalk<false>::pixel(k);
+    const size_t i = PixelWalk<false>::pixel(k);
     if (i >= npix) break;
     const int t = A.owner[(size_t)bi * npix + i];
     if (t < 0) continue;
@@ -291,15 +281,6 @@ interp_attr_finish_kernel(const unsigned long long *__restrict__ acc, const uint
 }
 
 }  // namespace shr
-
-// An accumulator takes at most one term per corner per pixel: N = 3 W H terms, the crop's largest below
-// 2^(62 - ceil(log2 N)), 2^41 at most (mesh_depth_bwd.hip's raster_fix_bits).
-static int interp_fix_bits(int W, int H) {
-  const unsigned long long n = 3ull * (unsigned long long)W * (unsigned long long)H;
-  int lg = 0;
-  while ((1ull << lg) < n) lg++;
-  return 62 - lg < shr::kFixBits ? 62 - lg : shr::kFixBits;
-}
 
 static int interp_groups(int C) { return (C + 2) / 3; }
 
@@ -378,7 +359,8 @@ extern "C" int shr_tri_interp_bwd(const int32_t *owner, const float *vertices, c
   if ((long long)B * interp_groups(C) > 65535) return SHR_ETOOLARGE;   // (one grid row per crop and channel group)
   const InterpArgs A{owner, reinterpret_cast<const float4 *>(vertices), faces, attr, attr_batch_stride, NV, F, W, H, C};
   hipStream_t s = (hipStream_t)stream;
-  const int bits = interp_fix_bits(W, H);
+  // an accumulator takes at most one term per corner per pixel: three per pixel
+  const int bits = fix_term_bits(3, W, H);
   const size_t npix = (size_t)W * H;
   char *ws = reinterpret_cast<char *>(workspace);
   if (grad_vertices) {

@@ -1007,25 +1007,43 @@ class TriRaster(torch.autograd.Function):
         return tri_raster_bwd(face_vertices, owner, grad_depth.contiguous().float()), None, None
 
 
+def vertices4(vertices):
+    """vertices [B,NV,3 or 4] -> (the contiguous [B,NV,4] the kernels take, a zero appended to three components; whether
+    the input had four): the Functions below hand the gradient back in the width they were given."""
+    if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
+        raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
+    width4 = vertices.shape[-1] == 4
+    return (vertices.contiguous() if width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()), width4
+
+
+def _grad_as_given(ctx, gverts):
+    return gverts if gverts is None or ctx.width4 else gverts[..., :3]
+
+
+def _tri_indexed_forward(ctx, vertices, faces, width, height):
+    v4, ctx.width4 = vertices4(vertices)
+    depth, owner = tri_raster_indexed_owner_fwd(width, height, v4, faces)
+    ctx.save_for_backward(v4, faces, owner)
+    return depth, owner
+
+
+def _tri_indexed_backward(ctx, grad_depth):
+    v4, faces, owner = ctx.saved_tensors
+    g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
+    return _grad_as_given(ctx, g), None, None, None
+
+
 class TriRasterIndexed(torch.autograd.Function):
     """TriRaster on an indexed mesh: vertices [B,NV,3 or 4] (pixel space) + faces [F,3] int32 -> raw depth
     [B,height,width], the bits of tri_raster_indexed_fwd; differentiable w.r.t. vertices[..., :3]."""
 
     @staticmethod
     def forward(ctx, vertices, faces, width, height):
-        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
-            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
-        ctx.width4 = vertices.shape[-1] == 4
-        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
-        depth, owner = tri_raster_indexed_owner_fwd(width, height, v4, faces)
-        ctx.save_for_backward(v4, faces, owner)
-        return depth
+        return _tri_indexed_forward(ctx, vertices, faces, width, height)[0]
 
     @staticmethod
     def backward(ctx, grad_depth):
-        v4, faces, owner = ctx.saved_tensors
-        g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
-        return (g if ctx.width4 else g[..., :3]), None, None, None
+        return _tri_indexed_backward(ctx, grad_depth)
 
 
 class TriRasterIndexedOwner(torch.autograd.Function):
@@ -1035,20 +1053,13 @@ class TriRasterIndexedOwner(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, faces, width, height):
-        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
-            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
-        ctx.width4 = vertices.shape[-1] == 4
-        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
-        depth, owner = tri_raster_indexed_owner_fwd(width, height, v4, faces)
-        ctx.save_for_backward(v4, faces, owner)
+        depth, owner = _tri_indexed_forward(ctx, vertices, faces, width, height)
         ctx.mark_non_differentiable(owner)
         return depth, owner
 
     @staticmethod
     def backward(ctx, grad_depth, _grad_owner):
-        v4, faces, owner = ctx.saved_tensors
-        g = tri_raster_indexed_bwd(v4, faces, owner, grad_depth.contiguous().float())
-        return (g if ctx.width4 else g[..., :3]), None, None, None
+        return _tri_indexed_backward(ctx, grad_depth)
 
 
 def tri_edge_table(faces, weld=None):
@@ -1096,38 +1107,62 @@ def _aa_shape(values, depth, owner, vertices, faces, edges):
     return B, NV, F, values.shape[2], values.shape[1]
 
 
+def _aa_call_fwd(entry, tensors, *dims):
+    """One of the two forward entries of the pass (dims: B, NV, F, W, H and, for maps, C) on (values, depth, owner,
+    vertices, faces, edges), already checked."""
+    with _on(tensors[0].device):
+        out = torch.empty_like(tensors[0])
+        _lib.check(getattr(_lib.lib(), entry)(*[_ptr(t) for t in tensors], *dims, _ptr(out), _stream()), entry)
+    return out
+
+
+def _aa_call_bwd(entry, tensors, grad_out, want_values, want_vertices, *dims):
+    """One of the two backward entries of the pass, as _aa_call_fwd: (grad_values or None, grad_vertices or None)."""
+    if not (want_values or want_vertices):
+        return None, None
+    lib, values, (B, NV) = _lib.lib(), tensors[0], dims[:2]
+    with _on(values.device):
+        gvals = torch.empty_like(values) if want_values else None
+        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=values.device) if want_vertices else None
+        ws = torch.empty((max(16, getattr(lib, entry + "_workspace_bytes")(B, NV)),), dtype=torch.uint8,
+                         device=values.device) if want_vertices else None
+        _lib.check(getattr(lib, entry)(*[_ptr(t) for t in tensors], *dims, _ptr(grad_out), _ptr(gvals), _ptr(gverts),
+                                       _ptr(ws), _stream()), entry)
+    return gvals, gverts
+
+
 def tri_antialias(values, depth, owner, vertices, faces, edges):
     """The antialias pass (include/spherehand_hip.h, shr_tri_antialias_fwd): values [B,H,W] blended across the
     silhouette edges of the owner faces -> [B,H,W]; depth, owner from tri_raster_indexed_owner_fwd, vertices [B,NV,4]
     pixel space, faces [F,3] int32, edges [F,3] int32 (tri_edge_table)."""
-    B, NV, F, W, H = _aa_shape(values, depth, owner, vertices, faces, edges)
-    with _on(values.device):
-        out = torch.empty_like(values)
-        _lib.check(_lib.lib().shr_tri_antialias_fwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
-                                                    _ptr(edges), B, NV, F, W, H, _ptr(out), _stream()),
-                   "shr_tri_antialias_fwd")
-    return out
+    dims = _aa_shape(values, depth, owner, vertices, faces, edges)
+    return _aa_call_fwd("shr_tri_antialias_fwd", (values, depth, owner, vertices, faces, edges), *dims)
 
 
 def tri_antialias_bwd(values, depth, owner, vertices, faces, edges, grad_out, want_values=True, want_vertices=True):
     """tri_antialias's backward: (grad_values [B,H,W] or None, grad_vertices [B,NV,4] = (d/dx, d/dy, 0, 0) or None);
     the vertex sums are deterministic fixed point."""
-    B, NV, F, W, H = _aa_shape(values, depth, owner, vertices, faces, edges)
+    dims = _aa_shape(values, depth, owner, vertices, faces, edges)
     _check_input(grad_out, "grad_out")
     if grad_out.shape != values.shape:
         raise RuntimeError("grad_out must be [B,H,W] as values")
-    if not (want_values or want_vertices):
-        return None, None
-    lib = _lib.lib()
-    with _on(values.device):
-        gvals = torch.empty_like(values) if want_values else None
-        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=values.device) if want_vertices else None
-        ws = torch.empty((max(16, lib.shr_tri_antialias_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
-                         device=values.device) if want_vertices else None
-        _lib.check(lib.shr_tri_antialias_bwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
-                                             _ptr(edges), B, NV, F, W, H, _ptr(grad_out), _ptr(gvals), _ptr(gverts),
-                                             _ptr(ws), _stream()), "shr_tri_antialias_bwd")
-    return gvals, gverts
+    return _aa_call_bwd("shr_tri_antialias_bwd", (values, depth, owner, vertices, faces, edges), grad_out, want_values,
+                        want_vertices, *dims)
+
+
+def _aa_forward(ctx, fwd, values, depth, owner, vertices, faces, edges):
+    v4, ctx.width4 = vertices4(vertices)
+    values, depth, owner = values.contiguous(), depth.contiguous(), owner.contiguous()
+    out = fwd(values, depth, owner, v4, faces, edges)
+    ctx.save_for_backward(values, depth, owner, v4, faces, edges)
+    return out
+
+
+def _aa_backward(ctx, bwd, grad_out):
+    values, depth, owner, v4, faces, edges = ctx.saved_tensors
+    gvals, gverts = bwd(values, depth, owner, v4, faces, edges, grad_out.contiguous().float(), ctx.needs_input_grad[0],
+                        ctx.needs_input_grad[3])
+    return gvals, None, None, _grad_as_given(ctx, gverts), None, None
 
 
 class TriAntialias(torch.autograd.Function):
@@ -1137,23 +1172,11 @@ class TriAntialias(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, values, depth, owner, vertices, faces, edges):
-        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
-            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
-        ctx.width4 = vertices.shape[-1] == 4
-        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
-        values, depth, owner = values.contiguous(), depth.contiguous(), owner.contiguous()
-        out = tri_antialias(values, depth, owner, v4, faces, edges)
-        ctx.save_for_backward(values, depth, owner, v4, faces, edges)
-        return out
+        return _aa_forward(ctx, tri_antialias, values, depth, owner, vertices, faces, edges)
 
     @staticmethod
     def backward(ctx, grad_out):
-        values, depth, owner, v4, faces, edges = ctx.saved_tensors
-        gvals, gverts = tri_antialias_bwd(values, depth, owner, v4, faces, edges, grad_out.contiguous().float(),
-                                          ctx.needs_input_grad[0], ctx.needs_input_grad[3])
-        if gverts is not None and not ctx.width4:
-            gverts = gverts[..., :3]
-        return gvals, None, None, gverts, None, None
+        return _aa_backward(ctx, tri_antialias_bwd, grad_out)
 
 
 TRI_INTERP_MAX_CHANNELS = 64   # include/spherehand_hip.h, shr_tri_interp_fwd
@@ -1215,10 +1238,7 @@ class TriInterpolate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, owner, vertices, faces):
-        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
-            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
-        ctx.width4 = vertices.shape[-1] == 4
-        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
+        v4, ctx.width4 = vertices4(vertices)
         attr, owner = attr.contiguous(), owner.contiguous()
         out = tri_interpolate(attr, owner, v4, faces)
         ctx.save_for_backward(attr, owner, v4, faces)
@@ -1231,9 +1251,7 @@ class TriInterpolate(torch.autograd.Function):
                                             ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         if gattr is not None and attr.dim() == 2:
             gattr = gattr.sum(0)
-        if gverts is not None and not ctx.width4:
-            gverts = gverts[..., :3]
-        return gattr, None, gverts, None
+        return gattr, None, _grad_as_given(ctx, gverts), None
 
 
 def _aa_maps_shape(values, depth, owner, vertices, faces, edges):
@@ -1270,34 +1288,19 @@ def tri_antialias_maps(values, depth, owner, vertices, faces, edges):
     """The antialias pass over multi-channel maps (include/spherehand_hip.h, shr_tri_antialias_maps_fwd): values
     [B,C,H,W] (tri_interpolate's maps, 1 <= C <= 64) -> [B,C,H,W], every channel the bits of tri_antialias on that plane,
     with each pair decided once for all channels; the other arguments as tri_antialias takes them."""
-    B, NV, F, W, H, C = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
-    with _on(values.device):
-        out = torch.empty_like(values)
-        _lib.check(_lib.lib().shr_tri_antialias_maps_fwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices),
-                                                         _ptr(faces), _ptr(edges), B, NV, F, W, H, C, _ptr(out),
-                                                         _stream()), "shr_tri_antialias_maps_fwd")
-    return out
+    dims = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
+    return _aa_call_fwd("shr_tri_antialias_maps_fwd", (values, depth, owner, vertices, faces, edges), *dims)
 
 
 def tri_antialias_maps_bwd(values, depth, owner, vertices, faces, edges, grad_out, want_values=True, want_vertices=True):
     """tri_antialias_maps's backward: (grad_values [B,C,H,W] or None, grad_vertices [B,NV,4] = (d/dx, d/dy, 0, 0) or
     None); the vertex sums are deterministic fixed point."""
-    B, NV, F, W, H, C = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
+    dims = _aa_maps_shape(values, depth, owner, vertices, faces, edges)
     _check_input(grad_out, "grad_out")
     if grad_out.shape != values.shape or grad_out.device != values.device:
         raise RuntimeError("grad_out must be [B,C,H,W] as values, on their device")
-    if not (want_values or want_vertices):
-        return None, None
-    lib = _lib.lib()
-    with _on(values.device):
-        gvals = torch.empty_like(values) if want_values else None
-        gverts = torch.empty((B, NV, 4), dtype=torch.float32, device=values.device) if want_vertices else None
-        ws = torch.empty((max(16, lib.shr_tri_antialias_maps_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
-                         device=values.device) if want_vertices else None
-        _lib.check(lib.shr_tri_antialias_maps_bwd(_ptr(values), _ptr(depth), _ptr(owner), _ptr(vertices), _ptr(faces),
-                                                  _ptr(edges), B, NV, F, W, H, C, _ptr(grad_out), _ptr(gvals),
-                                                  _ptr(gverts), _ptr(ws), _stream()), "shr_tri_antialias_maps_bwd")
-    return gvals, gverts
+    return _aa_call_bwd("shr_tri_antialias_maps_bwd", (values, depth, owner, vertices, faces, edges), grad_out,
+                        want_values, want_vertices, *dims)
 
 
 class TriAntialiasMaps(torch.autograd.Function):
@@ -1307,23 +1310,11 @@ class TriAntialiasMaps(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, values, depth, owner, vertices, faces, edges):
-        if vertices.dim() != 3 or vertices.shape[-1] not in (3, 4):
-            raise RuntimeError("vertices must be [B,NV,3] or [B,NV,4]")
-        ctx.width4 = vertices.shape[-1] == 4
-        v4 = vertices.contiguous() if ctx.width4 else torch.nn.functional.pad(vertices, (0, 1)).contiguous()
-        values, depth, owner = values.contiguous(), depth.contiguous(), owner.contiguous()
-        out = tri_antialias_maps(values, depth, owner, v4, faces, edges)
-        ctx.save_for_backward(values, depth, owner, v4, faces, edges)
-        return out
+        return _aa_forward(ctx, tri_antialias_maps, values, depth, owner, vertices, faces, edges)
 
     @staticmethod
     def backward(ctx, grad_out):
-        values, depth, owner, v4, faces, edges = ctx.saved_tensors
-        gvals, gverts = tri_antialias_maps_bwd(values, depth, owner, v4, faces, edges, grad_out.contiguous().float(),
-                                               ctx.needs_input_grad[0], ctx.needs_input_grad[3])
-        if gverts is not None and not ctx.width4:
-            gverts = gverts[..., :3]
-        return gvals, None, None, gverts, None, None
+        return _aa_backward(ctx, tri_antialias_maps_bwd, grad_out)
 
 
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,

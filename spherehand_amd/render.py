@@ -164,8 +164,7 @@ class DepthRasterization(nn.Module):
         if self.differentiable and vertices.requires_grad and torch.is_grad_enabled():
             if not (vertices.is_cuda and vertices.dtype == torch.float32 and vertices.shape[-1] in (3, 4)):
                 raise RuntimeError("the differentiable mesh path takes CUDA fp32 vertices [B,NV,3 or 4]")
-            v4 = vertices if vertices.shape[-1] == 4 else torch.nn.functional.pad(vertices, (0, 1))
-            return ops.MeshDepthRaster.apply(v4, self.faces_i32, self.height, 640, 100.0)
+            return ops.MeshDepthRaster.apply(ops.vertices4(vertices)[0], self.faces_i32, self.height, 640, 100.0)
         on_kernel = vertices.is_cuda and vertices.shape[-1] == 4 and vertices.dtype == torch.float32
         if on_kernel and self.fused and self.width == self.height and 2 * self.width <= 641:
             # raster + clamp + resize in one pass over the sampled source pixels only
@@ -208,8 +207,7 @@ class TriangleDepthRaster(nn.Module):
         v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
         if v.requires_grad and torch.is_grad_enabled():
             return ops.TriRasterIndexed.apply(v, self.faces_i32, self.width, self.height)
-        v4 = v if v.shape[-1] == 4 else torch.nn.functional.pad(v, (0, 1))
-        return ops.tri_raster_indexed_fwd(self.width, self.height, v4.contiguous(), self.faces_i32)
+        return ops.tri_raster_indexed_fwd(self.width, self.height, ops.vertices4(v)[0], self.faces_i32)
 
 
 class AntialiasedDepthRaster(nn.Module):

@@ -142,15 +142,19 @@ def _asm(unit, tmp_path):
     return open(out).read()
 
 
-def test_antialias_unit_uses_no_scratch_and_no_scalar_stores(tmp_path):
+def test_antialias_pass_uses_no_scratch_and_no_scalar_stores(tmp_path):
+    """The merged unit (one plane and maps): every kernel of the one pass."""
     text = _asm("tri_antialias", tmp_path)
     meta = text[text.index("amdhsa.kernels:"):]
     d = {}
     for block in meta.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         d[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1)) for k in ("vgpr_count", "private_segment_fixed_size")}
-    assert len([n for n in d if "aa_pixel_kernel" in n]) == 2                 # forward and value gradient
+    # the one pass: the pixel kernel with C a run-time argument and with C = 1 at compile time (the single plane), the tap
+    # walker with a run-time C alone -- no second set of instances
+    assert len([n for n in d if "aa_pixel_kernel" in n]) == 4                 # (forward, value gradient) x (C, 1)
     assert len([n for n in d if "AATaps" in n]) == 3                          # maximum, LDS sums, global sums
+    assert len(d) == 4 + 3 + 2                                                # ... and fixed_point.h's clear and conversion
     assert all(v["private_segment_fixed_size"] == 0 for v in d.values()), d
     # one 16-wave workgroup of the fixed-point passes per CU at least; the pixel kernels at full occupancy
     assert all(v["vgpr_count"] <= 64 for n, v in d.items() if "AATaps" in n or "aa_pixel" in n), d

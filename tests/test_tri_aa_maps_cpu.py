@@ -1,10 +1,9 @@
 """The antialias pass over multi-channel maps without a GPU: the C ABI's new entries, their argument checks, the
-wrappers' checks, and the new unit's kernel resources (tri_antialias.hip's own are checked, unchanged, by
+wrappers' checks, and that the pass is stated once (tri_antialias.hip's kernel resources are checked by
 tests/test_tri_aa_cpu.py)."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 import torch
@@ -113,44 +112,23 @@ def test_module_builds_the_depth_modules_tables():
         a(torch.zeros(4, 2), torch.zeros(4, 1))
 
 
-def _asm(unit, tmp_path):
-    from spherehand_amd import build
-    out = str(tmp_path / (unit + ".s"))
-    flags = [f for f in build.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.check_call([build.HIPCC] + flags + ["-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
-                                                   "-I", os.path.join(build.PKG, "csrc"), "-o", out,
-                                                   os.path.join(build.PKG, "csrc", unit + ".hip")],
-                          stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def test_maps_unit_uses_no_scratch_and_no_scalar_stores(tmp_path):
-    text = _asm("tri_antialias_maps", tmp_path)
-    meta = text[text.index("amdhsa.kernels:"):]
-    d = {}
-    for block in meta.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        d[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1)) for k in ("vgpr_count", "private_segment_fixed_size")}
-    assert len([n for n in d if "aa_maps_pixel_kernel" in n]) == 2              # forward and value gradient
-    assert len([n for n in d if "AAMapsTaps" in n]) == 3                        # maximum, LDS sums, global sums
-    assert all(v["private_segment_fixed_size"] == 0 for v in d.values()), d
-    # the single-plane kernels' budget: one 16-wave workgroup of the fixed-point passes per CU at least, the pixel kernels
-    # at full occupancy
-    assert all(v["vgpr_count"] <= 64 for n, v in d.items() if "AAMapsTaps" in n or "aa_maps_pixel" in n), d
-    sizes = [int(v) for v in re.findall(r"; ScratchSize: (\d+)", text)]
-    assert len(sizes) == len(d) and max(sizes) == 0, sizes
-    mnemonics = {l.split()[0] for l in text.split("\n") if l.startswith("\t") and l.strip() and not l.strip().startswith((".", ";"))}
-    scalar_writes = [m for m in mnemonics if m.startswith("s_") and ("store" in m or "atomic" in m or m.endswith("_wb"))]
-    assert not scalar_writes, scalar_writes
-
-
-def test_pair_decision_lives_in_one_header():
-    """Both units take pair_blend from csrc/tri_aa_pair.h; neither restates it."""
+def test_pair_decision_lives_in_one_file():
+    """The pass is one unit: pair_blend, one pixel kernel template and one tap walker, each stated once under csrc/; the
+    copies the pass, the raster's backward and the interpolation once kept of each other are gone."""
     csrc = os.path.join(ROOT, "spherehand_amd", "csrc")
-    header = open(os.path.join(csrc, "tri_aa_pair.h")).read()
-    for name in ("struct AAArgs", "struct PairBlend", "aa_sorts(", "aa_corners(", "aa_drawn(", "PairBlend pair_blend(",
-                 "void each_pair(", "int aa_fix_bits(", "int aa_check("):
-        assert name in header, name
-    for unit in ("tri_antialias.hip", "tri_antialias_maps.hip"):
-        text = open(os.path.join(csrc, unit)).read()
-        assert '#include "tri_aa_pair.h"' in text and "PairBlend pair_blend(" not in text, unit
+    texts = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".h", ".hip"))}
+    count = lambda pat: {n: len(re.findall(pat, t)) for n, t in texts.items() if re.search(pat, t)}   # noqa: E731
+    assert count(r"PairBlend pair_blend\(") == {"tri_antialias.hip": 1}
+    unit = texts["tri_antialias.hip"]
+    for name in ("struct AAArgs", "struct PairBlend", "aa_sorts(", "aa_corners(", "aa_drawn(", "int aa_check("):
+        assert name in unit, name
+    assert "tri_antialias_maps.hip" not in texts and "tri_aa_pair.h" not in texts
+    # one pixel kernel template and one tap walker of the pass, whatever their names
+    assert count(r"__global__[^;{]*\baa_\w*pixel\w*\(") == {"tri_antialias.hip": 1}
+    assert count(r"\bstruct AA\w*Taps\b") == {"tri_antialias.hip": 1}
+    assert count(r"\baa_pixel_kernel\(") == {"tri_antialias.hip": 1} and count(r"\bstruct AATaps\b") == {"tri_antialias.hip": 1}
+    # one bit bound and one pixel indexer for every fixed-point backward
+    assert count(r"\bint fix_term_bits\(") == {"fixed_point.h": 1} and count(r"\bstruct PixelWalk\b") == {"fixed_point.h": 1}
+    for gone in ("aa_maps_pixel_kernel", "AAMapsTaps", "each_pair", "raster_fix_bits", "interp_fix_bits", "aa_fix_bits",
+                 "InterpWalk"):
+        assert not count(r"\b%s\b" % gone), gone
