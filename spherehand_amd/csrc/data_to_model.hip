@@ -371,10 +371,8 @@ d2m_compact_kernel(const float *__restrict__ depth, int H, int W, int geom, uint
   // the compiler kept the loads "in flight" into the second pass and put vmcnt(3) .. vmcnt(0) in front of whatever reads
   // or reuses their registers there -- between the point stores, which count in the same in-order vmcnt queue: a wave stood
   // with at most three stores under way (SQ counters, round 5: 59 % of this kernel's wave cycles parked at a wait).
-#ifndef EXP_COMPACT_NO_FENCE
 #pragma unroll
   for (int k = 0; k < kCompactUnits; k++) asm volatile("" : : "v"(t[k].x), "v"(t[k].y), "v"(t[k].z), "v"(t[k].w));
-#endif
   __syncthreads();
   // tile prefix: lane = position of a tile in the region's boustrophedon order (at most 64 tiles)
   const int nsb = (kCompactWaves + SB - 1) / SB, ntiles = nsb * NC;
@@ -485,11 +483,7 @@ d2m_points_kernel(const uint2 *__restrict__ points, const int *__restrict__ coun
   while (g < G) {
     const int gn = g + stride;
     if (gn < G) load_group(gn, en);               // the next group's points travel while this one is searched
-#ifndef EXP_NO_SEARCH
     d2m_search_points<K, WANT_GRAD>(ctx, e, min(GS, T - g * GS), loss_fx);
-#else
-    loss_fx += (long long)e[0].x + (long long)e[3].z;
-#endif
 #pragma unroll
     for (int i = 0; i < K; i++) e[i] = en[i];
     g = gn;

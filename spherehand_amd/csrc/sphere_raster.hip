@@ -374,9 +374,14 @@ static int sphere_raster_mse_launch(const float *spheres, const int32_t *crop_in
   // Two workgroups per CU when the launch has them (forward with owner map, 1152 crops @256x256: 157 -> 95 us with the
   // box z-buffer at half of the LDS, tools/exp_fwd256.py): the box variant, 64 VGPRs, zcells cells of z-buffer.
   const size_t half = kMaxLds / 2;
-  const bool box_ok = is_pow2(W) && is_pow2(H) && W >= 32 && lds > half && (long long)N * regions >= 2LL * num_cus() &&
+  // (the box kernel rotates a crop's regions whenever their count is a multiple of four, with a mask that permutes them
+  // only when the count is a power of two: any other multiple of four -- none that mse_rows() produces for a power-of-two
+  // image today -- takes the whole-region kernel, which keeps the image's order)
+  const bool rotates = (regions & 3) != 0 || is_pow2(regions);
+  const bool box_fits = is_pow2(W) && is_pow2(H) && W >= 32 && rotates;
+  const bool box_ok = box_fits && lds > half && (long long)N * regions >= 2LL * num_cus() &&
                       half >= kHdrBytes + part + 8 * (size_t)max_box_pitch(W) * 8;
-  const int box = g_tune.mse_box < 0 ? (box_ok ? 1 : 0) : (g_tune.mse_box && is_pow2(W) && is_pow2(H) && W >= 32);
+  const int box = g_tune.mse_box < 0 ? (box_ok ? 1 : 0) : (g_tune.mse_box && box_fits);
   if (box) {
     size_t blds = g_tune.mse_box > 1 ? (size_t)g_tune.mse_box : half;
     const size_t least = kHdrBytes + part + 8 * (size_t)max_box_pitch(W) * 8;

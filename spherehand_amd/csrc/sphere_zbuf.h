@@ -100,6 +100,21 @@ constexpr int kOffNext = 2304 + 64;       // [64] float4: the NEXT crop's record
 constexpr int kHdrBytes = kOffNext + 1024 + SHR_HDR_PAD;   // (SHR_HDR_PAD: experiment -- where the z-buffers start relative to the LDS banks)
 constexpr int kMaxFastWidth = 8192;  // 16-bit fields of the work items
 
+// The slots of the header's flag words: what one lane decides for the workgroup in front of a barrier and every wave
+// reads back behind it.
+enum {
+  kFlagGeneral = 0,   // the whole region takes the tile code (a sphere that is not tame, none at or in front of the background, ...)
+  kFlagTotal = 1,     // chunks in the work list
+  // forward with BOX: what the stream-out writes, [lo, hi) in 16-byte chunks (VEC4) or pixels; forward without BOX and the
+  // fused kernel: the touched UNITS [ua, ub); backward: the touched ROWS [cv0, cv1]
+  kFlagOutLo = 2, kFlagOutHi = 3,
+  // BOX: the z-buffer's rows [kFlagBoxRow0, kFlagBoxRowEnd) and columns [kFlagBoxCol0, kFlagBoxCol0 + kFlagBoxWidth) at
+  // kFlagPitch cells per row, the walks' clip row, the rows [kFlagTileLo, kFlagTileHi) left to the tile code
+  kFlagBoxRow0 = 4, kFlagBoxRowEnd = 5, kFlagBoxCol0 = 6, kFlagBoxWidth = 7, kFlagPitch = 8, kFlagClip = 9,
+  kFlagTileLo = 10, kFlagTileHi = 11,
+  kFlagMayTie = 12,   // a sphere is centred behind the background: only such a one can hit at exactly 100.0 (tie_owner)
+};
+
 __device__ __forceinline__ uint32_t depth_key(float d) {
   const uint32_t b = __float_as_uint(d);
   return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
@@ -948,9 +963,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   // vmcnt(0) -- which at run time waits for the stores issued since: vmcnt counts loads and stores in one in-order queue and
   // the stream stores are asm statements the compiler does not count.  The storing waves stood at the scan's entry until
   // their background rows had reached memory.
-#ifndef EXP_NO_RECORD_FENCE
   asm volatile("" : : "v"(sph.x), "v"(sph.y), "v"(sph.z), "v"(sph.w));
-#endif
   if (list_wave) {
     s_sph[lane] = sph;
     // general path unless every sphere is tame and at least one has z <= 100: a pixel's
@@ -966,9 +979,9 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
                                                       TABLE ? s_run : nullptr);
     SHR_TL(0, 7);   // (list wave) the work list stands
     if (lane == 0) {
-      s_flag[0] = (bad != 0ull) || (low == 0ull) || too_big;
-      s_flag[1] = total;
-      s_flag[12] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
+      s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
+      s_flag[kFlagTotal] = total;
+      s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
     }
   }
 
@@ -1042,7 +1055,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   };
   if (VEC4 && bg_wave) store_background(nwaves == 1 ? 0 : wave_s - bg_first, nwaves == 1 ? 1 : nbgw);
   if (!BOX) {
-    if (VEC4 && wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) { s_flag[2] = ua; s_flag[3] = ub; }   // for the other waves
+    if (VEC4 && wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) { s_flag[kFlagOutLo] = ua; s_flag[kFlagOutHi] = ub; }   // for the other waves
   } else if (wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) {
     // Everything the other waves derive from the box, computed ONCE (the stores above drain meanwhile): sixteen
     // waves repeating this scalar arithmetic -- a division among it -- after the barrier cost 2 k cycles per crop.
@@ -1058,15 +1071,15 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     // on -- to the general tile code, which writes whole rows itself: no second pass, no loop around the scan.
     const int split = (cv0 + zcells / pitch) & ~(kTileH - 1);           // (zcells / pitch >= 8: the launcher's budget)
     const bool over = split <= cv1;
-    s_flag[2] = out_lo;
-    s_flag[3] = over ? min(out_hi, (split - r0) * row_len) : out_hi;
-    s_flag[4] = cv0; s_flag[5] = over ? split : cv1 + 1; s_flag[6] = cu0; s_flag[7] = bw;
-    s_flag[8] = pitch;
-    s_flag[9] = over ? split : r1;                                      // the scan conversion's clip row
+    s_flag[kFlagOutLo] = out_lo;
+    s_flag[kFlagOutHi] = over ? min(out_hi, (split - r0) * row_len) : out_hi;
+    s_flag[kFlagBoxRow0] = cv0; s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; s_flag[kFlagBoxCol0] = cu0; s_flag[kFlagBoxWidth] = bw;
+    s_flag[kFlagPitch] = pitch;
+    s_flag[kFlagClip] = over ? split : r1;                                      // the scan conversion's clip row
     // tile rows: from the split to the end of the touched units (rows below the box inside them are background,
     // which the tile code reproduces), on tile boundaries
-    s_flag[10] = over ? split : r1;
-    s_flag[11] = over ? min(r1, (r0 + (out_hi + row_len - 1) / row_len + kTileH - 1) & ~(kTileH - 1)) : r1;
+    s_flag[kFlagTileLo] = over ? split : r1;
+    s_flag[kFlagTileHi] = over ? min(r1, (r0 + (out_hi + row_len - 1) / row_len + kTileH - 1) & ~(kTileH - 1)) : r1;
   }
   SHR_TL(0, 1);   // this wave's work in front of the first barrier is done (list / table / background rows / init)
   __syncthreads();
@@ -1077,20 +1090,20 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   float4 sph_next = make_float4(0.f, 0.f, 0.f, 0.f);
   if (pf_wave && has_next && valid) sph_next = spheres[(size_t)(n + crop_step) * J + lane];
 
-  const bool general = s_flag[0] != 0;   // workgroup-uniform: the whole region takes the tile code
-  const bool may_tie = rfl(s_flag[12]) != 0;
+  const bool general = s_flag[kFlagGeneral] != 0;   // workgroup-uniform: the whole region takes the tile code
+  const bool may_tie = rfl(s_flag[kFlagMayTie]) != 0;
   int tile_lo = r0, tile_hi = r1;        // rows for the tile code
   if (!general) {
     // (BOX = false: the z-buffer holds the whole region at the image's own pitch -- one workgroup per CU has the LDS
     // for it, and nothing has to be derived from a box)
     int out_lo = 0, out_hi = VEC4 ? nchunk : rh * W;
-    if (!BOX && VEC4) { out_lo = rfl(s_flag[2]) << 6; out_hi = min(rfl(s_flag[3]) << 6, nchunk); }
-    if (BOX) { out_lo = rfl(s_flag[2]); out_hi = rfl(s_flag[3]); }
-    const int p0 = BOX ? rfl(s_flag[4]) : r0, pe = BOX ? rfl(s_flag[5]) : r1;
-    const int cu0 = BOX ? rfl(s_flag[6]) : 0, bw = BOX ? rfl(s_flag[7]) : W;
-    const int pitch = BOX ? rfl(s_flag[8]) : W + kRowPad, clip = BOX ? rfl(s_flag[9]) : r1;
-    tile_lo = BOX ? rfl(s_flag[10]) : r1;
-    tile_hi = BOX ? rfl(s_flag[11]) : r1;
+    if (!BOX && VEC4) { out_lo = rfl(s_flag[kFlagOutLo]) << 6; out_hi = min(rfl(s_flag[kFlagOutHi]) << 6, nchunk); }
+    if (BOX) { out_lo = rfl(s_flag[kFlagOutLo]); out_hi = rfl(s_flag[kFlagOutHi]); }
+    const int p0 = BOX ? rfl(s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(s_flag[kFlagBoxRowEnd]) : r1;
+    const int cu0 = BOX ? rfl(s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(s_flag[kFlagBoxWidth]) : W;
+    const int pitch = BOX ? rfl(s_flag[kFlagPitch]) : W + kRowPad, clip = BOX ? rfl(s_flag[kFlagClip]) : r1;
+    tile_lo = BOX ? rfl(s_flag[kFlagTileLo]) : r1;
+    tile_hi = BOX ? rfl(s_flag[kFlagTileHi]) : r1;
 
     // ---- scan-convert the chunk list ---------------------------------------------------
     // A chunk may reach below its sphere's box (rows that are real pixels, or lie beyond the
@@ -1102,7 +1115,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
       wl.end = s_ends[lane];
       Key *zb = zbuf - (p0 * pitch + cu0);   // cell of pixel (v, u) = zb[v * pitch + u]
       walk_my_slice<POW2, kSphereCostFwd | (SEG2 ? kSeg2Tag : 0), true, TABLE>(
-          wl, J, s_flag[1], wave, nwaves, shares, lane, ax, ay, 0, clip, pitch,
+          wl, J, s_flag[kFlagTotal], wave, nwaves, shares, lane, ax, ay, 0, clip, pitch,
           [&](int j, const float4 s, int cell_a, int cell_b, float, float ca, float yga, float ygb, bool ok_a,
               bool ok_b, bool has_b, auto row_test) {
             const float dya = yga - s.y, dyb = ygb - s.y;
@@ -1321,7 +1334,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     SHR_TL(1, 6);   // (lead waves) the records have arrived, the touched rows are known
     if (wave_s == 0) {
       s_sph[lane] = sph;
-      if (!WHOLE && lane == 0) { s_flag[2] = lead_v0; s_flag[3] = lead_v1; }
+      if (!WHOLE && lane == 0) { s_flag[kFlagOutLo] = lead_v0; s_flag[kFlagOutHi] = lead_v1; }
     }
   }
   // WHOLE (the buffers hold the whole crop: one workgroup per CU): rows sit at their own index, one pass over
@@ -1331,8 +1344,8 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
   int cv0 = 0, cv1 = H - 1;
   if (!WHOLE) {
     __syncthreads();
-    cv0 = rfl(s_flag[2]);
-    cv1 = rfl(s_flag[3]);
+    cv0 = rfl(s_flag[kFlagOutLo]);
+    cv1 = rfl(s_flag[kFlagOutHi]);
   }
 
   // Passes over the touched rows (one, unless they exceed the staging buffers).  The first pass's list and
@@ -1342,7 +1355,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     if (wave_s == 0) {
       bool too_big;   // excluded by the launcher (W <= kMaxFastWidth)
       const int total = build_work_list<kSphereCostBwd | (SEG2 ? kSeg2Tag : 0)>(sph, lane < J, ax, ay, kx, ky, W, r0, r1, s_items, s_ends, lane, &too_big);
-      if (lane == 0) s_flag[1] = total;
+      if (lane == 0) s_flag[kFlagTotal] = total;
       SHR_TL(1, 7);   // (wave 0) the work list stands
     }
   };
@@ -1473,7 +1486,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     const int cell_max = rh * LW - 1;
     const WaveList wl = load_wave_list(s_sph, s_items, s_ends, lane);
     walk_my_slice<POW2, kSphereCostBwd | (SEG2 ? kSeg2Tag : 0), false>(
-        wl, J, s_flag[1], wave, NW, shares, lane, ax, ay, r0, r1, LW,
+        wl, J, s_flag[kFlagTotal], wave, NW, shares, lane, ax, ay, r0, r1, LW,
         [&](int j, const float4 s, int cell_a, int cell_b, float dx, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto) {
           // lanes without a pixel may point past the pass: clamped, and never counted.  Most chunks own nothing: only
@@ -1583,10 +1596,9 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   // only store background and sum the error, against ~25 us for a region with the hand in it: all of them at the END of the
   // launch they fill the slots the last round of long workgroups leaves idle (1152 crops @256 x 256: 149.5 -> 147.4 us; the other
   // rotations 153 / 162 us -- a long workgroup in the tail -- and any order that MIXES short and long ones 162-200 us: the dispatcher
-  // hands workgroups to the CUs in turn, not to the first free one).
-#ifndef EXP_MSE_NO_ROTATE
+  // hands workgroups to the CUs in turn, not to the first free one).  The mask makes this a permutation of the regions only
+  // for a power-of-two count: the launcher gives this variant no other multiple of four (sphere_raster.hip).
   if (BOX && !PERSIST && (nregions & 3) == 0) region = (region + (nregions >> 2)) & (nregions - 1);
-#endif
   // Every crop starts from OPAQUE copies of the launch constants and of the thread index: otherwise the compiler
   // hoists each crop-invariant value out of the crop loop and keeps it in a register (forward: 92 instead of 51
   // VGPRs; the fused kernel spilled).
@@ -1603,13 +1615,6 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   // (BOX: the prologue and the convert pass -- the phases that wait for memory and issue the stores -- outrank the co-resident
   // workgroup's scan / walk, see the forward: 1152 crops @128 x 128 43.3 -> 42.5 us, 9216 crops 302 -> 293, @256 x 256 160.1 -> 159.5)
   if (BOX) __builtin_amdgcn_s_setprio(1);
-#ifdef EXP_MSE_STAGGER   // (timing experiment: the second workgroup of every CU starts EXP_MSE_STAGGER x 3.4 us late)
-  {
-    const unsigned wg = blockIdx.x + blockIdx.y * gridDim.x;
-    if (wg >= 256u && wg < 512u)
-      for (int k = 0; k < EXP_MSE_STAGGER; k++) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   SHR_TL_ENTRY(2);
   const int r0 = region * rows_per_region;
   const int r1 = min(H, r0 + rows_per_region);
@@ -1619,22 +1624,14 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   const float kx = axk.kx, ky = axk.ky;   // pixels per millimetre (launch constants: common.h AxisK)
   const int wave_s = rfl(wave);
   // (ONE wave derives the touched box and publishes it: this kernel stores the background rows in its convert pass -- see
-  // there --, so the forward's seven storing waves would each evaluate the box for nothing; EXP_MSE_BG_PROLOGUE brings them back)
-#if defined(EXP_MSE_BG_PROLOGUE) || defined(EXP_MSE_SEVEN_BOXES)
-  constexpr int kBgW = BOX ? kBgWavesBox : kBgWaves;
-#else
+  // there --, so the forward's seven storing waves would each evaluate the box for nothing)
   constexpr int kBgW = 1;
-#endif
   const bool bg_wave = wave_s >= 1 && wave_s <= kBgW;
   const bool valid = lane < J;
   const bool pf_wave = wave_s == kZWaves - 1;
   const bool has_next = PERSIST && n + crop_step < N;
   // crop_index (shr_sphere_raster_mse_indexed): workgroup n renders crop c = crop_index[n] of the batch -- its records,
   // its observed image, its slot of the depth output -- and reports into slot n of the partial results
-#if defined(EXP_MSE_EMPTY) && EXP_MSE_EMPTY == 3   // (timing experiment: the launch alone -- every workgroup returns at once)
-  if (tid == 0 && n == 0x7fffffff) sse_out[0] = 0.f;
-  return;
-#endif
   const int c = crop_index ? crop_index[n] : n;
   float4 sph = make_float4(0.f, 0.f, 0.f, 0.f);
   if (valid && (wave_s == 0 || bg_wave))   // the others: wave 0's LDS copy, later
@@ -1663,18 +1660,10 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   // conversion instead of costing the convert pass one HBM round trip per unit.
   constexpr int kTgtAhead = 4;   // a 128x128 crop / a 64-row region of a 256-wide one: 64 units, four per wave
   float4 tpre[kTgtAhead];
-#ifdef EXP_MSE_LATE_TARGET    // (experiment: requested past the first barrier, under the scan, instead of at the kernel's entry)
-#elif !defined(EXP_MSE_SKIP_TARGET)   // (timing experiment: the observed image is never read)
 #pragma unroll
   for (int k = 0; k < kTgtAhead; k++) tpre[k] = tgt4[min(((wave_s + (k << 4)) << 6) + lane, nchunk - 1)];
-#else
-#pragma unroll
-  for (int k = 0; k < kTgtAhead; k++) tpre[k] = make_float4((float)lane, 1.f, 2.f, (float)k);
-#endif
   int ua = 0, ub = nunits;
-#ifndef EXP_NO_RECORD_FENCE
   asm volatile("" : : "v"(sph.x), "v"(sph.y), "v"(sph.z), "v"(sph.w));   // (the records: waited for by every wave, see the forward)
-#endif
   if (bg_wave) {   // rows no sphere touches: depth = background, stored while wave 0 builds the list
     int cv0, cv1, cu0 = 0, cu1 = W - 1;
     if (BOX) touched_box(sph, valid, ax, ay, kx, ky, W, r0, r1, lane, cv0, cv1, cu0, cu1);
@@ -1684,14 +1673,14 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     ua = rfl(ua);
     ub = rfl(ub);
     if (wave_s == 1 && lane == 0) {
-      s_flag[2] = ua; s_flag[3] = ub;
+      s_flag[kFlagOutLo] = ua; s_flag[kFlagOutHi] = ub;
       if (BOX) {   // everything the other waves derive from the box (see the forward)
         cu0 &= ~3;
         const int bw = cu1 >= cu0 ? ((cu1 | 3) - cu0 + 1) : 4;
         int pitch = box_pitch(bw);
         // A box whose rows do not all fit at that pitch would leave its last rows to the tile code -- at 256 x 256 nearly
         // every hand region: 64 rows x 136 cells against 8 504 in half of a CU's LDS, i.e. EIGHT rows of tile code per
-        // region, 14-17 us of the kernel's 160 (round 6, EXP_MSE_SKIP_TILE).  A tighter row pitch (even: 16-byte cell pairs;
+        // region, 14-17 us of the kernel's 160 (round 6, docs/EXPERIMENTS.md S5).  A tighter row pitch (even: 16-byte cell pairs;
         // never a multiple of 32 cells) that holds the whole box is taken instead: the padding only spreads a chunk's rows
         // over the banks, no lane writes there, and the waves wait for LDS 1-2 % of their cycles.
         if ((cv1 - cv0 + 1) * pitch > zcells) {
@@ -1700,29 +1689,19 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
         }
         const int split = (cv0 + zcells / pitch) & ~(kTileH - 1);        // rows [cv0, split) fit the z-buffer
         const bool over = split <= cv1;
-        s_flag[4] = cv0; s_flag[5] = over ? split : cv1 + 1; s_flag[6] = cu0; s_flag[7] = bw;
-        s_flag[8] = pitch;
-        s_flag[9] = over ? split : r1;                                   // the walks' clip row
+        s_flag[kFlagBoxRow0] = cv0; s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; s_flag[kFlagBoxCol0] = cu0; s_flag[kFlagBoxWidth] = bw;
+        s_flag[kFlagPitch] = pitch;
+        s_flag[kFlagClip] = over ? split : r1;                                   // the walks' clip row
         // tile rows: from the split to the end of the touched units (whole units: W >= 32 is a power of two)
-        s_flag[10] = over ? split : r1;
-        s_flag[11] = over ? min(r1, (r0 + ((ub << 6) + w4 - 1) / w4 + kTileH - 1) & ~(kTileH - 1)) : r1;
+        s_flag[kFlagTileLo] = over ? split : r1;
+        s_flag[kFlagTileHi] = over ? min(r1, (r0 + ((ub << 6) + w4 - 1) / w4 + kTileH - 1) & ~(kTileH - 1)) : r1;
       }
     }
     // The background rows' depth is NOT stored here, as the forward does it, but by the convert pass below, unit by unit:
     // this kernel has the observed image's pieces in flight from its entry, and a store issued behind them makes every later
     // wait for a piece a wait for that store (one in-order vmcnt queue).  Stored here, the untouched rows cost the kernel
-    // 7 us more at 1152 crops @256 x 256 (157.2 -> 150.0), 2.1 of 41.7 at 128 x 128, 18 of 295 at 9216 crops.
-#ifdef EXP_MSE_BG_PROLOGUE
-    if (out) {
-      const float4 bgd = make_float4(kBackground, kBackground, kBackground, kBackground);
-      const int nbg = ua + (nunits - ub);
-      for (int t = wave_s - 1; t < nbg; t += kBgW) {
-        const int u = t < ua ? t : t - ua + ub;
-        const int c = (u << 6) + lane;
-        if (c < nchunk) stream_store(out4 + c, bgd);
-      }
-    }
-#endif
+    // 7 us more at 1152 crops @256 x 256 (157.2 -> 150.0), 2.1 of 41.7 at 128 x 128, 18 of 295 at 9216 crops
+    // (docs/EXPERIMENTS.md S5).
   }
   if (wave_s == 0) {
     s_sph[lane] = sph;
@@ -1732,40 +1711,32 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     bool too_big;
     const int total = build_work_list<kSphereCostMse | (SEG2 ? kSeg2Tag : 0)>(sph, valid, ax, ay, kx, ky, W, r0, r1, s_items, s_ends, lane, &too_big);
     if (lane == 0) {
-      s_flag[0] = (bad != 0ull) || (low == 0ull) || too_big;
-      s_flag[1] = total;
-      s_flag[12] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
+      s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
+      s_flag[kFlagTotal] = total;
+      s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
     }
   }
   SHR_TL(2, 1);   // this wave's work in front of the first barrier is done
   __syncthreads();
   if (BOX) __builtin_amdgcn_s_setprio(0);
-#ifdef EXP_MSE_LATE_TARGET
-#pragma unroll
-  for (int k = 0; k < kTgtAhead; k++) tpre[k] = tgt4[min(((wave_s + (k << 4)) << 6) + lane, nchunk - 1)];
-#endif
   SHR_TL(2, 2);   // past the first barrier
-#if defined(EXP_MSE_EMPTY) && EXP_MSE_EMPTY == 1   // (timing experiment: the prologue alone -- every workgroup returns past the first barrier)
-  if (tid == 0) sse_out[(size_t)n * nregions + region] = tpre[0].x + tpre[1].y + tpre[2].z + tpre[3].w + (float)s_flag[1];
-  return;
-#endif
   if (!(wave_s == 0 || bg_wave)) sph = s_sph[lane];
   float4 sph_next = make_float4(0.f, 0.f, 0.f, 0.f);
   if (pf_wave && has_next && valid)
     sph_next = spheres[(size_t)(crop_index ? crop_index[n + crop_step] : n + crop_step) * J + lane];
-  const bool general = s_flag[0] != 0;
-  const bool may_tie = rfl(s_flag[12]) != 0;
-  ua = rfl(s_flag[2]);
-  ub = rfl(s_flag[3]);
+  const bool general = s_flag[kFlagGeneral] != 0;
+  const bool may_tie = rfl(s_flag[kFlagMayTie]) != 0;
+  ua = rfl(s_flag[kFlagOutLo]);
+  ub = rfl(s_flag[kFlagOutHi]);
   // the z-buffer's rows [p0, pe) and columns [cu0, cu0 + bw) at `pitch` (BOX = false: the whole region at the image's
   // own), the walks' clip row, and the rows [tile_lo, tile_hi) that go through the tile code
-  const int p0 = BOX ? rfl(s_flag[4]) : r0, pe = BOX ? rfl(s_flag[5]) : r1;
-  const int cu0 = BOX ? rfl(s_flag[6]) : 0, bw = BOX ? rfl(s_flag[7]) : W;
-  const int pitch = BOX ? rfl(s_flag[8]) : LW, clip = BOX ? rfl(s_flag[9]) : r1;
+  const int p0 = BOX ? rfl(s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(s_flag[kFlagBoxRowEnd]) : r1;
+  const int cu0 = BOX ? rfl(s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(s_flag[kFlagBoxWidth]) : W;
+  const int pitch = BOX ? rfl(s_flag[kFlagPitch]) : LW, clip = BOX ? rfl(s_flag[kFlagClip]) : r1;
   // (both words read whatever `general` says: as conditional reads they gave the compiler a branch structure with a dead edge
   // from here to the closing reductions, along which it believed the observed image's pieces still in flight -- and made every
   // wave wait for its depth stores there)
-  int flag_lo = BOX ? rfl(s_flag[10]) : r1, flag_hi = BOX ? rfl(s_flag[11]) : r1;
+  int flag_lo = BOX ? rfl(s_flag[kFlagTileLo]) : r1, flag_hi = BOX ? rfl(s_flag[kFlagTileHi]) : r1;
   if (BOX) asm volatile("" : "+s"(flag_lo), "+s"(flag_hi));
   const int tile_lo = general ? r0 : flag_lo, tile_hi = general ? r1 : flag_hi;
   Key *zb = zbuf - (p0 * pitch + cu0);   // cell of pixel (v, u) = zb[v * pitch + u]
@@ -1777,23 +1748,13 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     wl.sph = sph;
     wl.item = s_items[lane];
     wl.end = s_ends[lane];
-    // (EXP_MSE_SKIP_*: timing-only ablations of tools/ab_variant.py -- wrong results, never in the product build)
-#ifndef EXP_MSE_SKIP_SCAN
     walk_my_slice<POW2, kSphereCostMse | (SEG2 ? kSeg2Tag : 0), true>(
-        wl, J, s_flag[1], wave, kZWaves, shares_fwd, lane, ax, ay, 0, clip, pitch,
+        wl, J, s_flag[kFlagTotal], wave, kZWaves, shares_fwd, lane, ax, ay, 0, clip, pitch,
         [&](int j, const float4 s, int cell_a, int cell_b, float, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto row_test) {
           const float dya = yga - s.y, dyb = ygb - s.y;
           float qa = ca - dya * dya, qb = ca - dyb * dyb;
           if (decltype(row_test)::value) { qa = ok_a ? qa : -1.f; qb = ok_b ? qb : -1.f; }
-#ifdef EXP_MSE_SCAN_JUNK   // (timing experiment: EXP_MSE_SCAN_JUNK independent VALU instructions more per chunk pair)
-          {
-            float junk = qa;
-#pragma unroll
-            for (int k = 0; k < EXP_MSE_SCAN_JUNK; k++) asm volatile("v_add_f32 %0, %1, %1" : "=v"(junk) : "v"(qb));
-            asm volatile("" : : "v"(junk));
-          }
-#endif
           unsigned jv = (unsigned)j;
           asm("" : "+v"(jv));   // (kept in the low register of the 64-bit pair across the run, see the forward)
           auto put = [&](Key *cell, float d) { atomicMin(cell, ((Key)depth_key(d) << 32) | jv); };
@@ -1807,7 +1768,6 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
           }
         },
         [](int) {});
-#endif
     if (pf_wave && has_next) s_next[lane] = sph_next;
     SHR_TL(2, 3);   // this wave's scan slice is done
     // (a region no sphere touches -- the top and the bottom quarter of a 256 x 256 hand crop cut into four 64-row
@@ -1829,9 +1789,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
       if (u < ua || u >= ub) {   // background rows
         const float e0 = kBackground - t.x, e1 = kBackground - t.y, e2 = kBackground - t.z, e3 = kBackground - t.w;
         sse += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-#if !defined(EXP_MSE_BG_PROLOGUE) && !defined(EXP_MSE_NO_BG_STORE)
         if (out) stream_store(out4 + c, make_float4(kBackground, kBackground, kBackground, kBackground));
-#endif
         return;
       }
       if (BOX) {
@@ -1866,30 +1824,22 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
       cell[0] = k01;
       cell[1] = k23;
     };
-#ifndef EXP_MSE_SKIP_CONVERT
     // Every requested piece of the observed image is waited for HERE, before the pass issues its first store.  vmcnt counts
     // loads and stores in one in-order queue: left alone, the wait in front of piece k covers the stores of units 0 .. k - 1
     // -- conditional, so the compiler cannot count them -- and becomes vmcnt(0) at the last unit and again at the walk's
     // entry (the pieces' registers are reused): the depth stores' write latency on every wave's critical path, twice.
     // The pieces were requested at the kernel's entry; nothing else is in flight but a background wave's early stores.
-#ifndef EXP_MSE_NO_LOAD_FENCE
 #pragma unroll
     for (int k = 0; k < kTgtAhead; k++) asm volatile("" : : "v"(tpre[k].x), "v"(tpre[k].y), "v"(tpre[k].z), "v"(tpre[k].w));
-#endif
 #pragma unroll
     for (int k = 0; k < kTgtAhead; k++)
       if (wave_s + (k << 4) < nunits) convert_unit(wave_s + (k << 4), tpre[k]);
     for (int u = wave_s + (kTgtAhead << 4); u < nunits; u += kZWaves) {
       const int c = (u << 6) + lane;
       float4 t = tgt4[min(c, nchunk - 1)];
-#ifndef EXP_MSE_NO_LOAD_FENCE
       asm volatile("" : "+v"(t.x), "+v"(t.y), "+v"(t.z), "+v"(t.w));   // (as above: no piece is left pending on the paths that do not use it)
-#endif
       convert_unit(u, t);
     }
-#else
-    sse += tpre[0].x + tpre[1].y + tpre[2].z + tpre[3].w;
-#endif
     SHR_TL(2, 5);   // this wave's convert units are done
     if (BOX) __builtin_amdgcn_s_setprio(0);
     if (!untouched) __syncthreads();
@@ -1898,9 +1848,8 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     // ---- walk (backward): static slices, per-run DPP sums into the wave's LDS row ------------
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const int cell_max = (p0 * pitch + cu0) + (pe - p0) * pitch - 1;   // the z-buffer's last cell, as the walk counts cells
-#ifndef EXP_MSE_SKIP_WALK
     walk_my_slice<POW2, kSphereCostMse | (SEG2 ? kSeg2Tag : 0), true>(
-        wl, J, s_flag[1], wave, kZWaves, shares_bwd, lane, ax, ay, 0, clip, pitch,
+        wl, J, s_flag[kFlagTotal], wave, kZWaves, shares_bwd, lane, ax, ay, 0, clip, pitch,
         [&](int j, const float4 s, int cell_a, int cell_b, float dx, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto) {
           auto take = [&](int cell, float yg, bool ok) {
@@ -1925,21 +1874,12 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
           if (lane >= 60) atomicAdd(reinterpret_cast<float *>(s_part + wave * J + j) + (lane & 3), t);
           a0 = a1 = a2 = a3 = 0.f;
         });
-#else
-    (void)cell_max; (void)a0; (void)a1; (void)a2; (void)a3;
-#endif
   }
-#ifndef EXP_MSE_NO_LOAD_FENCE
   if (general) {   // (the pieces nobody used: see the convert pass -- both ways into the code below are now free of pending loads)
 #pragma unroll
     for (int k = 0; k < kTgtAhead; k++) asm volatile("" : : "v"(tpre[k].x), "v"(tpre[k].y), "v"(tpre[k].z), "v"(tpre[k].w));
   }
-#endif
-#ifdef EXP_MSE_SKIP_TILE   // (timing experiment: the rows a box has beyond its z-buffer are dropped instead of going through the tile code)
-  if (false) {
-#else
   if (tile_lo < tile_hi) {
-#endif
     // ---- general path (or the rows beyond the z-buffer): 32x8 tiles, owners and gradient in registers ---
     // (rows_per_region is a multiple of the tile height whenever there are several regions)
     const int tiles_x = (W + kTileW - 1) / kTileW;

@@ -112,6 +112,17 @@ def test_no_wave_waits_for_its_own_stores(descriptors):
         assert not [l for l in body[bars[2]:bars[2] + 300] if "vmcnt" in l], name
 
 
+def test_no_experiment_switch_in_the_product_sources():
+    """Timing ablations that return wrong results (`EXP_*`) once lived inside the product kernels, one compiler flag away from
+    the library (docs/EXPERIMENTS.md S4 / S5, part K): no file of csrc/ names one."""
+    import glob
+    csrc = os.path.join(ROOT, "spherehand_amd", "csrc")
+    files = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert len(files) >= 20
+    hits = [(os.path.basename(f), n + 1) for f in files for n, l in enumerate(open(f)) if re.search(r"\bEXP_[A-Z]", l)]
+    assert not hits, hits
+
+
 @pytest.mark.parametrize("unit", ["tri_raster", "mesh_depth"])
 def test_face_setup_stays_in_registers(unit, tmp_path):
     """The sort of a face's vertices by x is three selects per coordinate; the compiler once turned them into loads from a

@@ -1,6 +1,7 @@
 """A/B of the sphere rasterizer forward / backward between the product library and a variant built with extra -D flags:
-    python tools/ab_variant.py build -DEXP_FLAG ...     (anywhere: tools/libspherehand_exp.so)
-    python tools/ab_variant.py build:NAME -DEXP_FLAG ...   (several variants side by side: tools/libspherehand_exp_NAME.so)
+    python tools/ab_variant.py build -DSHR_ROW_PAD=4 ...     (anywhere: tools/libspherehand_exp.so; any right-result tunable)
+    python tools/ab_variant.py build:NAME -DSHR_... ...    (several variants side by side: tools/libspherehand_exp_NAME.so)
+(another commit's library copied to tools/libspherehand_exp_NAME.so is a variant like any other)
     python tools/ab_variant.py                          (GPU box: alternating timings at 256 / 1152 / 9216 crops, same-bits check,
                                                          the product library against every variant library found)"""
 import ctypes, glob, os, subprocess, sys
