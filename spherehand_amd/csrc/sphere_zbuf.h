@@ -100,6 +100,17 @@ constexpr int kOffNext = 2304 + 64;       // [64] float4: the NEXT crop's record
 constexpr int kHdrBytes = kOffNext + 1024 + SHR_HDR_PAD;   // (SHR_HDR_PAD: experiment -- where the z-buffers start relative to the LDS banks)
 constexpr int kMaxFastWidth = 8192;  // 16-bit fields of the work items
 
+// The header as every kernel of this file sees it: a view built from the workgroup's dynamic LDS.
+struct LdsHeader {
+  float4 *s_sph;     // [64] the crop's records, lane j = sphere j
+  int4 *s_items;     // [64] the work items (build_work_list)
+  int *s_ends, *s_flag;   // [64] weight prefix after each sphere; [16] the flag words below
+  float4 *s_next;    // [64] the next crop's records
+  __device__ __forceinline__ explicit LdsHeader(unsigned char *smem)
+      : s_sph(reinterpret_cast<float4 *>(smem)), s_items(reinterpret_cast<int4 *>(smem + kOffItems)),
+        s_ends(reinterpret_cast<int *>(smem + kOffEnds)), s_flag(reinterpret_cast<int *>(smem + kOffFlags)),
+        s_next(reinterpret_cast<float4 *>(smem + kOffNext)) {}
+};
 // The slots of the header's flag words: what one lane decides for the workgroup in front of a barrier and every wave
 // reads back behind it.
 enum {
@@ -822,6 +833,27 @@ __host__ __device__ __forceinline__ int box_pitch(int bw) {
 // the widest pitch any box of a W-pixel row can get
 __host__ __device__ __forceinline__ int max_box_pitch(int W) { return ((W + 3) & ~3) + kRowPad + 8; }
 
+// ---- Stages the forward, the backward and the fused kernel share ----------------------------------------------
+// Every crop starts from OPAQUE copies of the launch constants and of the thread index: otherwise the compiler
+// hoists each crop-invariant value out of the crop loop and keeps it in a register (forward: 92 instead of 51
+// VGPRs; the fused kernel spilled).
+// (`packed`: log2(W / 4) or -1 in the low byte (signed), flag bits in the second byte -- the forward's SHR_RASTER_* flags,
+// the fused kernel's "slots by crop" --, the forward's waves per workgroup in the third: one SGPR less in a kernel whose
+// box variant sits at the occupancy limit of 80.  The backward's word is the plain shift.)
+struct CropConsts {
+  int J, H, W, rows, w4_shift, zcells, tid;   // the opaque copies
+  int flags, nwaves;                          // of the packed word (crop-invariant: free to be hoisted)
+};
+template <bool PERSIST>
+__device__ __forceinline__ CropConsts crop_consts(int J, int H, int W, int rows, int packed, int zcells) {
+  CropConsts c{J, H, W, rows, (int)(signed char)(packed & 0xff), zcells, (int)threadIdx.x, (packed >> 8) & 0xff, (packed >> 16) & 0xff};
+  if (PERSIST) {
+    asm volatile("" : "+s"(c.J), "+s"(c.H), "+s"(c.W), "+s"(c.rows), "+s"(c.w4_shift), "+s"(c.zcells));
+    asm volatile("" : "+v"(c.tid));
+  }
+  return c;
+}
+
 // ---------------------------------------------------------------------------
 // Forward.  grid = (N or fewer, nregions), block = 64 * nwaves (<= 1024), dynamic LDS = kHdrBytes +
 // zcells * sizeof(key).
@@ -850,17 +882,13 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
                        int w4_shift_flags, int shares, int zcells_, AxisK axk) {
   using Key = typename KeyOf<OWNER>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *s_sph = reinterpret_cast<float4 *>(smem);
-  int4 *s_items = reinterpret_cast<int4 *>(smem + kOffItems);
-  int *s_ends = reinterpret_cast<int *>(smem + kOffEnds);
-  int *s_flag = reinterpret_cast<int *>(smem + kOffFlags);
-  float4 *s_next = reinterpret_cast<float4 *>(smem + kOffNext);
+  const LdsHeader hdr(smem);
   Key *zbuf = reinterpret_cast<Key *>(smem + kHdrBytes);
   // TABLE (whole-region z-buffer, one workgroup per CU, not persistent): the run table follows the z-buffer, the
   // spheres' run records take the place of the next crop's records (build_run_table)
   static_assert(!TABLE || (POW2 && VEC4 && !BOX && !PERSIST && !SEG2), "run table: whole-crop workgroups on power-of-two images");
   uint2 *s_tab = reinterpret_cast<uint2 *>(smem + kHdrBytes + (size_t)zcells_ * sizeof(Key));
-  float4 *s_run = s_next;
+  float4 *s_run = hdr.s_next;
 
   // PERSISTENT workgroups: with more crops than the launch has workgroups (gridDim.x < N) a workgroup takes crops
   // blockIdx.x, blockIdx.x + gridDim.x, ...  The youngest wave requests the NEXT crop's records right after the
@@ -869,18 +897,8 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   // the forward at 36 crops per CU, nothing at 4.5 (the launcher decides: sphere_raster.hip persistent_grid).
   const int crop_step = gridDim.x;
   for (int n = blockIdx.x, crop_it = 0; PERSIST ? n < N : crop_it == 0; n += crop_step, ++crop_it) {
-  // Every crop starts from OPAQUE copies of the launch constants and of the thread index: otherwise the compiler
-  // hoists each crop-invariant value out of the crop loop and keeps it in a register (forward: 92 instead of 51
-  // VGPRs; the fused kernel spilled).
-  // (w4_shift_flags: log2(W / 4) or -1 in the low byte (signed), the SHR_RASTER_* flags in the second, the waves per
-  // workgroup in the third -- one SGPR less in a kernel whose box variant sits at the occupancy limit of 80)
-  int J = J_, H = H_, W = W_, rows_per_region = rows_per_region_, w4_shift = (int)(signed char)(w4_shift_flags & 0xff), tid = threadIdx.x;
-  const int flags = (w4_shift_flags >> 8) & 0xff;
-  int zcells = zcells_;
-  if (PERSIST) {
-    asm volatile("" : "+s"(J), "+s"(H), "+s"(W), "+s"(rows_per_region), "+s"(w4_shift), "+s"(zcells));
-    asm volatile("" : "+v"(tid));
-  }
+  const CropConsts cc = crop_consts<PERSIST>(J_, H_, W_, rows_per_region_, w4_shift_flags, zcells_);
+  const int J = cc.J, H = cc.H, W = cc.W, rows_per_region = cc.rows, w4_shift = cc.w4_shift, zcells = cc.zcells, tid = cc.tid, flags = cc.flags;
   const int lane = tid & 63, wave = tid >> 6;
   // BOX (two workgroups per CU): a workgroup in its PROLOGUE -- records, list, background rows: latency and stores, few
   // instructions, and every wave has to arrive -- outranks the co-resident workgroup's scan, whose waves otherwise win the
@@ -892,7 +910,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   SHR_TL_ENTRY(0);
   // (the workgroup size rides in the same launch argument: blockDim.x is a hidden kernel argument that is NOT among
   // the preloaded ones -- reading it put an s_load round trip in front of the records' request)
-  const int nwaves = (w4_shift_flags >> 16) & 0xff, nthr = nwaves << 6;
+  const int nwaves = cc.nwaves, nthr = nwaves << 6;
   const int r0 = blockIdx.y * rows_per_region;
   const int r1 = min(H, r0 + rows_per_region);
   const int rh = r1 - r0;
@@ -919,7 +937,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   const bool tab_wave = TABLE && wave_s >= 1 && wave_s <= 3;
   const bool init_wave = TABLE && wave_s >= 4 && wave_s <= 7;
   float4 sph = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (valid && (list_wave || bg_wave || tab_wave)) sph = crop_it == 0 ? spheres[(size_t)n * J + lane] : s_next[lane];
+  if (valid && (list_wave || bg_wave || tab_wave)) sph = crop_it == 0 ? spheres[(size_t)n * J + lane] : hdr.s_next[lane];
   // (the box variant sits at gfx950's occupancy limit of 80 SGPRs: its axis constants live in vector registers;
   // they are not among the preloaded arguments -- touched here, behind the records' request, not in front of it)
   if (BOX) asm volatile("" : "+v"(ax.mul), "+v"(ay.mul), "+v"(ax.half), "+v"(ay.half));
@@ -965,7 +983,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   // their background rows had reached memory.
   asm volatile("" : : "v"(sph.x), "v"(sph.y), "v"(sph.z), "v"(sph.w));
   if (list_wave) {
-    s_sph[lane] = sph;
+    hdr.s_sph[lane] = sph;
     // general path unless every sphere is tame and at least one has z <= 100: a pixel's
     // minimum can exceed the background only where ALL J spheres hit it, and there the
     // sphere with z <= 100 contributes z - sqrt(q) < 100, so min(100, hits) is exact
@@ -975,13 +993,13 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     const unsigned long long behind = __ballot(valid && sph.z > kBackground);
     SHR_TL(0, 6);   // (list wave) the crop's records have arrived
     bool too_big;   // excluded by the launcher (W <= kMaxFastWidth, H <= 32768)
-    const int total = build_work_list<kSphereCostFwd | (SEG2 ? kSeg2Tag : 0)>(sph, valid, ax, ay, kx, ky, W, r0, r1, s_items, s_ends, lane, &too_big,
+    const int total = build_work_list<kSphereCostFwd | (SEG2 ? kSeg2Tag : 0)>(sph, valid, ax, ay, kx, ky, W, r0, r1, hdr.s_items, hdr.s_ends, lane, &too_big,
                                                       TABLE ? s_run : nullptr);
     SHR_TL(0, 7);   // (list wave) the work list stands
     if (lane == 0) {
-      s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
-      s_flag[kFlagTotal] = total;
-      s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
+      hdr.s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
+      hdr.s_flag[kFlagTotal] = total;
+      hdr.s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
     }
   }
 
@@ -1055,7 +1073,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
   };
   if (VEC4 && bg_wave) store_background(nwaves == 1 ? 0 : wave_s - bg_first, nwaves == 1 ? 1 : nbgw);
   if (!BOX) {
-    if (VEC4 && wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) { s_flag[kFlagOutLo] = ua; s_flag[kFlagOutHi] = ub; }   // for the other waves
+    if (VEC4 && wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) { hdr.s_flag[kFlagOutLo] = ua; hdr.s_flag[kFlagOutHi] = ub; }   // for the other waves
   } else if (wave_s == (nwaves == 1 ? 0 : bg_first) && lane == 0) {
     // Everything the other waves derive from the box, computed ONCE (the stores above drain meanwhile): sixteen
     // waves repeating this scalar arithmetic -- a division among it -- after the barrier cost 2 k cycles per crop.
@@ -1071,39 +1089,39 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     // on -- to the general tile code, which writes whole rows itself: no second pass, no loop around the scan.
     const int split = (cv0 + zcells / pitch) & ~(kTileH - 1);           // (zcells / pitch >= 8: the launcher's budget)
     const bool over = split <= cv1;
-    s_flag[kFlagOutLo] = out_lo;
-    s_flag[kFlagOutHi] = over ? min(out_hi, (split - r0) * row_len) : out_hi;
-    s_flag[kFlagBoxRow0] = cv0; s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; s_flag[kFlagBoxCol0] = cu0; s_flag[kFlagBoxWidth] = bw;
-    s_flag[kFlagPitch] = pitch;
-    s_flag[kFlagClip] = over ? split : r1;                                      // the scan conversion's clip row
+    hdr.s_flag[kFlagOutLo] = out_lo;
+    hdr.s_flag[kFlagOutHi] = over ? min(out_hi, (split - r0) * row_len) : out_hi;
+    hdr.s_flag[kFlagBoxRow0] = cv0; hdr.s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; hdr.s_flag[kFlagBoxCol0] = cu0; hdr.s_flag[kFlagBoxWidth] = bw;
+    hdr.s_flag[kFlagPitch] = pitch;
+    hdr.s_flag[kFlagClip] = over ? split : r1;                                      // the scan conversion's clip row
     // tile rows: from the split to the end of the touched units (rows below the box inside them are background,
     // which the tile code reproduces), on tile boundaries
-    s_flag[kFlagTileLo] = over ? split : r1;
-    s_flag[kFlagTileHi] = over ? min(r1, (r0 + (out_hi + row_len - 1) / row_len + kTileH - 1) & ~(kTileH - 1)) : r1;
+    hdr.s_flag[kFlagTileLo] = over ? split : r1;
+    hdr.s_flag[kFlagTileHi] = over ? min(r1, (r0 + (out_hi + row_len - 1) / row_len + kTileH - 1) & ~(kTileH - 1)) : r1;
   }
   SHR_TL(0, 1);   // this wave's work in front of the first barrier is done (list / table / background rows / init)
   __syncthreads();
   if (BOX) __builtin_amdgcn_s_setprio(0);
   SHR_TL(0, 2);   // past the first barrier: the scan starts
-  if (!(list_wave || bg_wave || tab_wave)) sph = s_sph[lane];
+  if (!(list_wave || bg_wave || tab_wave)) sph = hdr.s_sph[lane];
   const bool has_next = PERSIST && n + crop_step < N;   // (the launcher keeps a prefetch wave whenever gridDim.x < N)
   float4 sph_next = make_float4(0.f, 0.f, 0.f, 0.f);
   if (pf_wave && has_next && valid) sph_next = spheres[(size_t)(n + crop_step) * J + lane];
 
-  const bool general = s_flag[kFlagGeneral] != 0;   // workgroup-uniform: the whole region takes the tile code
-  const bool may_tie = rfl(s_flag[kFlagMayTie]) != 0;
+  const bool general = hdr.s_flag[kFlagGeneral] != 0;   // workgroup-uniform: the whole region takes the tile code
+  const bool may_tie = rfl(hdr.s_flag[kFlagMayTie]) != 0;
   int tile_lo = r0, tile_hi = r1;        // rows for the tile code
   if (!general) {
     // (BOX = false: the z-buffer holds the whole region at the image's own pitch -- one workgroup per CU has the LDS
     // for it, and nothing has to be derived from a box)
     int out_lo = 0, out_hi = VEC4 ? nchunk : rh * W;
-    if (!BOX && VEC4) { out_lo = rfl(s_flag[kFlagOutLo]) << 6; out_hi = min(rfl(s_flag[kFlagOutHi]) << 6, nchunk); }
-    if (BOX) { out_lo = rfl(s_flag[kFlagOutLo]); out_hi = rfl(s_flag[kFlagOutHi]); }
-    const int p0 = BOX ? rfl(s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(s_flag[kFlagBoxRowEnd]) : r1;
-    const int cu0 = BOX ? rfl(s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(s_flag[kFlagBoxWidth]) : W;
-    const int pitch = BOX ? rfl(s_flag[kFlagPitch]) : W + kRowPad, clip = BOX ? rfl(s_flag[kFlagClip]) : r1;
-    tile_lo = BOX ? rfl(s_flag[kFlagTileLo]) : r1;
-    tile_hi = BOX ? rfl(s_flag[kFlagTileHi]) : r1;
+    if (!BOX && VEC4) { out_lo = rfl(hdr.s_flag[kFlagOutLo]) << 6; out_hi = min(rfl(hdr.s_flag[kFlagOutHi]) << 6, nchunk); }
+    if (BOX) { out_lo = rfl(hdr.s_flag[kFlagOutLo]); out_hi = rfl(hdr.s_flag[kFlagOutHi]); }
+    const int p0 = BOX ? rfl(hdr.s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(hdr.s_flag[kFlagBoxRowEnd]) : r1;
+    const int cu0 = BOX ? rfl(hdr.s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(hdr.s_flag[kFlagBoxWidth]) : W;
+    const int pitch = BOX ? rfl(hdr.s_flag[kFlagPitch]) : W + kRowPad, clip = BOX ? rfl(hdr.s_flag[kFlagClip]) : r1;
+    tile_lo = BOX ? rfl(hdr.s_flag[kFlagTileLo]) : r1;
+    tile_hi = BOX ? rfl(hdr.s_flag[kFlagTileHi]) : r1;
 
     // ---- scan-convert the chunk list ---------------------------------------------------
     // A chunk may reach below its sphere's box (rows that are real pixels, or lie beyond the
@@ -1111,11 +1129,11 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     {
       WaveList wl;
       wl.sph = sph;
-      wl.item = s_items[lane];
-      wl.end = s_ends[lane];
+      wl.item = hdr.s_items[lane];
+      wl.end = hdr.s_ends[lane];
       Key *zb = zbuf - (p0 * pitch + cu0);   // cell of pixel (v, u) = zb[v * pitch + u]
       walk_my_slice<POW2, kSphereCostFwd | (SEG2 ? kSeg2Tag : 0), true, TABLE>(
-          wl, J, s_flag[kFlagTotal], wave, nwaves, shares, lane, ax, ay, 0, clip, pitch,
+          wl, J, hdr.s_flag[kFlagTotal], wave, nwaves, shares, lane, ax, ay, 0, clip, pitch,
           [&](int j, const float4 s, int cell_a, int cell_b, float, float ca, float yga, float ygb, bool ok_a,
               bool ok_b, bool has_b, auto row_test) {
             const float dya = yga - s.y, dyb = ygb - s.y;
@@ -1144,7 +1162,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
           },
           [](int) {}, RunTab{s_tab, s_run});
     }
-    if (pf_wave && has_next) s_next[lane] = sph_next;   // (arrived long ago: the wave's own scan slice lies in between)
+    if (pf_wave && has_next) hdr.s_next[lane] = sph_next;   // (arrived long ago: the wave's own scan slice lies in between)
     SHR_TL(0, 3);   // this wave's scan slice is done
     __syncthreads();
     SHR_TL(0, 4);   // past the second barrier: the stream-out starts
@@ -1172,10 +1190,10 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
             if (may_tie && (is_background_tie(k01.x) || is_background_tie(k01.y) || is_background_tie(k23.x) ||
                             is_background_tie(k23.y))) {   // (practically never)
               const float yg = axis_coord_t<POW2>(ay, v + r0);
-              if (is_background_tie(k01.x)) a.x = (uint8_t)tie_owner(s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg);
-              if (is_background_tie(k01.y)) a.y = (uint8_t)tie_owner(s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg);
-              if (is_background_tie(k23.x)) a.z = (uint8_t)tie_owner(s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg);
-              if (is_background_tie(k23.y)) a.w = (uint8_t)tie_owner(s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg);
+              if (is_background_tie(k01.x)) a.x = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg);
+              if (is_background_tie(k01.y)) a.y = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg);
+              if (is_background_tie(k23.x)) a.z = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg);
+              if (is_background_tie(k23.y)) a.w = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg);
             }
           } else {
             const uint4 k = *reinterpret_cast<const uint4 *>(cell);
@@ -1194,7 +1212,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
           out[(size_t)(r0 + v) * W + u] = key_depth((uint32_t)((unsigned long long)k >> 32));
           aout[(size_t)(r0 + v) * W + u] =
               (may_tie && is_background_tie((unsigned long long)k))
-                  ? (uint8_t)tie_owner(s_sph, (uint32_t)k, axis_coord_t<POW2>(ax, u), axis_coord_t<POW2>(ay, v + r0))
+                  ? (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k, axis_coord_t<POW2>(ax, u), axis_coord_t<POW2>(ay, v + r0))
                   : (uint8_t)k;
         } else {
           out[(size_t)(r0 + v) * W + u] = key_depth((uint32_t)k);
@@ -1207,7 +1225,7 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     const int t0 = (tile_lo / kTileH) * tiles_x, t1 = ((tile_hi + kTileH - 1) / kTileH) * tiles_x;
     tile_forward<VEC4, OWNER>(sph, J, H, W, out, aout, tiles_x, t0 + wave, t1, nwaves, lane);
   }
-  if (general && pf_wave && has_next) s_next[lane] = sph_next;
+  if (general && pf_wave && has_next) hdr.s_next[lane] = sph_next;
   SHR_TL(0, 5);   // end: the touched rows are streamed out
   if (PERSIST && n + crop_step < N) __syncthreads();   // the z-buffer is re-initialised next: every wave's stream-out reads are done
   }  // crops
@@ -1239,24 +1257,15 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
   static_assert(NW == 8 || NW == 16, "waves per workgroup");
   constexpr int NT = 64 * NW, NW_SHIFT = NW == 16 ? 4 : 3;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *s_sph = reinterpret_cast<float4 *>(smem);
-  int4 *s_items = reinterpret_cast<int4 *>(smem + kOffItems);
-  int *s_ends = reinterpret_cast<int *>(smem + kOffEnds);
-  int *s_flag = reinterpret_cast<int *>(smem + kOffFlags);
-  float4 *s_next = reinterpret_cast<float4 *>(smem + kOffNext);
+  const LdsHeader hdr(smem);
   float4 *s_part = reinterpret_cast<float4 *>(smem + kHdrBytes);
   // PERSISTENT workgroups (gridDim.x < N: crops blockIdx.x, blockIdx.x + gridDim.x, ...): the youngest wave requests
   // the next crop's records after the staging barrier and parks them in LDS (see the forward).
   const int crop_step = gridDim.x;
   for (int n = blockIdx.x, crop_it = 0; PERSIST ? n < N : crop_it == 0; n += crop_step, ++crop_it) {
-  // Every crop starts from OPAQUE copies of the launch constants and of the thread index: otherwise the compiler
-  // hoists each crop-invariant value out of the crop loop and keeps it in a register (forward: 92 instead of 51
-  // VGPRs; the fused kernel spilled).
-  int J = J_, H = H_, W = W_, rows = rows_, w4_shift = w4_shift_, tid = threadIdx.x;
-  if (PERSIST) {
-    asm volatile("" : "+s"(J), "+s"(H), "+s"(W), "+s"(rows), "+s"(w4_shift));
-    asm volatile("" : "+v"(tid));
-  }
+  // (the plain shift, -1 or log2(W / 4), passes the low-byte decode unchanged; cc.flags / cc.nwaves mean nothing here; no z-buffer: 0)
+  const CropConsts cc = crop_consts<PERSIST>(J_, H_, W_, rows_, w4_shift_, 0);
+  const int J = cc.J, H = cc.H, W = cc.W, rows = cc.rows, w4_shift = cc.w4_shift, tid = cc.tid;
   const int lane = tid & 63, wave = tid >> 6;
   SHR_TL_ENTRY(1);
   const int LW = W + kRowPad;
@@ -1284,7 +1293,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     if (lead)
       asm volatile("global_load_dwordx4 v[110:113], %0, off" : : "v"(rec + min(lane, J - 1)) : "v110", "v111", "v112", "v113", "memory");
   } else if (lead) {
-    if (lane < J) sph = s_next[lane];
+    if (lane < J) sph = hdr.s_next[lane];
     have_sph = true;
   }
   for (int i = tid; i < kZWaves * SHR_MAX_SPHERES; i += NT) s_part[i] = make_float4(0.f, 0.f, 0.f, 0.f);  // [wave][sphere]
@@ -1333,8 +1342,8 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     touched_rows(sph, lane < J, ay, ky, 0, H, lead_v0, lead_v1);
     SHR_TL(1, 6);   // (lead waves) the records have arrived, the touched rows are known
     if (wave_s == 0) {
-      s_sph[lane] = sph;
-      if (!WHOLE && lane == 0) { s_flag[kFlagOutLo] = lead_v0; s_flag[kFlagOutHi] = lead_v1; }
+      hdr.s_sph[lane] = sph;
+      if (!WHOLE && lane == 0) { hdr.s_flag[kFlagOutLo] = lead_v0; hdr.s_flag[kFlagOutHi] = lead_v1; }
     }
   }
   // WHOLE (the buffers hold the whole crop: one workgroup per CU): rows sit at their own index, one pass over
@@ -1344,8 +1353,8 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
   int cv0 = 0, cv1 = H - 1;
   if (!WHOLE) {
     __syncthreads();
-    cv0 = rfl(s_flag[kFlagOutLo]);
-    cv1 = rfl(s_flag[kFlagOutHi]);
+    cv0 = rfl(hdr.s_flag[kFlagOutLo]);
+    cv1 = rfl(hdr.s_flag[kFlagOutHi]);
   }
 
   // Passes over the touched rows (one, unless they exceed the staging buffers).  The first pass's list and
@@ -1354,8 +1363,8 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
   auto build_list = [&](int r0, int r1) {
     if (wave_s == 0) {
       bool too_big;   // excluded by the launcher (W <= kMaxFastWidth)
-      const int total = build_work_list<kSphereCostBwd | (SEG2 ? kSeg2Tag : 0)>(sph, lane < J, ax, ay, kx, ky, W, r0, r1, s_items, s_ends, lane, &too_big);
-      if (lane == 0) s_flag[kFlagTotal] = total;
+      const int total = build_work_list<kSphereCostBwd | (SEG2 ? kSeg2Tag : 0)>(sph, lane < J, ax, ay, kx, ky, W, r0, r1, hdr.s_items, hdr.s_ends, lane, &too_big);
+      if (lane == 0) hdr.s_flag[kFlagTotal] = total;
       SHR_TL(1, 7);   // (wave 0) the work list stands
     }
   };
@@ -1484,9 +1493,9 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     // transposed wave sum into the wave's private LDS slot.
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const int cell_max = rh * LW - 1;
-    const WaveList wl = load_wave_list(s_sph, s_items, s_ends, lane);
+    const WaveList wl = load_wave_list(hdr.s_sph, hdr.s_items, hdr.s_ends, lane);
     walk_my_slice<POW2, kSphereCostBwd | (SEG2 ? kSeg2Tag : 0), false>(
-        wl, J, s_flag[kFlagTotal], wave, NW, shares, lane, ax, ay, r0, r1, LW,
+        wl, J, hdr.s_flag[kFlagTotal], wave, NW, shares, lane, ax, ay, r0, r1, LW,
         [&](int j, const float4 s, int cell_a, int cell_b, float dx, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto) {
           // lanes without a pixel may point past the pass: clamped, and never counted.  Most chunks own nothing: only
@@ -1526,7 +1535,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     float4 t;
     asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, v106\n\tv_mov_b32 %1, v107\n\tv_mov_b32 %2, v108\n\tv_mov_b32 %3, v109"
                  : "=v"(t.x), "=v"(t.y), "=v"(t.z), "=v"(t.w) : : "memory");
-    s_next[lane] = t;
+    hdr.s_next[lane] = t;
   }
   SHR_TL(1, 3);   // this wave's walk is done
   __syncthreads();
@@ -1538,7 +1547,7 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
       const float4 a = s_part[w * SHR_MAX_SPHERES + tid];
       t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
     }
-    t.w = t.w * s_sph[tid].w;
+    t.w = t.w * hdr.s_sph[tid].w;
     const v4u_t tt = {__float_as_uint(t.x), __float_as_uint(t.y), __float_as_uint(t.z), __float_as_uint(t.w)};
     asm_store16<SHR_BWD_STORE_MODE>(grad_spheres + (size_t)n * J + tid, tt);
   }
@@ -1577,11 +1586,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
                      const int *__restrict__ crop_index) {
   using Key = unsigned long long;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4 *s_sph = reinterpret_cast<float4 *>(smem);
-  int4 *s_items = reinterpret_cast<int4 *>(smem + kOffItems);
-  int *s_ends = reinterpret_cast<int *>(smem + kOffEnds);
-  int *s_flag = reinterpret_cast<int *>(smem + kOffFlags);
-  float4 *s_next = reinterpret_cast<float4 *>(smem + kOffNext);
+  const LdsHeader hdr(smem);
   float4 *s_part = reinterpret_cast<float4 *>(smem + kHdrBytes);                          // [wave][J]
   Key *zbuf = reinterpret_cast<Key *>(smem + kHdrBytes + (size_t)kZWaves * J_ * sizeof(float4));
 
@@ -1599,18 +1604,11 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   // hands workgroups to the CUs in turn, not to the first free one).  The mask makes this a permutation of the regions only
   // for a power-of-two count: the launcher gives this variant no other multiple of four (sphere_raster.hip).
   if (BOX && !PERSIST && (nregions & 3) == 0) region = (region + (nregions >> 2)) & (nregions - 1);
-  // Every crop starts from OPAQUE copies of the launch constants and of the thread index: otherwise the compiler
-  // hoists each crop-invariant value out of the crop loop and keeps it in a register (forward: 92 instead of 51
-  // VGPRs; the fused kernel spilled).
-  // (w4_shift_: log2(W / 4) or -1 in the low byte (signed); bit 8: the partial results go to the CROP's slots, not the
-  // workgroup's -- shr_sphere_raster_mse_ordered, where crop_index is a permutation that only changes the launch order)
-  int J = J_, H = H_, W = W_, rows_per_region = rows_per_region_, w4_shift = (int)(signed char)(w4_shift_ & 0xff), tid = threadIdx.x;
-  const bool slot_by_crop = (w4_shift_ & 0x100) != 0;
-  int zcells = zcells_;
-  if (PERSIST) {
-    asm volatile("" : "+s"(J), "+s"(H), "+s"(W), "+s"(rows_per_region), "+s"(w4_shift), "+s"(zcells));
-    asm volatile("" : "+v"(tid));
-  }
+  // (flag bit 0 of w4_shift_: the partial results go to the CROP's slots, not the workgroup's --
+  // shr_sphere_raster_mse_ordered, where crop_index is a permutation that only changes the launch order)
+  const CropConsts cc = crop_consts<PERSIST>(J_, H_, W_, rows_per_region_, w4_shift_, zcells_);
+  const int J = cc.J, H = cc.H, W = cc.W, rows_per_region = cc.rows, w4_shift = cc.w4_shift, zcells = cc.zcells, tid = cc.tid;
+  const bool slot_by_crop = (cc.flags & 1) != 0;
   const int lane = tid & 63, wave = tid >> 6;
   // (BOX: the prologue and the convert pass -- the phases that wait for memory and issue the stores -- outrank the co-resident
   // workgroup's scan / walk, see the forward: 1152 crops @128 x 128 43.3 -> 42.5 us, 9216 crops 302 -> 293, @256 x 256 160.1 -> 159.5)
@@ -1635,7 +1633,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   const int c = crop_index ? crop_index[n] : n;
   float4 sph = make_float4(0.f, 0.f, 0.f, 0.f);
   if (valid && (wave_s == 0 || bg_wave))   // the others: wave 0's LDS copy, later
-    sph = crop_it == 0 ? spheres[(size_t)c * J + lane] : s_next[lane];
+    sph = crop_it == 0 ? spheres[(size_t)c * J + lane] : hdr.s_next[lane];
   // (behind the records' request: the index is a scalar load, the output pointers are not among the preloaded arguments)
   const float *tgt = target + (size_t)(target_index ? target_index[c] : c) * H * W + (size_t)r0 * W;
   float *out = depth ? depth + (size_t)c * H * W + (size_t)r0 * W : nullptr;
@@ -1673,7 +1671,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     ua = rfl(ua);
     ub = rfl(ub);
     if (wave_s == 1 && lane == 0) {
-      s_flag[kFlagOutLo] = ua; s_flag[kFlagOutHi] = ub;
+      hdr.s_flag[kFlagOutLo] = ua; hdr.s_flag[kFlagOutHi] = ub;
       if (BOX) {   // everything the other waves derive from the box (see the forward)
         cu0 &= ~3;
         const int bw = cu1 >= cu0 ? ((cu1 | 3) - cu0 + 1) : 4;
@@ -1689,12 +1687,12 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
         }
         const int split = (cv0 + zcells / pitch) & ~(kTileH - 1);        // rows [cv0, split) fit the z-buffer
         const bool over = split <= cv1;
-        s_flag[kFlagBoxRow0] = cv0; s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; s_flag[kFlagBoxCol0] = cu0; s_flag[kFlagBoxWidth] = bw;
-        s_flag[kFlagPitch] = pitch;
-        s_flag[kFlagClip] = over ? split : r1;                                   // the walks' clip row
+        hdr.s_flag[kFlagBoxRow0] = cv0; hdr.s_flag[kFlagBoxRowEnd] = over ? split : cv1 + 1; hdr.s_flag[kFlagBoxCol0] = cu0; hdr.s_flag[kFlagBoxWidth] = bw;
+        hdr.s_flag[kFlagPitch] = pitch;
+        hdr.s_flag[kFlagClip] = over ? split : r1;                                   // the walks' clip row
         // tile rows: from the split to the end of the touched units (whole units: W >= 32 is a power of two)
-        s_flag[kFlagTileLo] = over ? split : r1;
-        s_flag[kFlagTileHi] = over ? min(r1, (r0 + ((ub << 6) + w4 - 1) / w4 + kTileH - 1) & ~(kTileH - 1)) : r1;
+        hdr.s_flag[kFlagTileLo] = over ? split : r1;
+        hdr.s_flag[kFlagTileHi] = over ? min(r1, (r0 + ((ub << 6) + w4 - 1) / w4 + kTileH - 1) & ~(kTileH - 1)) : r1;
       }
     }
     // The background rows' depth is NOT stored here, as the forward does it, but by the convert pass below, unit by unit:
@@ -1704,39 +1702,39 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     // (docs/EXPERIMENTS.md S5).
   }
   if (wave_s == 0) {
-    s_sph[lane] = sph;
+    hdr.s_sph[lane] = sph;
     const unsigned long long bad = __ballot(valid && !(sphere_is_tame(sph) && fabsf(sph.z) < 1e30f));
     const unsigned long long low = __ballot(valid && sph.z <= kBackground);
     const unsigned long long behind = __ballot(valid && sph.z > kBackground);
     bool too_big;
-    const int total = build_work_list<kSphereCostMse | (SEG2 ? kSeg2Tag : 0)>(sph, valid, ax, ay, kx, ky, W, r0, r1, s_items, s_ends, lane, &too_big);
+    const int total = build_work_list<kSphereCostMse | (SEG2 ? kSeg2Tag : 0)>(sph, valid, ax, ay, kx, ky, W, r0, r1, hdr.s_items, hdr.s_ends, lane, &too_big);
     if (lane == 0) {
-      s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
-      s_flag[kFlagTotal] = total;
-      s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
+      hdr.s_flag[kFlagGeneral] = (bad != 0ull) || (low == 0ull) || too_big;
+      hdr.s_flag[kFlagTotal] = total;
+      hdr.s_flag[kFlagMayTie] = behind != 0ull;   // only a sphere centred behind the background can hit at exactly 100.0 (tie_owner)
     }
   }
   SHR_TL(2, 1);   // this wave's work in front of the first barrier is done
   __syncthreads();
   if (BOX) __builtin_amdgcn_s_setprio(0);
   SHR_TL(2, 2);   // past the first barrier
-  if (!(wave_s == 0 || bg_wave)) sph = s_sph[lane];
+  if (!(wave_s == 0 || bg_wave)) sph = hdr.s_sph[lane];
   float4 sph_next = make_float4(0.f, 0.f, 0.f, 0.f);
   if (pf_wave && has_next && valid)
     sph_next = spheres[(size_t)(crop_index ? crop_index[n + crop_step] : n + crop_step) * J + lane];
-  const bool general = s_flag[kFlagGeneral] != 0;
-  const bool may_tie = rfl(s_flag[kFlagMayTie]) != 0;
-  ua = rfl(s_flag[kFlagOutLo]);
-  ub = rfl(s_flag[kFlagOutHi]);
+  const bool general = hdr.s_flag[kFlagGeneral] != 0;
+  const bool may_tie = rfl(hdr.s_flag[kFlagMayTie]) != 0;
+  ua = rfl(hdr.s_flag[kFlagOutLo]);
+  ub = rfl(hdr.s_flag[kFlagOutHi]);
   // the z-buffer's rows [p0, pe) and columns [cu0, cu0 + bw) at `pitch` (BOX = false: the whole region at the image's
   // own), the walks' clip row, and the rows [tile_lo, tile_hi) that go through the tile code
-  const int p0 = BOX ? rfl(s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(s_flag[kFlagBoxRowEnd]) : r1;
-  const int cu0 = BOX ? rfl(s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(s_flag[kFlagBoxWidth]) : W;
-  const int pitch = BOX ? rfl(s_flag[kFlagPitch]) : LW, clip = BOX ? rfl(s_flag[kFlagClip]) : r1;
+  const int p0 = BOX ? rfl(hdr.s_flag[kFlagBoxRow0]) : r0, pe = BOX ? rfl(hdr.s_flag[kFlagBoxRowEnd]) : r1;
+  const int cu0 = BOX ? rfl(hdr.s_flag[kFlagBoxCol0]) : 0, bw = BOX ? rfl(hdr.s_flag[kFlagBoxWidth]) : W;
+  const int pitch = BOX ? rfl(hdr.s_flag[kFlagPitch]) : LW, clip = BOX ? rfl(hdr.s_flag[kFlagClip]) : r1;
   // (both words read whatever `general` says: as conditional reads they gave the compiler a branch structure with a dead edge
   // from here to the closing reductions, along which it believed the observed image's pieces still in flight -- and made every
   // wave wait for its depth stores there)
-  int flag_lo = BOX ? rfl(s_flag[kFlagTileLo]) : r1, flag_hi = BOX ? rfl(s_flag[kFlagTileHi]) : r1;
+  int flag_lo = BOX ? rfl(hdr.s_flag[kFlagTileLo]) : r1, flag_hi = BOX ? rfl(hdr.s_flag[kFlagTileHi]) : r1;
   if (BOX) asm volatile("" : "+s"(flag_lo), "+s"(flag_hi));
   const int tile_lo = general ? r0 : flag_lo, tile_hi = general ? r1 : flag_hi;
   Key *zb = zbuf - (p0 * pitch + cu0);   // cell of pixel (v, u) = zb[v * pitch + u]
@@ -1746,10 +1744,10 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     // ---- scan-convert (forward) ------------------------------------------------------------
     WaveList wl;
     wl.sph = sph;
-    wl.item = s_items[lane];
-    wl.end = s_ends[lane];
+    wl.item = hdr.s_items[lane];
+    wl.end = hdr.s_ends[lane];
     walk_my_slice<POW2, kSphereCostMse | (SEG2 ? kSeg2Tag : 0), true>(
-        wl, J, s_flag[kFlagTotal], wave, kZWaves, shares_fwd, lane, ax, ay, 0, clip, pitch,
+        wl, J, hdr.s_flag[kFlagTotal], wave, kZWaves, shares_fwd, lane, ax, ay, 0, clip, pitch,
         [&](int j, const float4 s, int cell_a, int cell_b, float, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto row_test) {
           const float dya = yga - s.y, dyb = ygb - s.y;
@@ -1768,7 +1766,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
           }
         },
         [](int) {});
-    if (pf_wave && has_next) s_next[lane] = sph_next;
+    if (pf_wave && has_next) hdr.s_next[lane] = sph_next;
     SHR_TL(2, 3);   // this wave's scan slice is done
     // (a region no sphere touches -- the top and the bottom quarter of a 256 x 256 hand crop cut into four 64-row
     // regions: the list is empty, every unit of the convert pass is a background unit that never looks at the
@@ -1809,10 +1807,10 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
       if (may_tie && (is_background_tie(k01.x) || is_background_tie(k01.y) || is_background_tie(k23.x) ||
                       is_background_tie(k23.y))) {   // a hit at exactly 100.0 (practically never): who owns it (tie_owner)
         const float yg = axis_coord_t<POW2>(ay, v + r0);
-        if (is_background_tie(k01.x)) k01.x = (k01.x & ~0xffull) | tie_owner(s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg);
-        if (is_background_tie(k01.y)) k01.y = (k01.y & ~0xffull) | tie_owner(s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg);
-        if (is_background_tie(k23.x)) k23.x = (k23.x & ~0xffull) | tie_owner(s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg);
-        if (is_background_tie(k23.y)) k23.y = (k23.y & ~0xffull) | tie_owner(s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg);
+        if (is_background_tie(k01.x)) k01.x = (k01.x & ~0xffull) | tie_owner(hdr.s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg);
+        if (is_background_tie(k01.y)) k01.y = (k01.y & ~0xffull) | tie_owner(hdr.s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg);
+        if (is_background_tie(k23.x)) k23.x = (k23.x & ~0xffull) | tie_owner(hdr.s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg);
+        if (is_background_tie(k23.y)) k23.y = (k23.y & ~0xffull) | tie_owner(hdr.s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg);
       }
       const float e0 = d.x - t.x, e1 = d.y - t.y, e2 = d.z - t.z, e3 = d.w - t.w;
       sse += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
@@ -1849,7 +1847,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     const int cell_max = (p0 * pitch + cu0) + (pe - p0) * pitch - 1;   // the z-buffer's last cell, as the walk counts cells
     walk_my_slice<POW2, kSphereCostMse | (SEG2 ? kSeg2Tag : 0), true>(
-        wl, J, s_flag[kFlagTotal], wave, kZWaves, shares_bwd, lane, ax, ay, 0, clip, pitch,
+        wl, J, hdr.s_flag[kFlagTotal], wave, kZWaves, shares_bwd, lane, ax, ay, 0, clip, pitch,
         [&](int j, const float4 s, int cell_a, int cell_b, float dx, float ca, float yga, float ygb, bool ok_a,
             bool ok_b, bool has_b, auto) {
           auto take = [&](int cell, float yg, bool ok) {
@@ -1911,7 +1909,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
         const float w = in ? gk[k] / bsq[k] : 0.f;
         pz[k] = in ? gk[k] : 0.f;
         pw[k] = -w;
-        const float4 o = s_sph[in ? owner[k] : 0];
+        const float4 o = hdr.s_sph[in ? owner[k] : 0];
         px[k] = -(w * (g.xg[k] - o.x));
         py[k] = -(w * (g.yg - o.y));
       }
@@ -1939,7 +1937,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
     }
   }
 
-  if (general && pf_wave && has_next) s_next[lane] = sph_next;
+  if (general && pf_wave && has_next) hdr.s_next[lane] = sph_next;
   // ---- reductions: waves in order --------------------------------------------------------------
   sse = wave_sum_lane63(sse);
   SHR_TL(2, 7);   // this wave's walk (and tile code) is done
@@ -1947,7 +1945,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
   // of their own, so ONE barrier closes the walk and publishes them; over the work list otherwise, behind a barrier of its own
   // (round 6: -0.3 to -1.2 % on the fused kernel; the header keeps its size, so no z-buffer moves -- SHR_HDR_PAD 16 .. 192
   // measured on the way: where the z-buffers start relative to the LDS banks changes nothing, +-0.3 %)
-  float *s_wsum = PERSIST ? reinterpret_cast<float *>(s_items) : reinterpret_cast<float *>(s_next);
+  float *s_wsum = PERSIST ? reinterpret_cast<float *>(hdr.s_items) : reinterpret_cast<float *>(hdr.s_next);
   if (PERSIST) __syncthreads();
   if (lane == 63) s_wsum[wave] = sse;
   __syncthreads();
@@ -1963,7 +1961,7 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
       const float4 a = s_part[w * J + tid];
       t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
     }
-    t.w = t.w * s_sph[tid].w;
+    t.w = t.w * hdr.s_sph[tid].w;
     grad_out[slot * J + tid] = t;
   }
   if (has_next) __syncthreads();   // records, work list, partials and z-buffer are rewritten next

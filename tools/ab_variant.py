@@ -3,8 +3,13 @@
     python tools/ab_variant.py build:NAME -DSHR_... ...    (several variants side by side: tools/libspherehand_exp_NAME.so)
 (another commit's library copied to tools/libspherehand_exp_NAME.so is a variant like any other)
     python tools/ab_variant.py                          (GPU box: alternating timings at 256 / 1152 / 9216 crops, same-bits check,
-                                                         the product library against every variant library found)"""
-import ctypes, glob, os, subprocess, sys
+                                                         the product library against every variant library found)
+Environment: S (image size), NS (crop counts), MSE=1 (the fused render-and-compare kernel as well: its SSE partials, gradient
+partials and depth output are compared with the product's, byte for byte), C5=1 (config 5's wide boxes), NODEPTH=1, REPS_X (a
+factor on the launches per timing).  Every round prints a line per library; the medians of the three rounds and their ratio
+to the PRODUCT's follow at the end (a variant's percentage is variant / product - 1: with the parent's library as the
+variant, a positive figure means the tree is FASTER than the parent -- the opposite sign of tables that compare against the parent).  The exit status is 1 if any line said `same bits: False`."""
+import ctypes, glob, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 EXP = os.path.join(ROOT, "tools", "libspherehand_exp.so")
@@ -50,6 +55,7 @@ def main():
     hbr = HandBallPrimitiveRender(mesh["bones"], S, S).to(dev)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
+        times, all_same = {}, True
         for n in [int(v) for v in os.environ.get("NS", "256,1152,9216").split(",")]:
             with torch.no_grad():
                 sph = hbr.spheres(fk(sample_poses(n, seed=7).to(dev))).contiguous()
@@ -68,8 +74,8 @@ def main():
             depth = torch.empty(n, S, S, device=dev); owner = torch.empty(n, S, S, device=dev, dtype=torch.uint8)
             grad = torch.randn(n, S, S, device=dev); gs = torch.empty(n, J, 4, device=dev)
             p = [t.data_ptr() for t in (sph, depth, owner, grad, gs)]
-            reps = 200 if n == 256 else (40 if n == 1152 else 8)
-            ref = {}
+            reps = (200 if n == 256 else (40 if n == 1152 else 8)) * int(os.environ.get("REPS_X", 1))
+            ref, tgt = {}, obs
             for rnd in range(3):
                 for name, l in libs.items():
                     f = lambda s: l.shr_sphere_raster_fwd_ex(p[0], n, J, S, S, p[1], p[2], 1, s)
@@ -81,17 +87,35 @@ def main():
                     t0 = bench.mean_launch_us(f0, stream, reps, 3, 3, warm_ms=30.0)
                     f(stream.cuda_stream); b(stream.cuda_stream); stream.synchronize()
                     key = (depth.clone(), gs.clone())
-                    same = "" if name == "product" else "  same bits: %s" % (torch.equal(key[0], ref["d"]) and torch.equal(key[1], ref["g"]))
-                    if name == "product": ref = {"d": key[0], "g": key[1]}
+                    ok = name == "product" or (torch.equal(key[0], ref["d"]) and torch.equal(key[1], ref["g"]))
+                    same = "" if name == "product" else "  same bits: %s" % ok
+                    if name == "product": ref.update(d=key[0], g=key[1])
+                    rows = [("fwd+owner", tf), ("bwd", tb), ("fwd depth-only", t0)]
                     if os.environ.get("MSE"):   # the fused render-and-compare kernel on the same crops (target: the depth map + noise)
                         R = l.shr_sphere_raster_mse_regions(S, S)
-                        tgt = obs if obs is not None else (ref.get("d", depth) + 3.0 * torch.randn_like(depth)).contiguous()
-                        sse = torch.empty(n * R, device=dev); gsp = torch.empty(n * R * J * 4, device=dev)
+                        if tgt is None:         # (one target for every library and round: the product's first depth map + noise)
+                            tgt = (ref["d"] + 3.0 * torch.randn_like(depth)).contiguous()
+                        sse = torch.zeros(n * R, device=dev); gsp = torch.zeros(n * R * J * 4, device=dev)
                         m = lambda s: l.shr_sphere_raster_mse(p[0], n, J, S, S, tgt.data_ptr(), None if index is None else index.data_ptr(),
                                                               None if os.environ.get("NODEPTH") else p[1], sse.data_ptr(), gsp.data_ptr(), s)
+                        depth.zero_()
                         assert m(stream.cuda_stream) == 0
-                        print("n %5d %-10s render-and-compare %7.2f us" % (n, name, bench.mean_launch_us(m, stream, reps, 3, 3, warm_ms=30.0)), flush=True)
+                        stream.synchronize()
+                        mkey = (sse.clone(), gsp.clone(), depth.clone())   # raw tensors: SSE partials, gradient partials, depth output
+                        mok = name == "product" or all(torch.equal(a, b) for a, b in zip(mkey, ref["m"]))
+                        if name == "product" and "m" not in ref: ref["m"] = mkey
+                        tm = bench.mean_launch_us(m, stream, reps, 3, 3, warm_ms=30.0)
+                        rows.append(("render-and-compare", tm))
+                        print("n %5d %-10s render-and-compare %7.2f us%s" % (n, name, tm, "" if name == "product" else "  same bits: %s" % mok), flush=True)
+                        ok = ok and mok
+                    all_same = all_same and ok
+                    for row, t in rows: times.setdefault((n, row), {}).setdefault(name, []).append(t)
                     print("n %5d %-10s fwd+owner %7.2f  bwd %7.2f  fwd depth-only %7.2f us%s" % (n, name, tf, tb, t0, same), flush=True)
+        for (n, row), by in times.items():   # medians of the rounds, and each library's against the product's
+            med = {name: statistics.median(v) for name, v in by.items()}
+            print("median n %5d %-18s " % (n, row) + "  ".join("%s %.2f (%+.2f %%)" % (k, v, 100.0 * (v / med["product"] - 1.0)) for k, v in med.items()), flush=True)
+    if not all_same:
+        sys.exit(1)
 
 
 if __name__ == "__main__":
