@@ -611,6 +611,60 @@ int shr_tri_interp_bwd(const int32_t *owner, const float *vertices, const int32_
                        long long attr_batch_stride, int B, int NV, int F, int W, int H, int C, const float *grad_out,
                        float *grad_attr, float *grad_vertices, void *workspace, void *stream);
 
+/* Vertex normals of an indexed mesh and unit normalisation of three-plane maps (a capability the reference does not
+ * have; with shr_tri_interp_fwd they give a normal map).  Per crop b:
+ *   points[B,NV,4]   fp32 (x, y, z, -), 16-byte aligned: the raster's vertex layout (shr_lbs_project's output as it is);
+ *                    the fourth component is ignored and gets zero gradient
+ *   faces[F,3]       as the raster takes them (after the right hand's winding swap)
+ *   the tables       built once on the host (ops.tri_vertex_tables), all int32; a CORNER is the integer 3 f + k, corner k
+ *                    of face f; faces with a vertex id outside [0, NV) appear in no table
+ *     point[NV]                        vertex -> welded point id in [0, NP)
+ *     inc_start[NP+1], inc[NI]         welded incidence (CSR by point): the corners whose vertex welds to the point, ascending
+ *     copy_start[NP+1], copy[NV]       the copies of each point (CSR by point): the vertices that weld to it, ascending
+ *     own_start[NV+1], own[NO]         own-id incidence (CSR by vertex): the corners with faces[f,k] == v, ascending
+ *   Without welding NP = NV, point and copy are the identity and inc == own.  Entries out of range are skipped.
+ * In fp32 with one rounding per written operator (no contraction):
+ *   1. face normal, area-weighted, corners p0, p1, p2 in the order of faces[f]:  e1 = p1 - p0, e2 = p2 - p0,
+ *      n_f = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,  e1x e2y - e1y e2x).
+ *   2. N_v = sum of n_f over the corners of inc for v's point, in ascending corner order (a face with two corners on the
+ *      point counts twice): one add per term, starting FROM the first term; no corner: N = 0.  The sum is evaluated once
+ *      per point and stored to its copies: copies of a point get identical bits.
+ *   3. unit3:  s = (Nx Nx + Ny Ny) + Nz Nz;  s > 0 and finite:  n = N / sqrt(s), the IEEE square root and three IEEE
+ *      divisions;  otherwise n = (0, 0, 0) and nothing flows back through it (the ZERO RULE).  NaN and infinite inputs
+ *      give 0 (n) or NaN / inf (N), never a fault.
+ *   shr_tri_vertex_normals_fwd   -> normals[B,NV,4] = (n, 0) and, when raw is not NULL, raw[B,NV,4] = (N, 0); both
+ *       16-byte aligned.  No flip: the normals are those of the faces' own winding.  The raster's cull (.cu:33) draws a
+ *       face when (y2 - y0)(x1 - x0) >= (y1 - y0)(x2 - x0), which is n_f.z >= 0: drawn faces point AWAY from the camera
+ *       in this convention (smaller depth is nearer).  render.MeshNormalRaster turns them by building its tables from
+ *       the faces with corners 1 and 2 exchanged, which negates every n_f exactly (a b - c d = -(c d - a b) in IEEE).
+ *   shr_tri_vertex_normals_bwd   grad_normals[B,NV,4] (the fourth component is not read) -> grad_points[B,NV,4] =
+ *       (d/dx, d/dy, d/dz, 0): the exact derivative of 1 .. 3 with the zero rule's fp32 decision held fixed, evaluated in
+ *       fp64 from the fp32 points by two gathers in fixed order, no atomics:
+ *         per welded point p:  g = sum of grad_normals over copy (ascending);  N, n = N / |N| in fp64 (N summed as in 2.);
+ *             G_p = (g - n (n . g)) / |N|   (0 under the zero rule, or when the fp64 |N|^2 is 0 or not finite)
+ *         per vertex v:  over own (ascending), with H_f = (G_point(c0) + G_point(c1)) + G_point(c2):
+ *             corner 1: e2 x H_f;  corner 2: H_f x e1;  corner 0: -(both);  one rounding to fp32 at the end.
+ *       The gradients land on faces[f,k], the positions that were read.  Bitwise reproducible, independent of B and of
+ *       the launch shape, no host synchronisation.  workspace: 16-byte aligned,
+ *       shr_tri_vertex_normals_bwd_workspace_bytes(B, NP) bytes (-1 on a negative size), fully written by the call.
+ *   shr_unit3_maps_fwd   maps[B,3,H,W] -> out[B,3,H,W]: step 3 on every pixel's three planes (the same device function;
+ *       a background pixel, all planes 0, stays 0).  One read and one write of the planes.  out must not overlap maps
+ *       (SHR_EINVAL).
+ *   shr_unit3_maps_bwd   grad_out[B,3,H,W] -> grad_maps[B,3,H,W] = (g - o (o . g)) / |m|, o = m / |m| in fp64 from the
+ *       fp32 m, one rounding; 0 under the zero rule.  grad_maps must not overlap maps (it may be grad_out).
+ *   B, W, H <= 65535 (SHR_ETOOLARGE beyond); B == 0 is a no-op; NULLs and misaligned points / normals / raw / gradients /
+ *   workspace: SHR_EINVAL. */
+int shr_tri_vertex_normals_fwd(const float *points, const int32_t *faces, const int32_t *point, const int32_t *inc_start,
+                               const int32_t *inc, const int32_t *copy_start, const int32_t *copy, int B, int NV, int F,
+                               int NP, int NI, float *normals, float *raw, void *stream);
+long long shr_tri_vertex_normals_bwd_workspace_bytes(int B, int NP);
+int shr_tri_vertex_normals_bwd(const float *points, const int32_t *faces, const int32_t *point, const int32_t *inc_start,
+                               const int32_t *inc, const int32_t *copy_start, const int32_t *copy, const int32_t *own_start,
+                               const int32_t *own, int B, int NV, int F, int NP, int NI, int NO, const float *grad_normals,
+                               float *grad_points, void *workspace, void *stream);
+int shr_unit3_maps_fwd(const float *maps, int B, int W, int H, float *out, void *stream);
+int shr_unit3_maps_bwd(const float *maps, const float *grad_out, int B, int W, int H, float *grad_maps, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -95,7 +95,13 @@ SIGNATURES = {
     "shr_tri_interp_fwd": ([_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "shr_tri_interp_bwd_workspace_bytes": ([_i, _i, _i, _i, _i], ctypes.c_longlong),
     "shr_tri_interp_bwd": ([_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
-    "shr_fk_fwd": ([_vp, _i, _vp, _vp, _vp, _vp], _i),
+    "shr_tri_vertex_normals_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "shr_tri_vertex_normals_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_tri_vertex_normals_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                                    _vp], _i),
+    "shr_unit3_maps_fwd": ([_vp, _i, _i, _i, _vp, _vp], _i),
+    "shr_unit3_maps_bwd": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "shr_fk_fwd":([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "shr_pose_spheres_bwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -1317,6 +1317,202 @@ class TriAntialiasMaps(torch.autograd.Function):
         return _aa_backward(ctx, tri_antialias_maps_bwd, grad_out)
 
 
+class TriVertexTables:
+    """The incidence tables of the vertex normals (include/spherehand_hip.h, shr_tri_vertex_normals_fwd), all int32; a
+    corner is the integer 3 f + k.  NV, F: what they were built for.
+        point[NV]                    vertex -> welded point id in [0, NP)
+        inc_start[NP+1], inc[NI]     welded incidence: the corners whose vertex welds to the point, ascending
+        copy_start[NP+1], copy[NV]   the vertices that weld to the point, ascending
+        own_start[NV+1], own[NO]     own-id incidence: the corners with faces[f,k] == v, ascending
+    tri_vertex_tables returns them as numpy arrays; .to(device) gives the torch tensors the entry points take."""
+    FIELDS = ("point", "inc_start", "inc", "copy_start", "copy", "own_start", "own")
+
+    def __init__(self, NV, F, **arrays):
+        self.NV, self.F = int(NV), int(F)
+        for name in self.FIELDS:
+            setattr(self, name, arrays[name])
+
+    @property
+    def NP(self):
+        return len(self.inc_start) - 1
+
+    def arrays(self):
+        return tuple(getattr(self, name) for name in self.FIELDS)
+
+    def to(self, device):
+        return TriVertexTables(self.NV, self.F, **{
+            name: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.int32))).to(device)
+            for name, a in zip(self.FIELDS, self.arrays())})
+
+
+def _csr(keys, n, items):
+    """items grouped by key (stable: ascending items stay ascending within a key) -> (start [n+1], items) int32"""
+    order = np.argsort(keys, kind="stable")
+    start = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(keys, minlength=n), out=start[1:])
+    return start.astype(np.int32), np.asarray(items)[order].astype(np.int32)
+
+
+def tri_vertex_tables(faces, NV, weld=None):
+    """The vertex normals' tables (host, numpy, built once): faces [F,3] as the raster takes them (after the right hand's
+    winding swap), NV vertices -> TriVertexTables.  `weld` as tri_edge_table takes it: None (every vertex its own point),
+    an integer array [NV] (vertex -> point id; ids are renumbered densely), or a float array [NV,C] of positions
+    (vertices with bit-identical rows are one point).  Faces with a vertex id outside [0, NV) appear in no table.
+    Without welding the three tables coincide: inc == own and copy is the identity."""
+    f = np.asarray(faces.cpu().numpy() if isinstance(faces, torch.Tensor) else faces).astype(np.int64)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise RuntimeError("faces must be [F,3]")
+    NV = int(NV)
+    if NV <= 0:
+        raise RuntimeError("NV must be positive")
+    if weld is None:
+        point = np.arange(NV, dtype=np.int64)
+    else:
+        w = np.asarray(weld.cpu().numpy() if isinstance(weld, torch.Tensor) else weld)
+        if len(w) != NV:
+            raise RuntimeError("weld must have NV rows")
+        if w.dtype.kind == "f":
+            rows = np.ascontiguousarray(w.reshape(len(w), -1))
+            w = rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).ravel()
+        _, point = np.unique(np.asarray(w).ravel(), return_inverse=True)
+        point = np.asarray(point, np.int64).ravel()
+    NP = int(point.max()) + 1
+    valid = np.all((f >= 0) & (f < NV), axis=1)
+    corners = np.nonzero(np.repeat(valid, 3))[0]
+    vid = f.ravel()[corners]
+    own_start, own = _csr(vid, NV, corners)
+    inc_start, inc = _csr(point[vid], NP, corners)
+    copy_start, copy = _csr(point, NP, np.arange(NV))
+    return TriVertexTables(NV, len(f), point=point.astype(np.int32), inc_start=inc_start, inc=inc, copy_start=copy_start,
+                           copy=copy, own_start=own_start, own=own)
+
+
+def _normals_shape(points, faces, tables):
+    _check_input(points, "points")
+    _check_input(faces, "faces", torch.int32)
+    if points.dim() != 3 or points.shape[2] != 4 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("points must be [B,NV,4] and faces [F,3]")
+    B, NV, F = points.shape[0], points.shape[1], faces.shape[0]
+    if not isinstance(tables, TriVertexTables):
+        raise RuntimeError("tables must be a TriVertexTables (tri_vertex_tables(...).to(device))")
+    for name, t in zip(tables.FIELDS, tables.arrays()):
+        _check_input(t, "tables." + name, torch.int32)
+        if t.dim() != 1 or t.device != points.device:
+            raise RuntimeError("tables.%s must be one-dimensional, on the points' device" % name)
+    if faces.device != points.device:
+        raise RuntimeError("points, faces and tables must be on one device")
+    NP = tables.NP
+    if tables.NV != NV or tables.F != F or NP < 1 or tables.point.numel() != NV or tables.copy.numel() != NV or \
+            tables.copy_start.numel() != NP + 1 or tables.own_start.numel() != NV + 1:
+        raise RuntimeError("tables do not match faces [F,3] and the points' NV (built for NV = %d, F = %d)"
+                           % (tables.NV, tables.F))
+    return B, NV, F, NP, tables.inc.numel(), tables.own.numel()
+
+
+def tri_vertex_normals(points, faces, tables, want_raw=False):
+    """Area-weighted vertex normals (include/spherehand_hip.h, shr_tri_vertex_normals_fwd): points [B,NV,4] (x, y, z, -),
+    faces [F,3] int32, tables from tri_vertex_tables(...).to(device) -> unit normals [B,NV,4] = (n, 0); with want_raw
+    also the unnormalised sums [B,NV,4] = (N, 0).  The normals of the faces' own winding: never flipped."""
+    B, NV, F, NP, NI, _ = _normals_shape(points, faces, tables)
+    T = tables
+    with _on(points.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=points.device)
+        raw = torch.empty_like(out) if want_raw else None
+        _lib.check(_lib.lib().shr_tri_vertex_normals_fwd(_ptr(points), _ptr(faces), _ptr(T.point), _ptr(T.inc_start),
+                                                         _ptr(T.inc), _ptr(T.copy_start), _ptr(T.copy), B, NV, F, NP, NI,
+                                                         _ptr(out), _ptr(raw), _stream()), "shr_tri_vertex_normals_fwd")
+    return (out, raw) if want_raw else out
+
+
+def tri_vertex_normals_bwd(points, faces, tables, grad_normals):
+    """tri_vertex_normals's backward: grad_normals [B,NV,4] (the fourth component is not read) -> grad_points [B,NV,4] =
+    (d/dx, d/dy, d/dz, 0); fp64 gathers in a fixed order, bitwise reproducible."""
+    B, NV, F, NP, NI, NO = _normals_shape(points, faces, tables)
+    _check_input(grad_normals, "grad_normals")
+    if grad_normals.shape != points.shape or grad_normals.device != points.device:
+        raise RuntimeError("grad_normals must be [B,NV,4] as points, on their device")
+    T, lib = tables, _lib.lib()
+    with _on(points.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=points.device)
+        ws = torch.empty((max(16, lib.shr_tri_vertex_normals_bwd_workspace_bytes(B, NP)),), dtype=torch.uint8,
+                         device=points.device)
+        _lib.check(lib.shr_tri_vertex_normals_bwd(_ptr(points), _ptr(faces), _ptr(T.point), _ptr(T.inc_start), _ptr(T.inc),
+                                                  _ptr(T.copy_start), _ptr(T.copy), _ptr(T.own_start), _ptr(T.own), B, NV,
+                                                  F, NP, NI, NO, _ptr(grad_normals), _ptr(out), _ptr(ws), _stream()),
+                   "shr_tri_vertex_normals_bwd")
+    return out
+
+
+class TriVertexNormals(torch.autograd.Function):
+    """tri_vertex_normals with a backward: (points [B,NV,3 or 4], faces [F,3] int32, tables) -> unit normals [B,NV,4] =
+    (n, 0).  Differentiable w.r.t. points[..., :3], the zero rule held fixed; the gradient comes back in the width
+    given."""
+
+    @staticmethod
+    def forward(ctx, points, faces, tables):
+        p4, ctx.width4 = vertices4(points)
+        ctx.tables = tables
+        ctx.save_for_backward(p4, faces)
+        return tri_vertex_normals(p4, faces, tables)
+
+    @staticmethod
+    def backward(ctx, grad_normals):
+        p4, faces = ctx.saved_tensors
+        g = tri_vertex_normals_bwd(p4, faces, ctx.tables, grad_normals.contiguous().float())
+        return _grad_as_given(ctx, g), None, None
+
+
+def _unit3_shape(maps, name="maps"):
+    _check_input(maps, name)
+    if maps.dim() != 4 or maps.shape[1] != 3:
+        raise RuntimeError("%s must be [B,3,H,W]" % name)
+    return maps.shape[0], maps.shape[3], maps.shape[2]
+
+
+def unit3_maps(maps, out=None):
+    """Per-pixel unit normalisation of three planes (include/spherehand_hip.h, shr_unit3_maps_fwd): maps [B,3,H,W] ->
+    [B,3,H,W], each pixel's (m0, m1, m2) divided by its length; a pixel whose sum of squares is 0 or not finite gets 0.
+    `out`: where to write (not overlapping maps)."""
+    B, W, H = _unit3_shape(maps)
+    if out is not None:
+        _check_input(out, "out")
+        if out.shape != maps.shape or out.device != maps.device:
+            raise RuntimeError("out must be [B,3,H,W] as maps, on their device")
+    with _on(maps.device):
+        if out is None:
+            out = torch.empty_like(maps)
+        _lib.check(_lib.lib().shr_unit3_maps_fwd(_ptr(maps), B, W, H, _ptr(out), _stream()), "shr_unit3_maps_fwd")
+    return out
+
+
+def unit3_maps_bwd(maps, grad_out):
+    """unit3_maps's backward: grad_maps [B,3,H,W] = (g - o (o . g)) / |m| per pixel, 0 where the forward wrote 0."""
+    B, W, H = _unit3_shape(maps)
+    _check_input(grad_out, "grad_out")
+    if grad_out.shape != maps.shape or grad_out.device != maps.device:
+        raise RuntimeError("grad_out must be [B,3,H,W] as maps, on their device")
+    with _on(maps.device):
+        out = torch.empty_like(maps)
+        _lib.check(_lib.lib().shr_unit3_maps_bwd(_ptr(maps), _ptr(grad_out), B, W, H, _ptr(out), _stream()),
+                   "shr_unit3_maps_bwd")
+    return out
+
+
+class Unit3Maps(torch.autograd.Function):
+    """unit3_maps with a backward: maps [B,3,H,W] -> unit maps, differentiable w.r.t. maps."""
+
+    @staticmethod
+    def forward(ctx, maps):
+        maps = maps.contiguous()
+        ctx.save_for_backward(maps)
+        return unit3_maps(maps)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        maps, = ctx.saved_tensors
+        return unit3_maps_bwd(maps, grad_out.contiguous().float())
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

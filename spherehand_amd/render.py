@@ -10,6 +10,7 @@ signatures and return values), running on the hand-written HIP kernels.
     AntialiasedDepthRaster   the same, clamped and antialiased: gradients at the silhouette too
     MeshAttributeRaster      TriangleDepthRaster + per-pixel maps of per-vertex attributes (part maps, correspondences)
     AntialiasedAttributeRaster  the maps and the clamped depth, both antialiased: outline gradients for the maps too
+    MeshNormalRaster         a unit normal map from area-weighted vertex normals, and the depth: gradients reach z
 """
 import numpy as np
 import torch
@@ -310,6 +311,87 @@ class AntialiasedAttributeRaster(nn.Module):
         depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
         raw = depth.detach()
         maps = ops.TriInterpolate.apply(attributes, owner, v, self.faces_i32)
+        maps = ops.TriAntialiasMaps.apply(maps, raw, owner, v, self.faces_i32, self.edges_i32)
+        c = torch.clamp(depth, max=self.clamp_max)
+        return maps, ops.TriAntialias.apply(c, raw, owner, v, self.faces_i32, self.edges_i32)
+
+
+class MeshNormalRaster(nn.Module):
+    """A normal map and the depth from one raster: forward(vertices[B,NV,>=3] pixel-space x, y, z, points=None) ->
+    (normal_map [B,3,height,width], depth [B,height,width]).  One owner forward, ops.TriVertexNormals on `points`
+    ([B,NV,>=3]; default: the vertices' x, y, z), ops.TriInterpolate of the vertex normals and ops.Unit3Maps on the
+    result (include/spherehand_hip.h states all three).  Background pixels are (0, 0, 0); every owned pixel has unit
+    length.  `depth` is TriangleDepthRaster's raw depth, the same bits.
+
+    antialias=True adds ops.TriAntialiasMaps after the normalisation and returns AntialiasedDepthRaster's depth
+    (clamp(raw, max=clamp_max) through ops.TriAntialias), as AntialiasedAttributeRaster does: a blended outline pixel is
+    then SHORTER than 1, and its length carries the coverage.
+
+    The normals are those of the points given.  Pixel-space x, y with a depth-unit z is an anisotropic space: its normals
+    are good for consistency losses and for the out-of-plane gradient, not for angles.  For metric normals pass the
+    unprojected skinned points (SparseSkinning without a camera) as `points`.
+
+    Orientation: the raster's cull (mesh/cuda_kernel/depth_rasterization_cuda_kernel.cu:33) draws a face when
+    (y2 - y0)(x1 - x0) >= (y1 - y0)(x2 - x0), which is a non-negative z of e1 x e2 for the faces as the raster takes
+    them: in their own winding drawn faces point away from the camera (smaller depth is nearer).  The module builds its
+    normal tables from those faces with corners 1 and 2 exchanged, which negates every face normal exactly, so the normals
+    of drawn faces have z <= 0: they point at the camera.  (Only with `points` in a space of the vertices' handedness.)
+    ops.tri_vertex_normals itself never flips.
+
+    The map is differentiable w.r.t. `points` in x, y and z (through the normals) and w.r.t. vertices[..., :2] (through
+    the interpolation weights, and the outline with antialias=True); coverage and owner are held fixed.  `np_faces` gets
+    the right hand's winding swap (mesh/render.py:298-300) and is not modified; `np_vertices` (rest positions [NV,C])
+    welds vertices with bit-identical rows for the normals' sums and for the edge table -- a mesh that stores every face's
+    corners separately gets faceted normals without it."""
+
+    def __init__(self, width, height, np_faces, right_hand=True, np_vertices=None, antialias=False, clamp_max=100.0):
+        super().__init__()
+        self.width = width
+        self.height = height
+        self.antialias = antialias
+        self.clamp_max = clamp_max
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+        turned = np.ascontiguousarray(faces[:, [0, 2, 1]])
+        self.register_buffer('normal_faces_i32', torch.from_numpy(turned.astype(np.int32)).contiguous())
+        if np_vertices is not None:
+            self.num_vertices = len(np_vertices)
+        else:
+            self.num_vertices = None
+        self._np_faces, self._np_weld = turned, (None if np_vertices is None else np.array(np_vertices, copy=True))
+        self._tables = {}
+        if antialias:
+            self.register_buffer('edges_i32', torch.from_numpy(ops.tri_edge_table(faces, np_vertices)).contiguous())
+
+    def _normal_tables(self, NV, device):
+        """The tables for NV vertices on `device` (built on first use: without np_vertices the constructor does not know NV)."""
+        key = (NV, str(device))
+        if key not in self._tables:
+            if self.num_vertices is not None and NV != self.num_vertices:
+                raise RuntimeError("MeshNormalRaster was built for %d vertices" % self.num_vertices)
+            self._tables[key] = ops.tri_vertex_tables(self._np_faces, NV, self._np_weld).to(device)
+        return self._tables[key]
+
+    def forward(self, vertices, points=None):
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("MeshNormalRaster takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        if points is None:
+            p = v
+        else:
+            if points.dim() != 3 or points.shape[-1] < 3 or points.shape[:2] != vertices.shape[:2]:
+                raise RuntimeError("points must be [B,NV,>=3] with the vertices' B and NV")
+            p = points if points.shape[-1] in (3, 4) else points[..., :3]
+        depth, owner = ops.TriRasterIndexedOwner.apply(v, self.faces_i32, self.width, self.height)
+        tables = self._normal_tables(v.shape[1], v.device)
+        normals = ops.TriVertexNormals.apply(p, self.normal_faces_i32, tables)
+        maps = ops.TriInterpolate.apply(normals[..., :3], owner, v, self.faces_i32)
+        maps = ops.Unit3Maps.apply(maps)
+        if not self.antialias:
+            return maps, depth
+        raw = depth.detach()
         maps = ops.TriAntialiasMaps.apply(maps, raw, owner, v, self.faces_i32, self.edges_i32)
         c = torch.clamp(depth, max=self.clamp_max)
         return maps, ops.TriAntialias.apply(c, raw, owner, v, self.faces_i32, self.edges_i32)
