@@ -83,6 +83,10 @@ int shr_device_info(char *name_host, int name_len, int *num_cu_host);
 #define SHR_TUNE_MESH_BAND 17        /* shr_mesh_depth_fwd / shr_mesh_render_fwd at sizes without a lattice kernel whose resize
                                     * samples at least half of the source pixels (S = 256 from 640): 1 = the triangle band
                                     * kernel with clamp + resize as its stream-out (default), 0 = the tile kernel */
+#define SHR_TUNE_MESH_LATTICE 18     /* shr_mesh_depth_fwd / shr_mesh_render_fwd / shr_mesh_render_post_fwd at integer resize
+                                    * ratios whose sampled pixels fit a 128 x 128 lattice (S = 128 / 64 / 32 from 640): 1 =
+                                    * the one-workgroup-per-crop lattice kernel (default), 0 = never (the tile kernel; the
+                                    * *_one_launch queries answer 0 and shr_hand_synth_fwd SHR_EINVAL) */
 int shr_set_tuning(int key, int value);
 /* Self-test: adds to *mismatches (device, caller-zeroed u64) the number of fp32
  * bit patterns in [lo_bits, hi_bits) where the rasterizer's internal square root

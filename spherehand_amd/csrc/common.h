@@ -185,13 +185,14 @@ int d2m_set_band_units(int units);  // SHR_TUNE_D2M_BAND_UNITS
 int d2m_set_tiled(int on);          // SHR_TUNE_D2M_TILED
 int tri_set_band(int rows);         // tri_raster.hip: SHR_TUNE_TRI_BAND
 int mesh_set_band(int on);          // mesh_depth.hip: SHR_TUNE_MESH_BAND
+int mesh_set_lattice(int on);       // mesh_depth.hip: SHR_TUNE_MESH_LATTICE
 int tri_band_resize(const float *vertices, const int *faces, int B, int NV, int F, int src_size, int S, float clamp_max,
                     float *depth, hipStream_t s);   // tri_raster.hip: the band kernel with the clamp + resize epilogue (-1: not its problem)
 // data_to_model.hip: the two halves of shr_data_to_model_compact (mutual_project.hip: shr_mv_project_compact)
 int d2m_compact_check(const float *depth, int M, int H, int W, void *workspace, int **counts);
 int d2m_compact_launch(const float *depth, int M, int H, int W, void *workspace, hipStream_t s);
 
-// Linear blend skinning of one vertex for one sample, shared by lbs_project_kernel (tri_raster.hip) and the fused
+// Linear blend skinning of one vertex for one sample, shared by lbs_project_kernel (lbs_project.hip) and the fused
 // mesh_lattice_kernel (mesh_depth.hip): one (bone, weighted vertex) entry added to the four rows of the sum, and the
 // sign flip + orthographic camera of mesh/render.py:320-329 on the finished sum.  M = the bone's 4 x 4 matrix.
 __device__ __forceinline__ void lbs_add_entry(float (&acc)[4], const float *M, const float4 q) {

@@ -20,7 +20,6 @@
 // Zero-weight slots are not rasterized (0 * finite = 0 contributes nothing); the only
 // input on which this differs from the reference chain is a raster value of -inf next to a
 // sampled pixel (an exactly zero 1/z denominator), where the reference's 0 * -inf is NaN.
-#include <cstdlib>
 #include <type_traits>
 
 #include "fk_rows.h"
@@ -448,14 +447,14 @@ mesh_depth_owner_kernel(const float4 *__restrict__ vertices, const int *__restri
 // lane -- 68 batches x 3-4 iterations of ~140 instructions for a crop's ~4 800 sampled pixels, three lanes in ten busy
 // (EXPERIMENTS R4) -- and rebuilds the faces its 768-row table cannot hold; here every face is set up once and the
 // division chains run on full waves.  Same pixels, same arithmetic per pixel, integer minima: bit-identical images.
-// WAVES x NF: waves per workgroup x faces per batch.  16 x 32 (3.6 KB of scratch per wave) or 12 x 64 (6.7 KB): full
-// lanes in the set-up and fuller chunks and drains for a quarter fewer waves to hide latency with.
+constexpr int kLatWaves = 16, kLatFaces = 32;                   // waves per workgroup x faces per batch (3.6 KB of scratch per wave)
+constexpr int kFaceBits = 5;                                    // a queue entry's bits of face: kLatFaces = 32
 constexpr int kLatQueue = 128;                                  // queued pixels per wave (4-byte entries)
-constexpr int lat_scratch_bytes(int nf) { return nf * (int)sizeof(FaceRow) + kLatQueue * 4 + 64; }   // rows | queue | start marks
+constexpr int lat_scratch_bytes() { return kLatFaces * (int)sizeof(FaceRow) + kLatQueue * 4 + 64; }   // rows | queue | start marks
 constexpr int kLatMax = 128;                                    // lattice rows / columns (7 bits each in a queue entry)
 
-__host__ __device__ inline size_t lattice_lds_bytes(int L, int F, int waves, int nf, int skinned_vertices = 0) {
-  return (((size_t)L * (L + 1) * 4 + 15) & ~(size_t)15) + (size_t)((F + 7) & ~7) * 2 + (size_t)waves * lat_scratch_bytes(nf) +
+__host__ __device__ inline size_t lattice_lds_bytes(int L, int F, int skinned_vertices = 0) {
+  return (((size_t)L * (L + 1) * 4 + 15) & ~(size_t)15) + (size_t)((F + 7) & ~7) * 2 + (size_t)kLatWaves * lat_scratch_bytes() +
          (size_t)skinned_vertices * 16;
 }
 // SKIN (shr_mesh_render_fwd: all of DepthRender.forward in one launch): the crop's vertices are skinned and projected by
@@ -517,12 +516,10 @@ depth_post_kernel(const float *__restrict__ in, int B, int H, int W, LatticePost
   if (post.state && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) post.state[1] += 1ull;
 }
 
-template <int SL, int kLatWaves, int kLatFaces, bool SKIN = false, bool POST = false>
+template <int SL, bool SKIN = false, bool POST = false>
 __global__ void __launch_bounds__(kLatWaves * 64)
 mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__ faces, int NV, int F, int src, int S,
                     float clamp_max, float *__restrict__ depth, LatticeSkin skin, LatticePost post) {
-  static_assert(kLatFaces == 32 || kLatFaces == 64, "queue entries: 5 or 6 bits of face");
-  constexpr int kFaceBits = kLatFaces == 64 ? 6 : 5;
   extern __shared__ __attribute__((aligned(16))) unsigned char lat_smem[];
   const int L = SL * S, LP = L + 1;
   uint32_t *s_z = reinterpret_cast<uint32_t *>(lat_smem);                                   // [L][L + 1] keys
@@ -535,13 +532,13 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
   __shared__ float4 s_kp[POST ? 64 : 1];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool own_pose = POST && post.params != nullptr, paint = POST && post.uv_hm != nullptr;
-  float4 *s_verts = reinterpret_cast<float4 *>(s_scr + (size_t)kLatWaves * lat_scratch_bytes(kLatFaces));   // SKIN: [NV]
+  float4 *s_verts = reinterpret_cast<float4 *>(s_scr + (size_t)kLatWaves * lat_scratch_bytes());   // SKIN: [NV]
   const float4 *verts = SKIN ? s_verts : vertices + (size_t)b * NV;
   MESH_STAMP(0);
   if (tid == 0) s_nsurv = 0;
   // SKIN: the corners of this thread's faces of the first round of culls are requested now -- they depend on nothing, and
   // by the time the vertices stand in LDS the culls' only global round trip is over
-  constexpr int kPer = kLatWaves >= 16 ? 4 : 5;   // faces per thread and round of culls: one round for the 3382-face hand mesh
+  constexpr int kPer = 4;   // faces per thread and round of culls: one round for the 3382-face hand mesh
   int corner[kPer][3];
   if (SKIN) {
 #pragma unroll
@@ -552,7 +549,7 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
     }
   }
   if (SKIN) {
-    // ---- 0. skinning + camera (mesh/render.py:320-329; tri_raster.hip lbs_project_kernel) ----------------------------
+    // ---- 0. skinning + camera (mesh/render.py:320-329; lbs_project.hip lbs_project_kernel) ---------------------------
     float *s_T = reinterpret_cast<float *>(s_scr);                     // the bones' matrices, in the scratch nobody uses yet
     // A chain of round trips -- matrices, entry ranges, entries -- of which only the sum needs the matrices: a thread's
     // first two vertices' ranges and their first four entries each (a hand vertex has 1 .. 5) are requested before the
@@ -674,9 +671,9 @@ mesh_lattice_kernel(const float4 *__restrict__ vertices, const int *__restrict__
 
   // ---- 2. the survivors, 32 at a time per wave ------------------------------------------------------------------------
   {
-    FaceRow *s_face = reinterpret_cast<FaceRow *>(s_scr + (size_t)wave * lat_scratch_bytes(kLatFaces));
-    uint32_t *s_queue = reinterpret_cast<uint32_t *>(s_scr + (size_t)wave * lat_scratch_bytes(kLatFaces) + kLatFaces * sizeof(FaceRow));
-    unsigned char *s_mark = s_scr + (size_t)wave * lat_scratch_bytes(kLatFaces) + kLatFaces * sizeof(FaceRow) + kLatQueue * 4;
+    FaceRow *s_face = reinterpret_cast<FaceRow *>(s_scr + (size_t)wave * lat_scratch_bytes());
+    uint32_t *s_queue = reinterpret_cast<uint32_t *>(s_scr + (size_t)wave * lat_scratch_bytes() + kLatFaces * sizeof(FaceRow));
+    unsigned char *s_mark = s_scr + (size_t)wave * lat_scratch_bytes() + kLatFaces * sizeof(FaceRow) + kLatQueue * 4;
     const int n = s_nsurv;
     MESH_NOTE(9, n);
     // batches of 32 survivors dealt round robin (face numbers cluster: a wave's own contiguous share was all palm or all
@@ -898,45 +895,90 @@ extern "C" int shr_mesh_debug_timeline(unsigned long long *host_out) {
 }
 #endif
 
-static int g_mesh_band = 1;   // SHR_TUNE_MESH_BAND
+static int g_mesh_band = 1;      // SHR_TUNE_MESH_BAND
+static int g_mesh_lattice = 1;   // SHR_TUNE_MESH_LATTICE
 int shr::mesh_set_band(int on) { g_mesh_band = on; return SHR_OK; }
+int shr::mesh_set_lattice(int on) { g_mesh_lattice = on; return SHR_OK; }
+
+// ---- the launch plan: every decision of the entries below, stated once ------------------------------------------------------
+namespace {
+using namespace shr;
+
+// The resize src_size -> S as the kernels' template parameters: an integer ratio (EXACT: closed forms) or not, and SL, the
+// source slots per output pixel and axis -- 1 for an odd integer ratio (src = ratio * d + (ratio - 1) / 2 exactly, bilinear
+// weights (1, 0)), 2 for an even one and for any other ratio.
+struct Resize {
+  bool integer;
+  int SL;
+  Resize(int src_size, int S) : integer(src_size % S == 0), SL(integer && ((src_size / S) & 1) == 1 ? 1 : 2) {}
+};
+
+constexpr size_t kLatLdsMax = 160 * 1024 - 2048;   // the lattice kernel's dynamic LDS (+ the static arrays)
+
+// Does the lattice kernel take the problem?  An integer ratio, a lattice of sampled source pixels of at most 128 x 128, face
+// numbers of 16 bits, one workgroup's LDS; NB > 0: the fused skinning of NB bones (the vertices in LDS too, the matrices
+// staged in the waves' scratch), NB = 0: vertices that are skinned already.
+bool lattice_takes(int NB, int NV, int F, int src_size, int S) {
+  if (g_mesh_lattice == 0 || S <= 0 || src_size <= 0) return false;
+  const Resize rz(src_size, S);
+  if (!rz.integer || rz.SL * S > kLatMax || F <= 0 || F > 65535) return false;
+  if (lattice_lds_bytes(rz.SL * S, F, NB ? NV : 0) > kLatLdsMax) return false;
+  return (long long)NB * 64 <= kLatWaves * lat_scratch_bytes();
+}
+
+// sizes beyond the forward entries' packing: no up-sampling; work items pack the face index in 24 bits, the face rows pixel
+// ranges in 16
+bool mesh_fwd_too_large(int B, int F, int src_size, int S) {
+  return B > 65535 || S > 16384 || src_size > 32767 || S > src_size || F > (1 << 24);
+}
+
+dim3 tile_grid(int S, int TO, int B) {   // the tile kernels': ceil(S / TO)^2 tiles per crop
+  const int t = (S + TO - 1) / TO;
+  return dim3((unsigned)(t * t), (unsigned)B);
+}
+
+LatticeSkin lattice_skin(const float *T, int NB, const int32_t *skin_vertex_start, const int32_t *skin_bone, const float *skin_wv,
+                         int right_hand, float cx, float cy, float fx, float fy, const float *rand_f) {
+  return LatticeSkin{T, skin_vertex_start, skin_bone, reinterpret_cast<const float4 *>(skin_wv), rand_f, NB, right_hand, cx, cy, fx, fy};
+}
+
+// the scale-and-noise tail's arguments (keys = nullptr: no noise; the thresholds are then those of sigma 0.5, unread)
+LatticePost lattice_post(float depth_scale, const uint32_t *keys, float sigma_xy, float sigma_z, unsigned long long *state, int B) {
+  LatticePost po = {};
+  po.depth_scale = depth_scale; po.keys = keys; po.sigma_z = sigma_z; po.state = state; po.B = B;
+  // P(trunc(n sigma + 0.5) < k) = Phi((k - 0.5) / sigma) for k <= 0 (truncation towards zero: shift 0 holds (-1, 1))
+  auto Phi = [](double x) { return 0.5 * erfc(-x / 1.4142135623730951); };
+  const double s = keys ? (double)sigma_xy : 0.5;
+  po.t0 = (uint32_t)llround(65536.0 * Phi((-1.0 - 0.5) / s));     // shift <= -1  <=>  n sigma + 0.5 <= -1
+  po.t1 = (uint32_t)llround(65536.0 * Phi((1.0 - 0.5) / s));      // shift <= 0   <=>  n sigma + 0.5 < 1
+  po.t2 = (uint32_t)llround(65536.0 * Phi((2.0 - 0.5) / s));      // shift <= 1   <=>  n sigma + 0.5 < 2
+  return po;
+}
 
 // the lattice kernel's launch (vertices: skinned ones in HBM, or nullptr with `skin` for the fused kernel); returns -1
-// when the problem is not the lattice kernel's (non-integer ratio, lattice above 128 x 128, LDS)
-static int mesh_lattice_launch(const float4 *v4, const shr::LatticeSkin *skin, const int32_t *faces, int B, int NV, int F,
-                               int src_size, int S, float clamp_max, float *depth, hipStream_t s,
-                               const shr::LatticePost *post = nullptr) {
-  using namespace shr;
-  static const int lattice_mode = [] { const char *e = getenv("SHR_MESH_LATTICE"); return e ? atoi(e) : 1; }();   // 0: off, 1: 16 x 32, 2: 12 x 64
-  const bool single = (src_size % S == 0) && (((src_size / S) & 1) == 1);
-  const bool even = (src_size % S == 0) && (((src_size / S) & 1) == 0);
-  const int SLx = single ? 1 : 2;
-  const int lw = lattice_mode == 2 ? 12 : 16, lf = lattice_mode == 2 ? 64 : 32;
-  const size_t lat_lds = lattice_lds_bytes(SLx * S, F, lw, lf, skin ? NV : 0);
-  if (lattice_mode == 0 || !(single || even) || SLx * S > kLatMax || F <= 0 || F > 65535 || lat_lds > 160 * 1024 - 2048) return -1;   // (+ the static arrays)
-  if (skin && (skin->NB * 64 > lw * lat_scratch_bytes(lf))) return -1;     // (the matrices are staged in the scratch)
-  static AttrDone attr_done[10];   // per (kernel, device)
+// when the problem is not the lattice kernel's (lattice_takes)
+int mesh_lattice_launch(const float4 *v4, const LatticeSkin *skin, const int32_t *faces, int B, int NV, int F, int src_size,
+                        int S, float clamp_max, float *depth, hipStream_t s, const LatticePost *post = nullptr) {
+  if (!lattice_takes(skin ? skin->NB : 0, NV, F, src_size, S)) return -1;
+  const bool single = Resize(src_size, S).SL == 1;
+  const size_t lat_lds = lattice_lds_bytes(single ? S : 2 * S, F, skin ? NV : 0);
+  static AttrDone attr_done[6];   // per (kernel, device)
   LatticeSkin sk = {};
   if (skin) sk = *skin;
   LatticePost po = {};
   if (post) po = *post;
   auto launch = [&](auto kernel, int which) -> int {
-    const hipError_t e = allow_dynamic_lds(kernel, 160 * 1024 - 2048, &attr_done[which]);
+    const hipError_t e = allow_dynamic_lds(kernel, (int)kLatLdsMax, &attr_done[which]);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(lw * 64), lat_lds, s, v4, faces, NV, F, src_size, S, clamp_max, depth, sk, po);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kLatWaves * 64), lat_lds, s, v4, faces, NV, F, src_size, S, clamp_max, depth, sk, po);
     return (int)hipGetLastError();
   };
-  if (skin && post) {   // (the synthesizer's launch: the default wave x face shape only)
-    if (lattice_mode == 2) return -1;
-    return single ? launch(mesh_lattice_kernel<1, 16, 32, true, true>, 8) : launch(mesh_lattice_kernel<2, 16, 32, true, true>, 9);
-  }
-  if (skin) {
-    if (lattice_mode == 2) return single ? launch(mesh_lattice_kernel<1, 12, 64, true>, 6) : launch(mesh_lattice_kernel<2, 12, 64, true>, 7);
-    return single ? launch(mesh_lattice_kernel<1, 16, 32, true>, 4) : launch(mesh_lattice_kernel<2, 16, 32, true>, 5);
-  }
-  if (lattice_mode == 2) return single ? launch(mesh_lattice_kernel<1, 12, 64>, 2) : launch(mesh_lattice_kernel<2, 12, 64>, 3);
-  return single ? launch(mesh_lattice_kernel<1, 16, 32>, 0) : launch(mesh_lattice_kernel<2, 16, 32>, 1);
+  if (skin && post) return single ? launch(mesh_lattice_kernel<1, true, true>, 4) : launch(mesh_lattice_kernel<2, true, true>, 5);
+  if (skin) return single ? launch(mesh_lattice_kernel<1, true>, 2) : launch(mesh_lattice_kernel<2, true>, 3);
+  return single ? launch(mesh_lattice_kernel<1>, 0) : launch(mesh_lattice_kernel<2>, 1);
 }
+
+}  // namespace
 
 extern "C" int shr_mesh_depth_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int src_size,
                                   int S, float clamp_max, float *depth, void *stream) {
@@ -945,21 +987,11 @@ extern "C" int shr_mesh_depth_fwd(const float *vertices, const int32_t *faces, i
   if (!vertices || (!faces && F > 0) || !depth || B < 0 || NV <= 0 || F < 0 || src_size <= 0 || S <= 0)
     return SHR_EINVAL;
   if (((uintptr_t)vertices & 15u) != 0) return SHR_EINVAL;
-  if (B > 65535 || S > 16384 || src_size > 32767 || S > src_size || F > (1 << 24))
-    return SHR_ETOOLARGE;  // no up-sampling; work items pack the face index in 24 bits, the face rows pixel ranges in 16
+  if (mesh_fwd_too_large(B, F, src_size, S)) return SHR_ETOOLARGE;
   hipStream_t s = (hipStream_t)stream;
   const float4 *v4 = reinterpret_cast<const float4 *>(vertices);
-  // odd integer ratio: src = ratio * d + (ratio - 1) / 2 exactly, bilinear weights (1, 0)
-  const bool single = (src_size % S == 0) && (((src_size / S) & 1) == 1);
-  const bool even = (src_size % S == 0) && (((src_size / S) & 1) == 0);   // even integer ratio: two slots, closed forms
-#define MESH_LAUNCH(TO, SL, EX)                                                                                  \
-  do {                                                                                                           \
-    const int t = (S + (TO) - 1) / (TO);                                                                         \
-    hipLaunchKernelGGL((mesh_depth_kernel<TO, SL, EX>), dim3((unsigned)(t * t), (unsigned)B), dim3(1024), 0, s,  \
-                       v4, faces, NV, F, src_size, S, clamp_max, depth);                                         \
-  } while (0)
   {   // integer ratio and a lattice of sampled source pixels that fits one workgroup's LDS: the lattice kernel
-      // (SHR_MESH_LATTICE=0 in the environment keeps the tile kernel: tests and tools compare the two)
+      // (SHR_TUNE_MESH_LATTICE 0 keeps the tile kernel: tests and tools compare the two)
     const int r = mesh_lattice_launch(v4, nullptr, faces, B, NV, F, src_size, S, clamp_max, depth, s);
     if (r >= 0) return r;
   }
@@ -971,15 +1003,14 @@ extern "C" int shr_mesh_depth_fwd(const float *vertices, const int32_t *faces, i
       if (r >= 0) return r;
     }
   }
-  if (single) {
-    if (S > 64) MESH_LAUNCH(128, 1, true); else MESH_LAUNCH(64, 1, true);
-  } else if (even) {
-    if (S > 32) MESH_LAUNCH(64, 2, true); else MESH_LAUNCH(32, 2, true);
-  } else {
-    if (S > 32) MESH_LAUNCH(64, 2, false); else MESH_LAUNCH(32, 2, false);
-  }
-#undef MESH_LAUNCH
-  return (int)hipGetLastError();
+  auto launch = [&](auto kernel, int TO) -> int {
+    hipLaunchKernelGGL(kernel, tile_grid(S, TO, B), dim3(1024), 0, s, v4, faces, NV, F, src_size, S, clamp_max, depth);
+    return (int)hipGetLastError();
+  };
+  const Resize rz(src_size, S);
+  if (rz.SL == 1) return S > 64 ? launch(mesh_depth_kernel<128, 1, true>, 128) : launch(mesh_depth_kernel<64, 1, true>, 64);
+  if (rz.integer) return S > 32 ? launch(mesh_depth_kernel<64, 2, true>, 64) : launch(mesh_depth_kernel<32, 2, true>, 32);
+  return S > 32 ? launch(mesh_depth_kernel<64, 2, false>, 64) : launch(mesh_depth_kernel<32, 2, false>, 32);
 }
 
 /* shr_mesh_depth_fwd's images plus the owner of every bilinear tap, for the differentiable DepthRender: the tile kernel's
@@ -992,30 +1023,20 @@ extern "C" int shr_mesh_depth_owner_fwd(const float *vertices, const int32_t *fa
     return SHR_EINVAL;
   if ((((uintptr_t)vertices | (uintptr_t)owner) & 15u) != 0) return SHR_EINVAL;
   if (B > 65535 || src_size > 32767 || 2 * S > src_size || F > (1 << 24)) return SHR_ETOOLARGE;
-  hipStream_t s = (hipStream_t)stream;
-  const float4 *v4 = reinterpret_cast<const float4 *>(vertices);
-  const bool single = (src_size % S == 0) && (((src_size / S) & 1) == 1);
-  const bool even = (src_size % S == 0) && (((src_size / S) & 1) == 0);
-#define MESH_OWNER_LAUNCH(TO, SL, EX)                                                                            \
-  do {                                                                                                           \
-    const int t = (S + (TO) - 1) / (TO);                                                                         \
-    hipLaunchKernelGGL((mesh_depth_owner_kernel<TO, SL, EX>), dim3((unsigned)(t * t), (unsigned)B), dim3(1024), 0, s, \
-                       v4, faces, NV, F, src_size, S, clamp_max, depth, owner);                                  \
-  } while (0)
-  if (single) MESH_OWNER_LAUNCH(64, 1, true);
-  else if (even) MESH_OWNER_LAUNCH(32, 2, true);
-  else MESH_OWNER_LAUNCH(32, 2, false);
-#undef MESH_OWNER_LAUNCH
-  return (int)hipGetLastError();
+  auto launch = [&](auto kernel, int TO) -> int {
+    hipLaunchKernelGGL(kernel, tile_grid(S, TO, B), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<const float4 *>(vertices),
+                       faces, NV, F, src_size, S, clamp_max, depth, owner);
+    return (int)hipGetLastError();
+  };
+  const Resize rz(src_size, S);
+  if (rz.SL == 1) return launch(mesh_depth_owner_kernel<64, 1, true>, 64);
+  return rz.integer ? launch(mesh_depth_owner_kernel<32, 2, true>, 32) : launch(mesh_depth_owner_kernel<32, 2, false>, 32);
 }
 
 /* DepthRender.forward (mesh/render.py:315-331) in ONE launch where the lattice kernel applies: skinning + camera
  * (shr_lbs_project's arguments, always projecting) + raster + clamp + resize (shr_mesh_depth_fwd's).  Otherwise the two
  * launches, through `vertices_ws` [B][NV][4] (16-byte aligned; may be NULL only if the caller knows the fused kernel
  * applies: SHR_EINVAL then).  Same images either way. */
-extern "C" int shr_lbs_project(const float *T, int B, int NB, int NV, const int32_t *skin_vertex_start, const int32_t *skin_bone,
-                               const float *skin_wv, int right_hand, int project, float cx, float cy, float fx, float fy,
-                               const float *rand_f, float *out, void *stream);
 extern "C" int shr_mesh_render_fwd(const float *T, int B, int NB, int NV, const int32_t *skin_vertex_start,
                                    const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy,
                                    float fx, float fy, const float *rand_f, const int32_t *faces, int F, int src_size,
@@ -1026,10 +1047,8 @@ extern "C" int shr_mesh_render_fwd(const float *T, int B, int NB, int NV, const 
       F < 0 || src_size <= 0 || S <= 0)
     return SHR_EINVAL;
   if (((uintptr_t)skin_wv & 15u) != 0) return SHR_EINVAL;
-  if (B > 65535 || S > 16384 || src_size > 32767 || S > src_size || F > (1 << 24) || NB > 160) return SHR_ETOOLARGE;
-  LatticeSkin sk;
-  sk.T = T; sk.vstart = skin_vertex_start; sk.sbone = skin_bone; sk.swv = reinterpret_cast<const float4 *>(skin_wv);
-  sk.rand_f = rand_f; sk.NB = NB; sk.right_hand = right_hand; sk.cx = cx; sk.cy = cy; sk.fx = fx; sk.fy = fy;
+  if (mesh_fwd_too_large(B, F, src_size, S) || NB > 160) return SHR_ETOOLARGE;
+  const LatticeSkin sk = lattice_skin(T, NB, skin_vertex_start, skin_bone, skin_wv, right_hand, cx, cy, fx, fy, rand_f);
   const int r = mesh_lattice_launch(nullptr, &sk, faces, B, NV, F, src_size, S, clamp_max, depth, (hipStream_t)stream);
   if (r >= 0) return r;
   if (!vertices_ws) return SHR_EINVAL;
@@ -1041,13 +1060,7 @@ extern "C" int shr_mesh_render_fwd(const float *T, int B, int NB, int NV, const 
 
 /* 1 where shr_mesh_render_fwd / shr_mesh_render_post_fwd take the problem as ONE launch (no workspaces needed), else 0 */
 extern "C" int shr_mesh_render_one_launch(int NB, int NV, int F, int src_size, int S) {
-  using namespace shr;
-  static const int lattice_mode = [] { const char *e = getenv("SHR_MESH_LATTICE"); return e ? atoi(e) : 1; }();
-  if (lattice_mode != 1 || S <= 0 || src_size <= 0 || src_size % S != 0) return 0;
-  const int SLx = ((src_size / S) & 1) ? 1 : 2;
-  if (SLx * S > kLatMax || F <= 0 || F > 65535) return 0;
-  if (lattice_lds_bytes(SLx * S, F, 16, 32, NV) > 160 * 1024 - 2048 || NB * 64 > 16 * lat_scratch_bytes(32)) return 0;
-  return 1;
+  return NB > 0 && lattice_takes(NB, NV, F, src_size, S) ? 1 : 0;
 }
 
 /* HandSynthesizer.forward's depth branch (network/util_modules.py:111-116): DepthRender, `* depth_scale` and DepthNoise.
@@ -1068,19 +1081,9 @@ extern "C" int shr_mesh_render_post_fwd(const float *T, int B, int NB, int NV, c
     return SHR_EINVAL;
   if (((uintptr_t)skin_wv & 15u) != 0 || ((uintptr_t)depth & 15u) != 0 || ((uintptr_t)rng_state & 7u) != 0) return SHR_EINVAL;
   if (noise_keys && !(sigma_xy > 0.f && sigma_xy <= 0.6f)) return SHR_EINVAL;   // (shifts -1 .. +2 hold all but 1e-5 of the mass)
-  if (B > 65535 || S > 16384 || src_size > 32767 || S > src_size || F > (1 << 24) || NB > 160) return SHR_ETOOLARGE;
-  LatticePost po = {};
-  po.depth_scale = depth_scale; po.keys = noise_keys; po.sigma_z = sigma_z; po.state = rng_state; po.B = B;
-  {   // P(trunc(n sigma + 0.5) < k) = Phi((k - 0.5) / sigma) for k <= 0 (truncation towards zero: shift 0 holds (-1, 1))
-    auto Phi = [](double x) { return 0.5 * erfc(-x / 1.4142135623730951); };
-    const double s = noise_keys ? (double)sigma_xy : 0.5;
-    po.t0 = (uint32_t)llround(65536.0 * Phi((-1.0 - 0.5) / s));     // shift <= -1  <=>  n sigma + 0.5 <= -1
-    po.t1 = (uint32_t)llround(65536.0 * Phi((1.0 - 0.5) / s));      // shift <= 0   <=>  n sigma + 0.5 < 1
-    po.t2 = (uint32_t)llround(65536.0 * Phi((2.0 - 0.5) / s));      // shift <= 1   <=>  n sigma + 0.5 < 2
-  }
-  LatticeSkin sk;
-  sk.T = T; sk.vstart = skin_vertex_start; sk.sbone = skin_bone; sk.swv = reinterpret_cast<const float4 *>(skin_wv);
-  sk.rand_f = rand_f; sk.NB = NB; sk.right_hand = right_hand; sk.cx = cx; sk.cy = cy; sk.fx = fx; sk.fy = fy;
+  if (mesh_fwd_too_large(B, F, src_size, S) || NB > 160) return SHR_ETOOLARGE;
+  const LatticePost po = lattice_post(depth_scale, noise_keys, sigma_xy, sigma_z, rng_state, B);
+  const LatticeSkin sk = lattice_skin(T, NB, skin_vertex_start, skin_bone, skin_wv, right_hand, cx, cy, fx, fy, rand_f);
   const int r = mesh_lattice_launch(nullptr, &sk, faces, B, NV, F, src_size, S, clamp_max, depth, (hipStream_t)stream, &po);
   if (r >= 0) return r;
   if (!depth_ws || depth_ws == depth) return SHR_EINVAL;
@@ -1127,16 +1130,8 @@ extern "C" int shr_hand_synth_fwd(const float *params, int B, const float *offse
   if (noise && !(sigma_xy > 0.f && sigma_xy <= 0.6f)) return SHR_EINVAL;
   if (B > 65535) return SHR_ETOOLARGE;
   if (!shr_hand_synth_one_launch(kBones, NV, F, src_size, S, uv_hm ? J : 0, uv_hm ? hm : 1)) return SHR_EINVAL;
-  LatticePost po = {};
-  po.depth_scale = depth_scale; po.keys = noise ? reinterpret_cast<const uint32_t *>(draws) : nullptr; po.sigma_z = sigma_z;
-  po.state = rng_state; po.B = B;
-  {
-    auto Phi = [](double x) { return 0.5 * erfc(-x / 1.4142135623730951); };
-    const double sg = noise ? (double)sigma_xy : 0.5;
-    po.t0 = (uint32_t)llround(65536.0 * Phi(-1.5 / sg));
-    po.t1 = (uint32_t)llround(65536.0 * Phi(0.5 / sg));
-    po.t2 = (uint32_t)llround(65536.0 * Phi(1.5 / sg));
-  }
+  LatticePost po = lattice_post(depth_scale, noise ? reinterpret_cast<const uint32_t *>(draws) : nullptr, sigma_xy, sigma_z,
+                                rng_state, B);
   po.params = params; po.offset = offset; po.offset_inv = offset_inv;
   po.rand_scale = rand_scale; po.rand_half = (float)((double)rand_scale / 2.0); po.draws = draws;
   if (uv_hm) {
@@ -1148,9 +1143,7 @@ extern "C" int shr_hand_synth_fwd(const float *params, int B, const float *offse
     po.a00 = a00; po.a03 = a03; po.a11 = a11; po.a13 = a13;
     po.uv_hm = uv_hm; po.d_hm = d_hm; po.xyz = reinterpret_cast<float4 *>(xyz);
   }
-  LatticeSkin sk;
-  sk.T = nullptr; sk.vstart = skin_vertex_start; sk.sbone = skin_bone; sk.swv = reinterpret_cast<const float4 *>(skin_wv);
-  sk.rand_f = nullptr; sk.NB = kBones; sk.right_hand = right_hand; sk.cx = cx; sk.cy = cy; sk.fx = fx; sk.fy = fy;
+  const LatticeSkin sk = lattice_skin(nullptr, kBones, skin_vertex_start, skin_bone, skin_wv, right_hand, cx, cy, fx, fy, nullptr);
   const int r = mesh_lattice_launch(nullptr, &sk, faces, B, NV, F, src_size, S, clamp_max, depth, (hipStream_t)stream, &po);
   return r >= 0 ? r : SHR_EINVAL;
 }

@@ -1,5 +1,5 @@
 // mesh_depth_bwd.hip -- the backward of the differentiable DepthRender / DepthRasterization: owner taps -> vertex
-// gradient -> bone-transform gradient; and of the owner raster at its own resolution (shr_tri_raster_owner_fwd): one
+// gradient (on to the bone transforms: lbs_project.hip); and of the owner raster at its own resolution (shr_tri_raster_owner_fwd): one
 // tap of weight 1 per owned pixel -> face-corner or vertex gradient (PixelTaps below).  The reference defines no backward for the mesh path (mesh/render.py:282-287);
 // the contract is the sphere backward's (ops.SphereDepthRaster): the gradient routes to the owner and holds coverage
 // fixed -- no edge, silhouette or visibility terms.
@@ -178,61 +178,6 @@ struct PixelTaps {
   }
 };
 
-// Skinning + camera backward: grad_T[b][k] = sum over the skin entries e of bone k of dacc_v(e) (x) wv_e.  One workgroup
-// per crop, one wave per bone (bones dealt round robin), lanes striding over the vertices in a fixed assignment, fp64
-// partial sums and a fixed butterfly: the same order whatever the batch -- bitwise reproducible.
-__global__ void __launch_bounds__(1024)
-lbs_project_bwd_kernel(const float4 *__restrict__ grad_vertices, int NB, int NV, const int *__restrict__ vstart,
-                       const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, float cx, float cy,
-                       float fx, float fy, const float *__restrict__ rand_f, float *__restrict__ grad_T) {
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-  const float4 *gv = grad_vertices + (size_t)b * NV;
-  const double sgn = right_hand ? -1.0 : 1.0;
-  const bool has_rand = rand_f != nullptr;
-  const double rf = has_rand ? (double)rand_f[b] : 1.0;
-  for (int k = wave; k < NB; k += waves) {
-    double a[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) a[j] = 0.0;
-    for (int v = lane; v < NV; v += 64) {
-      const int e0 = vstart[v], e1 = vstart[v + 1];
-      int e = e0;
-      while (e < e1 && sbone[e] != k) e++;
-      if (e == e1) continue;
-      const float4 g = gv[v];
-      // d out / d acc (common.h lbs_finish)
-      double d[4];
-      if (!has_rand) {
-        d[0] = sgn * (double)fx * g.x; d[1] = (double)fy * g.y; d[2] = g.z;
-        d[3] = (double)cx * g.x + (double)cy * g.y + (double)g.w;
-      } else {
-        d[0] = sgn * rf * (double)fx * g.x; d[1] = rf * (double)fy * g.y; d[2] = g.z; d[3] = 0.0;
-      }
-      for (; e < e1; e++) {
-        if (sbone[e] != k) continue;
-        const float4 q = swv[e];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          a[4 * r] += d[r] * q.x; a[4 * r + 1] += d[r] * q.y; a[4 * r + 2] += d[r] * q.z; a[4 * r + 3] += d[r] * q.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      double t = a[j];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
-      a[j] = t;
-    }
-    if (lane < 16) {
-      double t = 0.0;
-#pragma unroll
-      for (int j = 0; j < 16; j++) t = (lane == j) ? a[j] : t;
-      grad_T[((size_t)b * NB + k) * 16 + lane] = (float)t;
-    }
-  }
-}
-
 }  // namespace shr
 
 
@@ -289,19 +234,4 @@ extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *
                               fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
   return fixed_point_bwd<4>(PixelTaps<true, true>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
                             fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
-}
-
-extern "C" int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
-                                   const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy,
-                                   float fx, float fy, const float *rand_f, float *grad_T, void *stream) {
-  using namespace shr;
-  if (B == 0) return SHR_OK;
-  if (!grad_vertices || !skin_vertex_start || !skin_bone || !skin_wv || !grad_T || B < 0 || NB <= 0 || NV <= 0)
-    return SHR_EINVAL;
-  if ((((uintptr_t)grad_vertices | (uintptr_t)skin_wv) & 15u) != 0) return SHR_EINVAL;
-  if (B > (1 << 30)) return SHR_ETOOLARGE;
-  hipLaunchKernelGGL(lbs_project_bwd_kernel, dim3((unsigned)B), dim3(NB >= 16 ? 1024 : 64 * NB), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4 *>(grad_vertices), NB, NV, skin_vertex_start, skin_bone,
-                     reinterpret_cast<const float4 *>(skin_wv), right_hand, cx, cy, fx, fy, rand_f, grad_T);
-  return (int)hipGetLastError();
 }

@@ -1,11 +1,9 @@
-// tri_raster.hip -- triangle-mesh depth rasterizer (forward; the owner raster its backward needs) + skinning.
+// tri_raster.hip -- triangle-mesh depth rasterizer (forward; the owner raster its backward needs).
 //
 // Replaces (reference file:line):
 //   mesh/cuda_kernel/depth_rasterization_cuda_kernel.cu:18-113 `kernel` and :6-16
 //   `atomicMin`, :115-134 depth_rasterization_cuda_forward  -> shr_tri_raster_fwd
 //   the same plus the face that made each pixel's depth       -> shr_tri_raster_owner_fwd (backward: mesh_depth_bwd.hip)
-//   mesh/pointTransformation.py:39-46 LinearBlendSkinning.forward and :84-99
-//   OthographicalProjection.forward                           -> shr_lbs_project
 //
 // The reference launches one single-thread block per face that walks the face's
 // pixel columns serially and CAS-loops a float min per pixel.  Here a wave takes
@@ -467,50 +465,6 @@ __global__ void zbuf_fill_kernel(uint4 *__restrict__ z, size_t n4, uint32_t key,
   if (blockIdx.x == 0 && (int)threadIdx.x < ntail) tail[threadIdx.x] = key;
 }
 
-// ---------------------------------------------------------------------------------------
-// Skinning + camera.  One thread per vertex and kLbsCrops samples: the samples' bone matrices are staged in LDS, a
-// vertex's skin entries (bone, weight * vertex) are read ONCE for the kLbsCrops samples (one sample per workgroup row
-// re-read the shared 0.5-MB table for every sample: 21 -> 1x us for 256 crops, round 3).  Visits only the non-zero
-// (bone, vertex) pairs of the reference's dense sum, in ascending bone order (association documented in DESIGN.md);
-// per sample the arithmetic is unchanged.
-constexpr int kLbsCrops = 4;
-__global__ void __launch_bounds__(256)
-lbs_project_kernel(const float *__restrict__ T, int B, int NB, int NV, const int *__restrict__ vstart,
-                   const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, int project,
-                   float cx, float cy, float fx, float fy, const float *__restrict__ rand_f,
-                   float4 *__restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) float s_T[];   // [kLbsCrops][NB][16]
-  const int b0 = blockIdx.y * kLbsCrops;
-  const int nb = min(kLbsCrops, B - b0);
-  for (int i = threadIdx.x; i < nb * NB * 16; i += blockDim.x) s_T[i] = T[(size_t)b0 * NB * 16 + i];
-  __syncthreads();
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= NV) return;
-  float acc[kLbsCrops][4];
-#pragma unroll
-  for (int c = 0; c < kLbsCrops; c++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) acc[c][r] = 0.f;
-  for (int e = vstart[v]; e < vstart[v + 1]; e++) {
-    const int bone = sbone[e];
-    const float4 q = swv[e];
-#pragma unroll
-    for (int c = 0; c < kLbsCrops; c++) {
-      if (c >= nb) continue;
-      lbs_add_entry(acc[c], s_T + (c * NB + bone) * 16, q);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < kLbsCrops; c++) {
-    if (c >= nb) continue;
-    const int b = b0 + c;
-    const float4 o = lbs_finish(acc[c], right_hand, project, cx, cy, fx, fy, rand_f != nullptr, rand_f ? rand_f[b] : 0.f);
-    // (written through: the vertices are read next by the rasterizer, left dirty they are flushed at the kernel's end)
-    const v4u_t t = {__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(out + (size_t)b * NV + v), "v"(t) : "memory");
-  }
-}
-
 }  // namespace shr
 
 using namespace shr;
@@ -672,18 +626,4 @@ extern "C" int shr_tri_raster_indexed_owner_fwd(const float *vertices, const int
     return SHR_ETOOLARGE;
   if ((((uintptr_t)depth | (uintptr_t)owner | (uintptr_t)vertices) & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(true, vertices, faces, B, F, NV, W, H, depth, (hipStream_t)stream, 0, 0.f, owner);
-}
-
-extern "C" int shr_lbs_project(const float *T, int B, int NB, int NV, const int32_t *skin_vertex_start,
-                               const int32_t *skin_bone, const float *skin_wv, int right_hand, int project, float cx,
-                               float cy, float fx, float fy, const float *rand_f, float *out, void *stream) {
-  if (B == 0 || NV == 0) return SHR_OK;
-  if (!T || !skin_vertex_start || !skin_bone || !skin_wv || !out || B < 0 || NB <= 0 || NV < 0) return SHR_EINVAL;
-  if ((((uintptr_t)skin_wv | (uintptr_t)out) & 15u) != 0) return SHR_EINVAL;
-  if (B > 65535 * kLbsCrops || NB > 160) return SHR_ETOOLARGE;   // (kLbsCrops x NB matrices of 64 bytes in LDS)
-  dim3 grid((unsigned)((NV + 255) / 256), (unsigned)((B + kLbsCrops - 1) / kLbsCrops));
-  hipLaunchKernelGGL(lbs_project_kernel, grid, dim3(256), (size_t)kLbsCrops * NB * 64, (hipStream_t)stream, T, B, NB, NV,
-                     skin_vertex_start, skin_bone, reinterpret_cast<const float4 *>(skin_wv), right_hand, project, cx,
-                     cy, fx, fy, rand_f, reinterpret_cast<float4 *>(out));
-  return (int)hipGetLastError();
 }

@@ -123,6 +123,52 @@ def test_no_experiment_switch_in_the_product_sources():
     assert not hits, hits
 
 
+def test_no_product_source_reads_the_environment():
+    """A kernel selected by an environment variable cannot be tested inside one process and is invisible to the caller
+    (SHR_MESH_LATTICE once chose between three kernels for DepthRender): switches go through shr_set_tuning."""
+    import glob
+    csrc = os.path.join(ROOT, "spherehand_amd", "csrc")
+    files = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert len(files) >= 20
+    hits = [(os.path.basename(f), n + 1) for f in files for n, l in enumerate(open(f)) if "getenv" in l]
+    assert not hits, hits
+
+
+def test_one_lattice_shape(tmp_path):
+    """mesh_lattice_kernel exists in one wave x face shape (16 x 32): SL = 1 / 2 x plain, SKIN, SKIN + POST; and the
+    skinning unit, like the units its kernels came from, uses no scratch memory."""
+    names = set(re.findall(r"^(_ZN3shr19mesh_lattice_kernel\w+):", _compile_asm("mesh_depth", tmp_path), re.M))
+    assert len(names) == 6, sorted(names)
+    assert {re.search(r"kernelI((?:L[bi]\d+E)+)", n).group(1) for n in names} == {
+        "Li%dELb%dELb%dE" % (sl, skin, post) for sl in (1, 2) for skin, post in ((0, 0), (1, 0), (1, 1))}
+    text = _compile_asm("lbs_project", tmp_path)
+    sizes = [int(v) for v in re.findall(r"; ScratchSize: (\d+)", text)]
+    assert len(sizes) == 2 and max(sizes) == 0, sizes
+
+
+def test_lattice_predicate_and_tuning_key():
+    """shr_mesh_render_one_launch for the hand (17 bones, 1 721 vertices, 3 382 faces) from 640: the lattice kernel takes
+    S = 128 / 64 / 32; not a lattice above 128 (S = 160: 160, S = 320: 640) nor a non-integer ratio (S = 256).
+    SHR_TUNE_MESH_LATTICE 0: never; values other than 0 and 1 are refused.  Host code only: no GPU."""
+    from spherehand_amd import _lib, ops
+    lib = _lib.lib()
+    want = {128: 1, 64: 1, 32: 1, 160: 0, 320: 0, 256: 0}
+    assert {S: lib.shr_mesh_render_one_launch(17, 1721, 3382, 640, S) for S in want} == want
+    assert {S: lib.shr_hand_synth_one_launch(17, 1721, 3382, 640, S, 21, 16) for S in want} == want
+    try:
+        ops.set_tuning(ops.TUNE_MESH_LATTICE, 0)
+        for S in want:
+            assert lib.shr_mesh_render_one_launch(17, 1721, 3382, 640, S) == 0, S
+            assert lib.shr_hand_synth_one_launch(17, 1721, 3382, 640, S, 21, 16) == 0, S
+        for bad in (-1, 2, 12):
+            with pytest.raises(RuntimeError):
+                ops.set_tuning(ops.TUNE_MESH_LATTICE, bad)
+        assert lib.shr_mesh_render_one_launch(17, 1721, 3382, 640, 64) == 0       # (a refused value changes nothing)
+    finally:
+        ops.set_tuning(ops.TUNE_MESH_LATTICE, 1)
+    assert lib.shr_mesh_render_one_launch(17, 1721, 3382, 640, 64) == 1
+
+
 @pytest.mark.parametrize("unit", ["tri_raster", "mesh_depth"])
 def test_face_setup_stays_in_registers(unit, tmp_path):
     """The sort of a face's vertices by x is three selects per coordinate; the compiler once turned them into loads from a

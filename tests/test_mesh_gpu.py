@@ -395,6 +395,81 @@ def test_mesh_render_one_launch_equals_skinning_then_raster(S):
             assert float((want < 100.0).float().mean()) > 0.02          # a hand is there
 
 
+@pytest.mark.parametrize("S", [128, 32])
+def test_lattice_kernel_equals_the_tile_kernel(S):
+    """SHR_TUNE_MESH_LATTICE 1 (default: one workgroup per crop, the lattice of sampled source pixels in LDS) against 0
+    (the tile kernel) at the two slot shapes, largest and smallest lattice: S = 128 (odd ratio 5, one slot, lattice 128)
+    and S = 32 (even ratio 20, two slots, lattice 64) -- the same pixels, the same arithmetic per pixel, integer minima:
+    bit for bit.  The same for shr_mesh_render_fwd: the fused skinning launch against two launches through the
+    workspace."""
+    from spherehand_amd import hand_model, ops
+    from spherehand_amd.joint_angle import sample_poses
+    from spherehand_amd.kinematicsTransformation import HandTransformationMat
+    from spherehand_amd.render import DepthRender
+    mesh = hand_model.load_mesh()
+    dr = DepthRender(mesh, S).cuda()
+    fk = HandTransformationMat([b["offset_matrix"].astype(np.float32) for b in mesh["bones"]]).cuda()
+    lbs, faces = dr.lbs, dr.rasterizer.faces_i32
+    with torch.no_grad():
+        T = fk(sample_poses(3, seed=40 + S).cuda()).contiguous()
+        verts = lbs(T, dr.camera, None).contiguous()
+    render = lambda: ops.mesh_render_fwd(T, lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, lbs.right_hand, dr.camera, None,
+                                         faces, S, 640, 100.0)
+    out = {}
+    try:
+        for mode in (0, 1):
+            ops.set_tuning(ops.TUNE_MESH_LATTICE, mode)
+            out[mode] = (ops.mesh_depth_fwd(verts, faces, S, 640, 100.0), render())
+    finally:
+        ops.set_tuning(ops.TUNE_MESH_LATTICE, 1)
+    assert torch.equal(out[1][0], out[0][0])
+    assert torch.equal(out[1][1], out[0][1])
+    assert 0.02 < (out[1][0] < 100).float().mean().item() < 0.6
+    assert not torch.equal(out[1][0][0], out[1][0][1]) and not torch.equal(out[1][0][1], out[1][0][2])     # distinct poses
+
+
+def test_synthesizer_without_the_lattice_kernel():
+    """SHR_TUNE_MESH_LATTICE 0 at S = 64: shr_mesh_render_post_fwd takes its three launches (skinning, tile kernel, the
+    scale-and-noise tail) and returns the bits of the one-launch route from a copy of the same rng_state, advancing the
+    call counter alike; ops.hand_synth reports that the one-launch kernel does not apply (None) instead of raising, and
+    the module goes on through the three-launch path with the same outputs."""
+    from spherehand_amd import hand_model, ops
+    from spherehand_amd.joint_angle import sample_poses
+    from spherehand_amd.util_modules import HandSynthesizer
+    S, B = 64, 3
+    syn = HandSynthesizer(hand_model.load_mesh(), S, 16, 1.0, 0.01).cuda()
+    pose = sample_poses(B, seed=14).cuda()
+    torch.manual_seed(99)
+    syn.reseed(device=pose.device)
+    fk, dr, nz = syn.hand_skeleton_transform, syn.dm_render, syn.depth_noiser
+    lbs, faces = dr.lbs, dr.rasterizer.faces_i32
+    state0 = syn.rng_state.clone()
+    T, draws = ops.synth_pose(pose, fk.offset, fk.offset_inv, state0, syn.rand_scale.rand_scale)
+    post = lambda state: ops.mesh_render_post(T, lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, lbs.right_hand, dr.camera,
+                                              draws[3], faces, S, syn.depth_scale, draws[4:6], nz.sigma_x, nz.sigma_z, state)
+    synth = lambda state: ops.hand_synth(pose, fk.offset, fk.offset_inv, state, syn.rand_scale.rand_scale, lbs, faces,
+                                         dr.camera, S, syn.depth_scale, True, nz.sigma_x, nz.sigma_z, None)
+    s1, s3 = state0.clone(), state0.clone()
+    one = post(s1)
+    whole = syn(pose)
+    assert synth(state0.clone()) is not None
+    syn.reseed(device=pose.device)
+    try:
+        ops.set_tuning(ops.TUNE_MESH_LATTICE, 0)
+        three = post(s3)
+        none = synth(state0.clone())
+        whole_off = syn(pose)
+    finally:
+        ops.set_tuning(ops.TUNE_MESH_LATTICE, 1)
+    assert none is None
+    assert torch.equal(one, three)
+    assert torch.equal(s1, s3) and int(s1[1]) == int(state0[1]) + 1 and int(s1[2]) == 0
+    for a, b in zip(whole, whole_off):
+        assert torch.equal(a, b)
+    assert torch.equal(whole[0], one)                       # (the module's depth is that launch's, on the same draws)
+    assert (one != one.flip(0)).any() and float((one < 0.99).float().mean()) > 0.02       # distinct poses, a hand is there
+
+
 def test_shared_reciprocal_divisions_equal_the_plain_ones():
     """The triangle kernels' pixel depth (tri_face.h tri_pixel_depth: three divisions by the weights' sum share one refined
     reciprocal, the three by the corners' z bring theirs from the face's set-up) against the reference's seven plain

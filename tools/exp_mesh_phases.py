@@ -1,4 +1,5 @@
-"""Where `mesh_depth_kernel` / `mesh_lattice_kernel` (SHR_MESH_LATTICE=0 for the former) spend their time: s_memtime stamps of every wave at the phase boundaries (mesh_depth.hip
+"""Where `mesh_depth_kernel` / `mesh_lattice_kernel` (TILE=1 in the environment for the former: SHR_TUNE_MESH_LATTICE 0)
+spend their time: s_memtime stamps of every wave at the phase boundaries (mesh_depth.hip
 built alone with -DMESH_TL into tools/libmesh_tl.so; the product build carries no stamps).
     python tools/exp_mesh_phases.py build     (anywhere)
     python tools/exp_mesh_phases.py           (GPU box: prints medians over the 256 workgroups of one launch, in us)
@@ -14,7 +15,8 @@ def build():
     from spherehand_amd import build as b
     subprocess.check_call([b.HIPCC] + list(b.FLAGS) + ["-DMESH_TL"] + os.environ.get("XFLAGS", "").split() + ["-I", os.path.join(ROOT, "include"),
                            "-I", os.path.join(b.PKG, "csrc"), "-o", SO, os.path.join(b.PKG, "csrc", "mesh_depth.hip"),
-                           os.path.join(b.PKG, "csrc", "tri_raster.hip")])      # (tri_raster.hip: shr_lbs_project, the fused entry's fallback)
+                           os.path.join(b.PKG, "csrc", "tri_raster.hip"),       # (the band kernel's resize entry and shr_lbs_project:
+                           os.path.join(b.PKG, "csrc", "lbs_project.hip")])     #  the entries' fallbacks)
     print(SO)
 
 
@@ -31,6 +33,8 @@ def main():
     lib = ctypes.CDLL(SO)
     lib.shr_mesh_depth_fwd.argtypes = [vp, vp, i, i, i, i, i, f, vp, vp]
     lib.shr_mesh_debug_timeline.argtypes = [vp]
+    if os.environ.get("TILE"):           # the tile kernel: what shr_set_tuning(SHR_TUNE_MESH_LATTICE, 0) calls -- shr_set_tuning
+        assert lib._ZN3shr16mesh_set_latticeEi(0) == 0      # itself (sphere_raster.hip) is not in this library
     ghz = float(os.environ.get("SHADER_GHZ", "2.4"))
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):

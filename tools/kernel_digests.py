@@ -4,8 +4,10 @@ listing two trees are compared by when a change must not move an instruction (no
 device code, of tools/tri_digests.py for outputs; docs/EXPERIMENTS.md, part K).
 
 A kernel's body runs from its label to the end of its `.amdhsa_kernel` descriptor block.  Blank lines and lines that are
-only a comment (`;`-only, `;;#ASMSTART` / `;;#ASMEND` among them) are dropped; instructions, labels, directives and the
-descriptor all count.  One line per kernel: name, instruction count, digest.
+only a comment (`;`-only, `;;#ASMSTART` / `;;#ASMEND` among them) are dropped, and so is a line's trailing comment; instructions, labels, directives and the
+descriptor all count; the kernel's own symbol is hashed as a placeholder and its local labels without the kernel's
+ordinal in the unit (a re-parameterised kernel, or one whose neighbours moved to another unit, keeps its digest).
+One line per kernel: name, instruction count, digest.
 
     python tools/kernel_digests.py sphere_raster data_to_model > listing.txt      (in each tree; then `diff`)"""
 import hashlib
@@ -39,7 +41,12 @@ def kernels(lines):
             continue
         kept = [l.split(" ; @")[0] if k == 0 else l for k, l in enumerate(body[:ends[0] + 1])
                 if l.strip() and not l.strip().startswith(";")]
-        yield lines[i].split(":")[0], kept
+        name = lines[i].split(":")[0]
+        # the kernel's own symbol (its encoding after `_Z`: labels, descriptor, the names of its static LDS) by a fixed
+        # placeholder, its ordinal in the unit out of its local labels (.LBB<ordinal>_<n>, .Lfunc_end<ordinal>) and no
+        # trailing notes (they name labels too), so that a kernel whose template parameters or whose neighbours in the
+        # unit change -- and nothing else -- keeps its digest
+        yield name, [re.sub(r"\.(LBB|Lfunc_end)\d+", r".\1", l.split(";")[0].rstrip().replace(name[2:], "KERNEL")) for l in kept]
 
 
 for unit in sys.argv[1:] or ["sphere_raster"]:
