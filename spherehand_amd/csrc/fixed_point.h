@@ -13,7 +13,13 @@
 // (three points x three coordinates; a zero term is skipped by the sums), pid[k] the accumulator point of g[k];
 // points(): the accumulator points of a crop; kThreads, kBlockPix: the threads and pixels of a workgroup; kRuns: a
 // thread's taps come in runs of one point triple (the sums merge a run in registers first).
+//
+// Host: fixed_point_bwd launches the four passes; with_runs picks a walker's RUNS instantiation from the point count, so
+// that an entry writes its call of fixed_point_bwd once.  What the walkers share about one face at one owned pixel (the
+// checked gather, the fp32 decisions and fp64 weights, the weights' chain to x, y) is tri_tap.h's.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -200,4 +206,12 @@ static int fixed_point_bwd(const Taps &taps, int B, int NP, size_t npix, int fix
     hipLaunchKernelGGL(mesh_bwd_finish_kernel<STRIDE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, acc, crop_max, B,
                        NP, fix_bits, out);
   return (int)hipGetLastError();
+}
+
+// A walker with a RUNS parameter takes it from the point count: fn(std::bool_constant<RUNS>{}) is called once, RUNS = the
+// accumulators do not fit LDS.  fn is a generic lambda that names the instantiation (Taps<decltype(runs)::value>) and calls
+// fixed_point_bwd -- the call and its arguments are written once.
+template <typename Fn>
+static int with_runs(long long NP, Fn fn) {
+  return NP <= shr::kBwdLdsVerts ? fn(std::false_type{}) : fn(std::true_type{});
 }

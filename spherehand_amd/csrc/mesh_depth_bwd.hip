@@ -12,68 +12,32 @@
 //     d zp / d z_k = zp^2 (c_k / s) / z_k^2,   d zp / d c_k = -zp^2 (1 / z_k - 1 / zp) / s,
 //     d w_k = (d n_k - w_k d den) / den,
 // a weight clamped strictly outside [0, 1] contributing nothing (torch's clamp passes at 0 and 1).  The clamp decisions
-// are the forward's fp32 arithmetic, the derivatives are evaluated in fp64.
+// are the forward's fp32 arithmetic, the derivatives are evaluated in fp64.  tri_tap.h states the part every backward of
+// the triangle family shares (owned_tap: decisions and weights; weight_chain: d w_k -> the corners' x, y; tri_corners: the
+// checked gather of PixelTaps); tap_terms below adds the depth's q, zp and z terms.
 //
 // Sums: fixed_point.h -- 64-bit fixed point in a per-crop unit computed on the device, bitwise reproducible and
 // independent of the batch and of the launch shape.
 #include "fixed_point.h"
-#include "tri_face.h"
+#include "tri_tap.h"
 
 namespace shr {
 
 // One tap's nine partial derivatives, times its upstream gradient: corner k of the face fv (x, y, z of its corners in
 // their ORIGINAL order) gets (d/du, d/dv, d/dz) in g[k][0..2].  (A degenerate face's NaN terms are dropped by the sums.)
+// tri_tap.h's owned_tap gives the weights; the depth's own part is q = 1 / zp, the z terms and the weights' coefficient.
 __device__ __forceinline__ void tap_terms(const float (&fv)[9], int xi, int yi, double gw, double (&g)[3][3]) {
-  // the forward's sort by x and fp32 weights (tri_face.h): the clamp decisions
-  float p[3][3], fi[9], w32[3], c32[3];
-  int order[3];
-  face_sort(fv, p, order);
-  face_matrix(p, fi);
-  pixel_weights(fi, (float)xi, (float)yi, w32, c32);
-  bool pass[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) pass[k] = w32[k] >= 0.f && w32[k] <= 1.f;
-  // fp64 derivatives
-  double x[3], y[3], z[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) { x[a] = p[a][0]; y[a] = p[a][1]; z[a] = p[a][2]; }
-  const double px = xi, py = yi;
-  const double den = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0]);
-  double c[3], w[3], s = 0.0;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int b = (a + 1) % 3, e = (a + 2) % 3;
-    w[a] = ((x[b] - px) * (y[e] - py) - (x[e] - px) * (y[b] - py)) / den;
-    c[a] = pass[a] ? w[a] : (double)c32[a];
-    s += c[a];
-  }
+  OwnedTap T;
+  owned_tap(fv, xi, yi, T);
   double q = 0.0;
 #pragma unroll
-  for (int a = 0; a < 3; a++) q += c[a] / s / z[a];
+  for (int a = 0; a < 3; a++) q += T.c[a] / T.s / T.z[a];
   const double zp = 1.0 / q, zp2 = zp * zp;
   double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  double kw = 0.0;
 #pragma unroll
-  for (int a = 0; a < 3; a++) {
-    G[a][2] = gw * zp2 * (c[a] / s) / (z[a] * z[a]);
-    if (!pass[a]) continue;
-    const double k = -gw * zp2 * (1.0 / z[a] - q) / s / den;
-    const int b = (a + 1) % 3, e = (a + 2) % 3;
-    G[b][0] += k * (y[e] - py);
-    G[b][1] -= k * (x[e] - px);
-    G[e][0] -= k * (y[b] - py);
-    G[e][1] += k * (x[b] - px);
-    kw += k * w[a];
-  }
-  // - sum_a k_a w_a d den
-  G[0][0] -= kw * (y[1] - y[2]); G[0][1] -= kw * (x[2] - x[1]);
-  G[1][0] -= kw * (y[2] - y[0]); G[1][1] -= kw * (x[0] - x[2]);
-  G[2][0] -= kw * (y[0] - y[1]); G[2][1] -= kw * (x[1] - x[0]);
-  // sorted corner a is original corner order[a]
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-#pragma unroll
-    for (int d = 0; d < 3; d++) g[k][d] = (order[0] == k) ? G[0][d] : ((order[1] == k) ? G[1][d] : G[2][d]);
+  for (int a = 0; a < 3; a++) G[a][2] = gw * zp2 * (T.c[a] / T.s) / (T.z[a] * T.z[a]);
+  weight_chain(T, [&](int a) { return -gw * zp2 * (1.0 / T.z[a] - q) / T.s / T.den; }, G);
+  tap_unsort(G, T.order, g);
 }
 // the same for face f of an indexed mesh; vid[k] the vertex of corner k
 __device__ __forceinline__ void tap_terms(const float4 *__restrict__ verts, const int *__restrict__ faces, int f, int xi,
@@ -156,21 +120,15 @@ struct PixelTaps {
       const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
       float fv[9];
       int pid[3];
-      bool ok = true;
+      if (INDEXED) {
+        if (!tri_corners(reinterpret_cast<const float4 *>(src) + (size_t)b * NV, faces, NV, F, f, fv, pid)) continue;
+      } else {
+        const float *fp = src + ((size_t)b * F + f) * 9;
 #pragma unroll
-      for (int c = 0; c < 3; c++) {
-        if (INDEXED) {
-          pid[c] = faces[f * 3 + c];
-          ok = ok && (unsigned)pid[c] < (unsigned)NV;
-          const float4 v = reinterpret_cast<const float4 *>(src)[(size_t)b * NV + (ok ? pid[c] : 0)];
-          fv[3 * c] = v.x; fv[3 * c + 1] = v.y; fv[3 * c + 2] = v.z;
-        } else {
-          pid[c] = 3 * f + c;
-          const float *fp = src + ((size_t)b * F + f) * 9 + 3 * c;
-          fv[3 * c] = fp[0]; fv[3 * c + 1] = fp[1]; fv[3 * c + 2] = fp[2];
-        }
+        for (int c = 0; c < 3; c++) pid[c] = 3 * f + c;
+#pragma unroll
+        for (int c = 0; c < 9; c++) fv[c] = fp[c];
       }
-      if (!ok) continue;
       double g[3][3];
       tap_terms(fv, x, y, (double)gd, g);
       fn(g, pid);
@@ -212,11 +170,10 @@ extern "C" int shr_tri_raster_bwd(const float *face_vertices, const int32_t *own
     return SHR_EINVAL;
   if (((uintptr_t)workspace & 15u) != 0) return SHR_EINVAL;
   if (B > 65535 || W > 65535 || H > 65535 || 3LL * F * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
-  if (3 * F <= kBwdLdsVerts)
-    return fixed_point_bwd<3>(PixelTaps<false, false>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
-                              (size_t)W * H, fix_term_bits(3, W, H), grad_face_vertices, workspace, (hipStream_t)stream);
-  return fixed_point_bwd<3>(PixelTaps<false, true>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B, 3 * F,
-                            (size_t)W * H, fix_term_bits(3, W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+  return with_runs(3 * F, [&](auto runs) {
+    return fixed_point_bwd<3>(PixelTaps<false, decltype(runs)::value>{face_vertices, nullptr, owner, grad_depth, F, 0, W, H}, B,
+                              3 * F, (size_t)W * H, fix_term_bits(3, W, H), grad_face_vertices, workspace, (hipStream_t)stream);
+  });
 }
 
 extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *faces, const int32_t *owner,
@@ -229,9 +186,8 @@ extern "C" int shr_tri_raster_indexed_bwd(const float *vertices, const int32_t *
     return SHR_EINVAL;
   if ((((uintptr_t)vertices | (uintptr_t)grad_vertices | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   if (B > 65535 || W > 65535 || H > 65535 || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
-  if (NV <= kBwdLdsVerts)
-    return fixed_point_bwd<4>(PixelTaps<true, false>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
-                              fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
-  return fixed_point_bwd<4>(PixelTaps<true, true>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV, (size_t)W * H,
-                            fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
+  return with_runs(NV, [&](auto runs) {
+    return fixed_point_bwd<4>(PixelTaps<true, decltype(runs)::value>{vertices, faces, owner, grad_depth, F, NV, W, H}, B, NV,
+                              (size_t)W * H, fix_term_bits(3, W, H), grad_vertices, workspace, (hipStream_t)stream);
+  });
 }

@@ -6,7 +6,8 @@
 // x, y and carries a gradient to the edges' endpoints.  ONE pass: the single-plane entries are its C = 1 case.
 //
 // Every kernel here evaluates ONE restatement of a pair's decision, pair_blend: the front pixel, the owner's first
-// qualifying silhouette edge (face_sort of tri_face.h for the drawn test of the owner and of the face across), and the
+// qualifying silhouette edge (tri_tap.h's checked gather of a face's corners, tri_face.h's face_sort for the drawn test of the
+// owner and of the face across), and the
 // crossing s.  It depends on depth, owner, vertices, faces and edges only, never on the values: a kernel takes it ONCE per
 // pair and applies it to all channels.  fp32 throughout (-ffp-contract=off), per channel in one order: the forward, the
 // value gradient and the vertex terms take the same decisions bit for bit, and plane ch of the output and of the value
@@ -16,7 +17,7 @@
 //   grad values   the same records for the gather of the upstream gradient (no atomics)
 //   grad vertex   fixed_point.h's passes over AATaps: each pair once, at its first pixel -- two points x (x, y) per pair
 #include "fixed_point.h"
-#include "tri_face.h"
+#include "tri_tap.h"
 
 namespace shr {
 
@@ -36,35 +37,18 @@ struct PairBlend {
 };
 
 // face_sort's drawn test on corners already loaded: (x, y, z) of the face's corners in their original order
-__device__ __forceinline__ bool aa_sorts(const float4 (&c)[3]) {
-  float fv[9];
-#pragma unroll
-  for (int k = 0; k < 3; k++) { fv[3 * k] = c[k].x; fv[3 * k + 1] = c[k].y; fv[3 * k + 2] = c[k].z; }
+__device__ __forceinline__ bool aa_sorts(const float (&fv)[9]) {
   float p[3][3];
   int order[3];
   return face_sort(fv, p, order);
 }
 
-// the corners of face f of crop bi (false: f or one of its vertex ids out of range); id[k]: the vertex of corner k
-__device__ __forceinline__ bool aa_corners(const AAArgs &A, int bi, int f, int (&id)[3], float4 (&c)[3]) {
-  if ((unsigned)f >= (unsigned)A.F) return false;
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    id[k] = A.faces[f * 3 + k];
-    ok = ok && (unsigned)id[k] < (unsigned)A.NV;
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int k = 0; k < 3; k++) c[k] = A.verts[(size_t)bi * A.NV + id[k]];
-  return true;
-}
-
-// face f of crop bi is drawn: its ids are in range and face_sort accepts it (front-facing, x0 != x2)
+// face f of crop bi is drawn: its ids are in range (tri_tap.h's checked gather) and face_sort accepts it (front-facing,
+// x0 != x2)
 __device__ __forceinline__ bool aa_drawn(const AAArgs &A, int bi, int f) {
   int id[3];
-  float4 c[3];
-  return aa_corners(A, bi, f, id, c) && aa_sorts(c);
+  float fv[9];
+  return tri_corners(A.verts + (size_t)bi * A.NV, A.faces, A.NV, A.F, f, fv, id) && aa_sorts(fv);
 }
 
 // The pair (p, q) of crop bi, p = (x, y), q = p + (1, 0) (VERT false) or p + (0, 1) (VERT true), both inside the image,
@@ -79,17 +63,17 @@ __device__ __forceinline__ PairBlend pair_blend(const AAArgs &A, int bi, int x, 
   const bool fp = op < 0 ? false : (oq < 0 ? true : !(A.depth[base + iq] < A.depth[base + ip]));   // equal bits: p
   const int t = fp ? op : oq;
   int id[3];
-  float4 c[3];
-  if (!aa_corners(A, bi, t, id, c)) return r;
+  float fv[9];   // (x, y, z of corner k at 3 k)
+  if (!tri_corners(A.verts + (size_t)bi * A.NV, A.faces, A.NV, A.F, t, fv, id)) return r;
   const float sigma = fp ? 1.f : -1.f;
   const float uf = (float)(VERT ? (fp ? y : y + 1) : (fp ? x : x + 1));   // the front pixel along the axis
   const float row = (float)(VERT ? x : y);                               // the pair's row (column) across it
   int t_drawn = -1;                                                       // -1: not yet tested
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    const float4 pa = c[k], pb = c[k == 2 ? 0 : k + 1];
-    const float ua = VERT ? pa.y : pa.x, wa = VERT ? pa.x : pa.y;   // along the axis, across it
-    const float ub = VERT ? pb.y : pb.x, wb = VERT ? pb.x : pb.y;
+    const int ka = 3 * k, kb = k == 2 ? 0 : 3 * k + 3;
+    const float ua = fv[ka + (VERT ? 1 : 0)], wa = fv[ka + (VERT ? 0 : 1)];   // along the axis, across it
+    const float ub = fv[kb + (VERT ? 1 : 0)], wb = fv[kb + (VERT ? 0 : 1)];
     const float du = ub - ua, dw = wb - wa;
     const bool steep = VERT ? fabsf(dw) > fabsf(du) : fabsf(dw) >= fabsf(du);
     if (!steep || dw == 0.f) continue;
@@ -97,7 +81,7 @@ __device__ __forceinline__ PairBlend pair_blend(const AAArgs &A, int bi, int x, 
     const float uc = ua + ((row - wa) * du) / dw;
     const float s = sigma * (uc - uf);
     if (!(s >= 0.f && s <= 1.f)) continue;
-    if (t_drawn < 0) t_drawn = aa_sorts(c) ? 1 : 0;
+    if (t_drawn < 0) t_drawn = aa_sorts(fv) ? 1 : 0;
     if (!t_drawn) return r;                                 // an undrawn face has no silhouette edge
     const int n = A.edges[t * 3 + k];
     if ((unsigned)n < (unsigned)A.F && aa_drawn(A, bi, n)) continue;   // shared with a drawn face: not a silhouette

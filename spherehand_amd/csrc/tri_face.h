@@ -1,5 +1,5 @@
 // tri_face.h -- the reference triangle kernel's per-face and per-pixel arithmetic, restated once for every mesh kernel
-// (tri_raster.hip, mesh_depth.hip, mesh_depth_bwd.hip; capi.hip's division self-test).
+// (tri_raster.hip, mesh_depth.hip, and through tri_tap.h the backwards; capi.hip's division self-test).
 //
 // mesh/cuda_kernel/depth_rasterization_cuda_kernel.cu:25-110, operator for operator: fp32, one rounding per written
 // operator (-ffp-contract=off), IEEE division -- the depth bits are the reference's.  The kernels compose these pieces

@@ -6,13 +6,14 @@
 //   forward        one thread per pixel, 64 x 4 tiles: the owner's set-up in registers, the three weights kept while the
 //                  channels loop; every channel plane is written coalesced.  fp32, one rounding per written operator.
 //   grad vertex    fixed_point.h's passes over InterpVertexTaps: nine terms per owned pixel, mesh_depth_bwd.hip's rule
-//                  (decisions in fp32, derivative in fp64; a weight clamped strictly outside [0, 1] is a constant)
+//                  (decisions in fp32, derivative in fp64; a weight clamped strictly outside [0, 1] is a constant) through
+//                  the same statements: tri_tap.h's tri_corners, owned_tap and weight_chain
 //   grad attr      C terms per corner: the channels go in groups of three, one group = the three coordinates of
 //                  fixed_point.h's accumulator points, "crop" b * G + j for group j of crop b (G = ceil(C / 3)).  One
 //                  walk over all channels finds the crop's largest term and gives every group of the crop that unit;
 //                  fixed_point.h's sum kernel then runs per group, and a conversion of its own writes [B,NV,C].
 #include "fixed_point.h"
-#include "tri_face.h"
+#include "tri_tap.h"
 
 namespace shr {
 
@@ -27,27 +28,9 @@ struct InterpArgs {
   int NV, F, W, H, C;
 };
 
-// face t of crop bi: its corners (x, y, z in the faces' own order) and vertex ids; false: t or an id out of range
-__device__ __forceinline__ bool interp_corners(const InterpArgs &A, int bi, int t, float (&fv)[9], int (&id)[3]) {
-  if ((unsigned)t >= (unsigned)A.F) return false;
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    id[k] = A.faces[t * 3 + k];
-    ok = ok && (unsigned)id[k] < (unsigned)A.NV;
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float4 v = A.verts[(size_t)bi * A.NV + id[k]];
-    fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
-  }
-  return true;
-}
-// sorted corner a is corner order[a]: its vertex id, without dynamic indexing
-__device__ __forceinline__ void interp_sorted_ids(const int (&id)[3], const int (&order)[3], int (&sid)[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; a++) sid[a] = (order[a] == 0) ? id[0] : ((order[a] == 1) ? id[1] : id[2]);
+// face t of crop bi: tri_tap.h's checked gather
+__device__ __forceinline__ bool interp_face(const InterpArgs &A, int bi, int t, float (&fv)[9], int (&id)[3]) {
+  return tri_corners(A.verts + (size_t)bi * A.NV, A.faces, A.NV, A.F, t, fv, id);
 }
 
 constexpr int kIntX = 64, kIntY = 4;   // a workgroup: 64 x 4 pixels, one wave per row segment
@@ -63,7 +46,7 @@ interp_fwd_kernel(InterpArgs A, float *__restrict__ out) {
   const int t = A.owner[(size_t)bi * npix + i];
   float fv[9], wh[3] = {0.f, 0.f, 0.f};
   int id[3], sid[3] = {0, 0, 0};
-  bool live = interp_corners(A, bi, t, fv, id);
+  bool live = interp_face(A, bi, t, fv, id);
   if (live) {
     float p[3][3], fi[9], w[3], c[3];
     int order[3];
@@ -74,7 +57,7 @@ interp_fwd_kernel(InterpArgs A, float *__restrict__ out) {
     if (live) {
 #pragma unroll
       for (int k = 0; k < 3; k++) wh[k] = c[k] / s;
-      interp_sorted_ids(id, order, sid);
+      tap_sorted_ids(id, order, sid);
     }
   }
   if (!live) {
@@ -98,42 +81,21 @@ interp_fwd_kernel(InterpArgs A, float *__restrict__ out) {
   }
 }
 
-// One owned pixel for the backward: the forward's fp32 decisions and the fp64 weights (mesh_depth_bwd.hip's tap_terms
-// with sum_k g_k c_k / s in place of the depth).  Everything is over the SORTED corners; sid[a] their vertex ids.
-struct InterpTap {
-  double x[3], y[3], w[3], wh[3], s, den;   // corners, unclamped weights, c / s, sum of the c, 2 x signed area
-  bool pass[3];                             // the fp32 weight lies inside [0, 1]
+// One owned pixel for the backward: tri_tap.h's owned_tap (the forward's fp32 decisions, the fp64 weights over the SORTED
+// corners), the forward's liveness rule, the normalised weights wh = c / s and the sorted corners' vertex ids.
+struct InterpTap : OwnedTap {
+  double wh[3];
   int sid[3];
 };
 __device__ __forceinline__ bool interp_tap(const InterpArgs &A, int bi, int t, int xi, int yi, InterpTap &T) {
   float fv[9];
   int id[3];
-  if (!interp_corners(A, bi, t, fv, id)) return false;
-  float p[3][3], fi[9], w32[3], c32[3];
-  int order[3];
-  face_sort(fv, p, order);
-  face_matrix(p, fi);
-  const float s32 = pixel_weights(fi, (float)xi, (float)yi, w32, c32);
+  if (!interp_face(A, bi, t, fv, id)) return false;
+  const float s32 = owned_tap(fv, xi, yi, T);
   if (!(s32 > 0.f && s32 <= 3.0e38f)) return false;   // the forward wrote a constant 0
-  interp_sorted_ids(id, order, T.sid);
+  tap_sorted_ids(id, T.order, T.sid);
 #pragma unroll
-  for (int a = 0; a < 3; a++) {
-    T.pass[a] = w32[a] >= 0.f && w32[a] <= 1.f;
-    T.x[a] = p[a][0]; T.y[a] = p[a][1];
-  }
-  const double px = xi, py = yi;
-  T.den = (T.x[1] - T.x[0]) * (T.y[2] - T.y[0]) - (T.x[2] - T.x[0]) * (T.y[1] - T.y[0]);
-  double c[3];
-  T.s = 0.0;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int b = (a + 1) % 3, e = (a + 2) % 3;
-    T.w[a] = ((T.x[b] - px) * (T.y[e] - py) - (T.x[e] - px) * (T.y[b] - py)) / T.den;
-    c[a] = T.pass[a] ? T.w[a] : (double)c32[a];
-    T.s += c[a];
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) T.wh[a] = c[a] / T.s;
+  for (int a = 0; a < 3; a++) T.wh[a] = T.c[a] / T.s;
   return true;
 }
 
@@ -168,23 +130,8 @@ struct InterpVertexTaps {
         gk[0] += g * (double)a0[ch]; gk[1] += g * (double)a1[ch]; gk[2] += g * (double)a2[ch];
       }
       const double gbar = (gk[0] * T.wh[0] + gk[1] * T.wh[1]) + gk[2] * T.wh[2];
-      const double px = xi, py = yi;
       double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-      double kw = 0.0;
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        if (!T.pass[a]) continue;
-        const double kk = (gk[a] - gbar) / T.s / T.den;
-        const int b = (a + 1) % 3, e = (a + 2) % 3;
-        G[b][0] += kk * (T.y[e] - py);
-        G[b][1] -= kk * (T.x[e] - px);
-        G[e][0] -= kk * (T.y[b] - py);
-        G[e][1] += kk * (T.x[b] - px);
-        kw += kk * T.w[a];
-      }
-      G[0][0] -= kw * (T.y[1] - T.y[2]); G[0][1] -= kw * (T.x[2] - T.x[1]);
-      G[1][0] -= kw * (T.y[2] - T.y[0]); G[1][1] -= kw * (T.x[0] - T.x[2]);
-      G[2][0] -= kw * (T.y[0] - T.y[1]); G[2][1] -= kw * (T.x[1] - T.x[0]);
+      weight_chain(T, [&](int a) { return (gk[a] - gbar) / T.s / T.den; }, G);
       fn(G, T.sid);
     }
   }
@@ -364,12 +311,13 @@ extern "C" int shr_tri_interp_bwd(const int32_t *owner, const float *vertices, c
   const size_t npix = (size_t)W * H;
   char *ws = reinterpret_cast<char *>(workspace);
   if (grad_vertices) {
-    const int e = NV <= kBwdLdsVerts
-                      ? fixed_point_bwd<4>(InterpVertexTaps<false>{A, grad_out}, B, NV, npix, bits, grad_vertices, ws, s)
-                      : fixed_point_bwd<4>(InterpVertexTaps<true>{A, grad_out}, B, NV, npix, bits, grad_vertices, ws, s);
+    const int e = with_runs(NV, [&](auto runs) {
+      return fixed_point_bwd<4>(InterpVertexTaps<decltype(runs)::value>{A, grad_out}, B, NV, npix, bits, grad_vertices, ws, s);
+    });
     if (e != 0 || !grad_attr) return e;
     ws += fix_workspace_bytes(B, NV);
   }
-  return NV <= kBwdLdsVerts ? interp_attr_bwd<false>(A, grad_out, B, bits, grad_attr, ws, s)
-                            : interp_attr_bwd<true>(A, grad_out, B, bits, grad_attr, ws, s);
+  return with_runs(NV, [&](auto runs) {
+    return interp_attr_bwd<decltype(runs)::value>(A, grad_out, B, bits, grad_attr, ws, s);
+  });
 }

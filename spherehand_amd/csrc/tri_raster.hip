@@ -588,12 +588,20 @@ int shr::tri_band_resize(const float *vertices, const int *faces, int B, int NV,
   return tri_raster_common(true, vertices, faces, B, F, NV, src_size, src_size, depth, s, S, clamp_max);
 }
 
+// The four forward entries' sizes, after an entry's own null-pointer line and before its alignment line (the order of
+// the return codes: SHR_EINVAL for a size that is no size, then SHR_ETOOLARGE, then the alignment's SHR_EINVAL).
+static int tri_raster_limits(int B, int F, int W, int H) {
+  if (B < 0 || F < 0 || W <= 0 || H <= 0) return SHR_EINVAL;
+  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
+    return SHR_ETOOLARGE;   // (pixel coordinates travel in 16 bits)
+  return SHR_OK;
+}
+
 extern "C" int shr_tri_raster_fwd(const float *face_vertices, int B, int F, int W, int H, float *depth,
                                   void *stream) {
   if (B == 0) return SHR_OK;
-  if (!depth || (!face_vertices && F > 0) || B < 0 || F < 0 || W <= 0 || H <= 0) return SHR_EINVAL;
-  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
-    return SHR_ETOOLARGE;   // (pixel coordinates travel in 16 bits)
+  if (!depth || (!face_vertices && F > 0)) return SHR_EINVAL;
+  if (const int rc = tri_raster_limits(B, F, W, H)) return rc;
   if (((uintptr_t)depth & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(false, face_vertices, nullptr, B, F, 0, W, H, depth, (hipStream_t)stream);
 }
@@ -601,9 +609,8 @@ extern "C" int shr_tri_raster_fwd(const float *face_vertices, int B, int F, int 
 extern "C" int shr_tri_raster_indexed_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int W,
                                           int H, float *depth, void *stream) {
   if (B == 0) return SHR_OK;
-  if (!depth || !vertices || (!faces && F > 0) || B < 0 || F < 0 || NV <= 0 || W <= 0 || H <= 0) return SHR_EINVAL;
-  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
-    return SHR_ETOOLARGE;
+  if (!depth || !vertices || (!faces && F > 0) || NV <= 0) return SHR_EINVAL;
+  if (const int rc = tri_raster_limits(B, F, W, H)) return rc;
   if ((((uintptr_t)depth | (uintptr_t)vertices) & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(true, vertices, faces, B, F, NV, W, H, depth, (hipStream_t)stream);
 }
@@ -611,9 +618,8 @@ extern "C" int shr_tri_raster_indexed_fwd(const float *vertices, const int32_t *
 extern "C" int shr_tri_raster_owner_fwd(const float *face_vertices, int B, int F, int W, int H, float *depth, int32_t *owner,
                                         void *stream) {
   if (B == 0) return SHR_OK;
-  if (!depth || !owner || (!face_vertices && F > 0) || B < 0 || F < 0 || W <= 0 || H <= 0) return SHR_EINVAL;
-  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
-    return SHR_ETOOLARGE;
+  if (!depth || !owner || (!face_vertices && F > 0)) return SHR_EINVAL;
+  if (const int rc = tri_raster_limits(B, F, W, H)) return rc;
   if ((((uintptr_t)depth | (uintptr_t)owner) & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(false, face_vertices, nullptr, B, F, 0, W, H, depth, (hipStream_t)stream, 0, 0.f, owner);
 }
@@ -621,9 +627,8 @@ extern "C" int shr_tri_raster_owner_fwd(const float *face_vertices, int B, int F
 extern "C" int shr_tri_raster_indexed_owner_fwd(const float *vertices, const int32_t *faces, int B, int NV, int F, int W,
                                                 int H, float *depth, int32_t *owner, void *stream) {
   if (B == 0) return SHR_OK;
-  if (!depth || !owner || !vertices || (!faces && F > 0) || B < 0 || F < 0 || NV <= 0 || W <= 0 || H <= 0) return SHR_EINVAL;
-  if ((long long)B * W * H > (1LL << 40) || (long long)B * ((F + 31) / 32) > (1LL << 31) || W > 65535 || H > 65535)
-    return SHR_ETOOLARGE;
+  if (!depth || !owner || !vertices || (!faces && F > 0) || NV <= 0) return SHR_EINVAL;
+  if (const int rc = tri_raster_limits(B, F, W, H)) return rc;
   if ((((uintptr_t)depth | (uintptr_t)owner | (uintptr_t)vertices) & 15u) != 0) return SHR_EINVAL;
   return tri_raster_common(true, vertices, faces, B, F, NV, W, H, depth, (hipStream_t)stream, 0, 0.f, owner);
 }

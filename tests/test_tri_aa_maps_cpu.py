@@ -120,8 +120,10 @@ def test_pair_decision_lives_in_one_file():
     count = lambda pat: {n: len(re.findall(pat, t)) for n, t in texts.items() if re.search(pat, t)}   # noqa: E731
     assert count(r"PairBlend pair_blend\(") == {"tri_antialias.hip": 1}
     unit = texts["tri_antialias.hip"]
-    for name in ("struct AAArgs", "struct PairBlend", "aa_sorts(", "aa_corners(", "aa_drawn(", "int aa_check("):
+    for name in ("struct AAArgs", "struct PairBlend", "aa_sorts(", "aa_drawn(", "int aa_check("):
         assert name in unit, name
+    # (the checked gather of a face's corners, once aa_corners here, is tri_tap.h's for every unit of the family)
+    assert count(r"\bbool tri_corners\(") == {"tri_tap.h": 1} and "tri_corners(" in unit and not count(r"\baa_corners\b")
     assert "tri_antialias_maps.hip" not in texts and "tri_aa_pair.h" not in texts
     # one pixel kernel template and one tap walker of the pass, whatever their names
     assert count(r"__global__[^;{]*\baa_\w*pixel\w*\(") == {"tri_antialias.hip": 1}

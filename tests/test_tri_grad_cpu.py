@@ -161,6 +161,31 @@ def test_owner_raster_keeps_the_band_kernels_budget(tmp_path):
     assert "ds_min_u64" in text and "flat_atomic" not in text
 
 
+def test_owned_tap_and_weight_chain_live_in_one_header():
+    """The backwards' shared statements about one face at one owned pixel -- the checked gather, the owned tap's fp32
+    decisions and fp64 weights, the chain from the three weights to the corners' x, y -- are defined once under csrc/, in
+    tri_tap.h, and the copies the units kept of each other are gone; no call of fixed_point_bwd is written once per RUNS."""
+    csrc = os.path.join(ROOT, "spherehand_amd", "csrc")
+    texts = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".h", ".hip"))}
+    count = lambda pat: {n: len(re.findall(pat, t)) for n, t in texts.items() if re.search(pat, t)}   # noqa: E731
+    assert count(r"\bbool tri_corners\(") == {"tri_tap.h": 1}
+    assert count(r"\bfloat owned_tap\(") == {"tri_tap.h": 1}
+    assert count(r"\bvoid weight_chain\(") == {"tri_tap.h": 1}
+    assert count(r"\bstruct OwnedTap\b") == {"tri_tap.h": 1}
+    assert count(r"kw \+= ") == {"tri_tap.h": 1}
+    assert count(r"\.den = ") == {"tri_tap.h": 1}                      # the fp64 preamble: 2 x the signed area, once
+    for gone in (r"\baa_corners\b", r"\binterp_corners\b", r"T\.den = ", r"\? fixed_point_bwd<"):
+        assert not count(gone), gone
+    # every unit of the family takes the header, and every caller of the gather, the tap and the chain is one of them
+    for unit in ("mesh_depth_bwd.hip", "tri_interp.hip", "tri_antialias.hip"):
+        assert '#include "tri_tap.h"' in texts[unit], unit
+    assert set(count(r"\btri_corners\(")) == {"tri_tap.h", "mesh_depth_bwd.hip", "tri_interp.hip", "tri_antialias.hip"}
+    assert set(count(r"\bowned_tap\(")) == {"tri_tap.h", "mesh_depth_bwd.hip", "tri_interp.hip"}
+    assert set(count(r"\bweight_chain\(")) == {"tri_tap.h", "mesh_depth_bwd.hip", "tri_interp.hip"}
+    assert count(r"\bint with_runs\(") == {"fixed_point.h": 1}
+    assert count(r"\bint tri_raster_limits\(") == {"tri_raster.hip": 1} and len(re.findall(r"tri_raster_limits\(", texts["tri_raster.hip"])) == 5
+
+
 def test_triangle_depth_raster_swaps_the_right_hands_winding():
     from spherehand_amd import hand_model
     from spherehand_amd.render import TriangleDepthRaster
