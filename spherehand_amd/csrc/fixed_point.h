@@ -4,10 +4,13 @@
 //
 // Sums: every (tap, corner, coordinate) term is a 64-bit FIXED-POINT integer in a per-crop power-of-two unit taken from
 // the crop's largest term (a first pass over the taps, an order-independent maximum), so that the largest term is below
-// 2^41 and any 2^21 of them -- more than three corners x four taps x 320^2 pixels -- below 2^62: no sum can wrap, and a
-// term is clamped to 2^41 besides.  Integer sums do not depend on order: the gradient is bitwise reproducible and
-// independent of the batch and of the launch shape (data_to_model's fixed-point sums, d2m_search.h).  The unit is
-// computed on the device: no host synchronisation, the backward can be captured into a graph.
+// 2^bits, a term is clamped to 2^bits besides, and any 2^(62 - bits) of them stay below 2^62.  bits is 41 while an
+// accumulator can take at most 2^21 terms and 62 - ceil(log2(terms)) above that: EVERY entry states its terms per pixel
+// and takes its bits from fix_term_bits(terms_per_pixel, W, H) below -- three for the owner raster and the interpolation
+// (a face's corners), two for the antialias pairs, twelve for shr_mesh_depth_bwd (four taps x three corners; 41 bits
+// up to S = 418) -- so no sum can wrap at any size an entry accepts.  Integer sums do not depend on order: the gradient
+// is bitwise reproducible and independent of the batch and of the launch shape (data_to_model's fixed-point sums,
+// d2m_search.h).  The unit is computed on the device: no host synchronisation, the backward can be captured into a graph.
 //
 // Taps: walk(fn) calls fn(g, pid) for every live tap of crop blockIdx.y in this workgroup's pixels, g its nine terms
 // (three points x three coordinates; a zero term is skipped by the sums), pid[k] the accumulator point of g[k];

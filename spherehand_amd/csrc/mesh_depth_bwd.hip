@@ -153,7 +153,10 @@ extern "C" int shr_mesh_depth_bwd(const float *vertices, const int32_t *faces, c
   if (B > 65535 || src_size > 32767 || 2 * S > src_size || (long long)NV * 3 >= (1LL << 31)) return SHR_ETOOLARGE;
   const MeshTaps taps{reinterpret_cast<const float4 *>(vertices), faces, reinterpret_cast<const int4 *>(owner), grad_depth, NV,
                       src_size, S};
-  return fixed_point_bwd<4>(taps, B, NV, (size_t)S * S, kFixBits, grad_vertices, workspace, (hipStream_t)stream);
+  // a vertex's accumulator takes at most twelve terms per output pixel: four taps x (at most) three corners of a tap's
+  // face on that vertex -- 41 bits for every S <= 418, fewer above (fixed_point.h)
+  return fixed_point_bwd<4>(taps, B, NV, (size_t)S * S, fix_term_bits(12, S, S), grad_vertices, workspace,
+                            (hipStream_t)stream);
 }
 
 // The owner raster's backward.  A point's accumulator takes at most three terms per pixel (a face's three corners, one

@@ -64,9 +64,12 @@ def clamp_decisions(p32, xf, yf):
     return (w >= 0) & (w <= 1), np.clip(w, 0, 1).astype(np.float32)
 
 
-def face_zp(vertices, faces, face, xi, yi):
+def face_zp(vertices, faces, face, xi, yi, keep=None):
     """zp of face[i] at source pixel (xi[i], yi[i]) for the flat lists face / xi / yi (crop index bi in vertices'
-    first axis given as a pair (bi, face)): differentiable (fp64) in `vertices`.  vertices: [B,NV,>=3] tensor."""
+    first axis given as a pair (bi, face)): differentiable (fp64) in `vertices`.  vertices: [B,NV,>=3] tensor.
+    keep: a dict that receives the gathered sorted corners `p` [N,3,3] (its gradient retained: after a backward, p.grad
+    holds every tap's nine terms), their crop `bi` [N] and their vertex ids `sorted_ids` [N,3]
+    (tests/fixed_point_ref.py)."""
     bi, f = face
     f = np.asarray(f, np.int64)
     bi = np.asarray(bi, np.int64)
@@ -79,6 +82,10 @@ def face_zp(vertices, faces, face, xi, yi):
     ok, c32 = clamp_decisions(p32, np.asarray(xi), np.asarray(yi))
     V = vertices.double()
     p = V[torch.from_numpy(bi)[:, None], torch.from_numpy(sorted_ids)][..., :3]   # [N,3,3] fp64, differentiable
+    if keep is not None:
+        if p.requires_grad:
+            p.retain_grad()
+        keep.update(p=p, bi=bi, sorted_ids=sorted_ids)
     x, y, z = p[..., 0], p[..., 1], p[..., 2]
     px = torch.from_numpy(np.asarray(xi, np.float64))[:, None].to(V.device)
     py = torch.from_numpy(np.asarray(yi, np.float64))[:, None].to(V.device)
@@ -92,10 +99,10 @@ def face_zp(vertices, faces, face, xi, yi):
     return 1.0 / q
 
 
-def owner_depth(vertices, faces, owner, src=640):
+def owner_depth(vertices, faces, owner, src=640, keep=None):
     """sum over all crops, pixels and owner taps of (bilinear weight) x zp(owner face at the tap), as a [B,S,S] fp64
     tensor of per-pixel sums (taps without an owner contribute nothing).  Its gradient w.r.t. vertices is the
-    differentiable mesh depth's."""
+    differentiable mesh depth's.  keep: face_zp's, one row per owner tap."""
     own = owner.cpu().numpy() if isinstance(owner, torch.Tensor) else np.asarray(owner)
     faces = faces.cpu().numpy().astype(np.int64) if isinstance(faces, torch.Tensor) else np.asarray(faces, np.int64)
     B, S = own.shape[0], own.shape[1]
@@ -104,7 +111,7 @@ def owner_depth(vertices, faces, owner, src=640):
     out = torch.zeros(B * S * S, dtype=torch.float64, device=vertices.device)
     if len(b) == 0:
         return out.view(B, S, S) + 0.0 * vertices.double().sum()
-    zp = face_zp(vertices, faces, (b, own[b, yy, xx, t]), xs[yy, xx, t], ys[yy, xx, t])
+    zp = face_zp(vertices, faces, (b, own[b, yy, xx, t]), xs[yy, xx, t], ys[yy, xx, t], keep)
     contrib = zp * torch.from_numpy(wt[yy, xx, t]).to(zp.device)
     out = out.index_add(0, torch.from_numpy((b * S + yy) * S + xx).to(zp.device), contrib)
     return out.view(B, S, S)

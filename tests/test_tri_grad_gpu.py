@@ -34,11 +34,7 @@ def _hand_soup(B):
     return np.ascontiguousarray(np.stack(out) if B else fv[:0], np.float32)
 
 
-def _random_soup(B, F, W, H, seed):
-    rs = np.random.RandomState(seed)
-    c = rs.uniform(-20, [W + 20, H + 20], (B, F, 1, 2))
-    spread = rs.choice([3.0, 12.0, 40.0], (B, F, 1, 1))
-    return np.concatenate([c + rs.normal(0, 1, (B, F, 3, 2)) * spread, rs.uniform(-50, 50, (B, F, 3, 1))], -1).astype(np.float32)
+_random_soup = ref.random_soup          # (tests/tri_grad_ref.py: tests/test_fixed_point_gpu.py draws the same soups)
 
 
 def _check_owner_raster(fv, W, H):

@@ -17,22 +17,31 @@ def soup_as_indexed(face_vertices):
     return face_vertices.reshape(B, 3 * F, 3), np.arange(3 * F, dtype=np.int64).reshape(F, 3)
 
 
+def random_soup(B, F, W, H, seed):
+    """[B,F,3,3] fp32: free triangles of three sizes centred up to 20 px off a W x H image, depths of both signs."""
+    rs = np.random.RandomState(seed)
+    c = rs.uniform(-20, [W + 20, H + 20], (B, F, 1, 2))
+    spread = rs.choice([3.0, 12.0, 40.0], (B, F, 1, 1))
+    return np.concatenate([c + rs.normal(0, 1, (B, F, 3, 2)) * spread, rs.uniform(-50, 50, (B, F, 3, 1))], -1).astype(np.float32)
+
+
 def _owned(owner):
     own = owner.cpu().numpy() if isinstance(owner, torch.Tensor) else np.asarray(owner)
     b, y, x = np.nonzero(own >= 0)
     return own, b, y, x
 
 
-def pixel_depth(vertices, faces, owner):
+def pixel_depth(vertices, faces, owner, keep=None):
     """[B,H,W] fp64 tensor: zp of the owner face at every owned pixel, 0 elsewhere; differentiable in `vertices`
-    ([B,NV,>=3] tensor, pixel space).  faces [F,3] vertex ids (original corner order)."""
+    ([B,NV,>=3] tensor, pixel space).  faces [F,3] vertex ids (original corner order).  keep: mesh_grad_ref.face_zp's,
+    one row per owned pixel."""
     faces = faces.cpu().numpy().astype(np.int64) if isinstance(faces, torch.Tensor) else np.asarray(faces, np.int64)
     own, b, y, x = _owned(owner)
     B, H, W = own.shape
     out = torch.zeros(B * H * W, dtype=torch.float64, device=vertices.device)
     if len(b) == 0:
         return out.view(B, H, W) + 0.0 * vertices.double().sum()
-    zp = ref.face_zp(vertices, faces, (b, own[b, y, x]), x, y)
+    zp = ref.face_zp(vertices, faces, (b, own[b, y, x]), x, y, keep)
     out = out.index_add(0, torch.from_numpy((b * H + y) * W + x).to(zp.device), zp)
     return out.view(B, H, W)
 

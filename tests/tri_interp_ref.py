@@ -87,9 +87,12 @@ def interp32(attr, owner, vertices, faces, with_info=False):
     return out
 
 
-def interp64(attr, owner, vertices, faces):
+def interp64(attr, owner, vertices, faces, keep=None):
     """Restatement (b): [B,C,H,W] fp64 tensor, differentiable in attr ([B,NV,C] or [NV,C] tensor) and vertices
-    ([B,NV,>=3] tensor); the clamp decisions and the zeroed pixels are restatement (a)'s."""
+    ([B,NV,>=3] tensor); the clamp decisions and the zeroed pixels are restatement (a)'s.  keep: a dict that receives the
+    live pixels' gathered sorted corners `P` [N,3,2] and attribute rows `rows` [N,3,C] (their gradients retained: after
+    a backward they hold every pixel's vertex and attribute terms), their crop `b` [N] and vertex ids `sid` [N,3]
+    (tests/fixed_point_ref.py)."""
     own = _np(owner)
     B, H, W = own.shape
     A, V = attr.double(), vertices.double()
@@ -114,6 +117,11 @@ def interp64(attr, owner, vertices, faces):
     c = torch.where(torch.from_numpy(ok), w, torch.from_numpy(c32).double())
     wh = c / c.sum(1, keepdim=True)
     rows = A[tb, tsid] if A.dim() == 3 else A[tsid]         # [N,3,C]
+    if keep is not None:
+        for t in (P, rows):
+            if t.requires_grad:
+                t.retain_grad()
+        keep.update(P=P, rows=rows, b=b, sid=sid)
     val = (wh[:, :, None] * rows).sum(1)
     out = out.index_add(0, torch.from_numpy((b * H + y) * W + x), val)
     return out.view(B, H, W, C).permute(0, 3, 1, 2)

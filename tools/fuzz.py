@@ -16,6 +16,7 @@ rs = np.random.RandomState(0)
 dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
 fails = 0
+skips = 0        # cases a family could not judge (trigrad, interp: a reference term that is not finite); run() counts them
 
 def sphere_case():
     global fails
@@ -499,38 +500,142 @@ def ks_case():
         print("KEYPOINT-SPHERES MISMATCH", dict(B=B), (sph - ref).abs().max().item(), (T1.grad - T2.grad).abs().max().item(),
               torch.equal(one, two), torch.equal(q1.grad, q2.grad))
 
+def _grad_helpers():
+    """tests/fixed_point_ref.py (the per-tap terms of the fp64 restatements and the error bound fixed_point.h's design
+    allows on every accumulator) and tests/tri_interp_ref.py"""
+    tests = os.path.join(ROOT, "tests")
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import fixed_point_ref, tri_interp_ref
+    return fixed_point_ref, tri_interp_ref
+
+def grad_case_draw(interp):
+    """One case of the trigrad / interp families, numpy only (tests/test_fixed_point_cpu.py draws it without a GPU): an
+    indexed mesh whose faces are tri_case's -- vertices on integer columns, degenerate faces, both windings -- at depths
+    20 .. 60, some faces welded to their predecessor's last corner, padded with unreferenced vertices to an NV on either
+    side of fixed_point.h's 2048 points; an upstream gradient +- 2^U(-20, 20) times one 2^k per crop."""
+    W = int(rs.choice([1, 5, 33, 64, 97])); H = int(rs.choice([1, 7, 40, 61]))
+    B = int(rs.randint(1, 4)); F = int(rs.choice([1, 31, 200, 683]))
+    c = rs.uniform(-0.2 * W, 1.2 * W, (B, F, 1, 1)) * np.array([1.0, H / W])
+    spread = rs.choice([0.7, 3.0, 12.0, 60.0], (B, F, 1, 1))
+    fv = np.concatenate([c + rs.normal(0, 1, (B, F, 3, 2)) * spread, rs.uniform(20, 60, (B, F, 3, 1))], -1).astype(np.float32)
+    if rs.rand() < 0.3: fv[:, :, :, 0] = np.round(fv[:, :, :, 0])
+    if rs.rand() < 0.2: fv[:, ::7, 1] = fv[:, ::7, 0]
+    faces = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    weld = np.nonzero(rs.rand(F) < 0.3)[0]
+    weld = weld[weld > 0]
+    faces[weld, 0] = faces[weld - 1, 2]
+    NV = int(rs.choice([n for n in (2040, 2047, 2048, 2049, 2300) if n >= 3 * F]))
+    pad = np.concatenate([rs.uniform(0, 60, (B, NV - 3 * F, 3)), np.ones((B, NV - 3 * F, 1))], -1)
+    verts = np.concatenate([np.concatenate([fv.reshape(B, 3 * F, 3), np.ones((B, 3 * F, 1))], -1), pad], 1).astype(np.float32)
+    case = dict(W=W, H=H, B=B, F=F, NV=NV, verts=np.ascontiguousarray(verts), faces=faces, band=int(rs.choice([-1, 0, 8])))
+    crop_scale = np.exp2(rs.randint(-30, 31, (B, 1, 1, 1)).astype(np.float64))
+    C = int(rs.choice([1, 3, 4, 17, 64])) if interp else 1
+    g = rs.choice([-1.0, 1.0], (B, C, H, W)) * np.exp2(rs.uniform(-20, 20, (B, C, H, W))) * crop_scale
+    case["grad"] = np.ascontiguousarray(g if interp else g[:, 0], np.float32)
+    if interp:
+        case["shared"] = bool(rs.rand() < 0.5)
+        case["attr"] = rs.standard_normal((NV, C) if case["shared"] else (B, NV, C)).astype(np.float32)
+    return case
+
+def grad_case_terms(case, owner):
+    """{entry: fixed_point_ref.Terms} of a drawn case for the owner map [B,H,W] of its indexed mesh"""
+    fx, _ = _grad_helpers()
+    if "attr" in case:
+        tv, ta, _ = fx.interp_terms(case["attr"], owner, case["verts"], case["faces"], case["grad"])
+        return {"vertices": tv, "attributes": ta}
+    B, F = case["B"], case["F"]
+    soup = case["verts"][:, case["faces"].astype(np.int64), :3].reshape(B, 3 * F, 3)
+    return {"indexed": fx.raster_terms(case["verts"], case["faces"], owner, case["grad"])[0],
+            "soup": fx.raster_terms(soup, np.arange(3 * F).reshape(F, 3), owner, case["grad"])[0]}
+
+def _grad_case(interp):
+    global fails, skips
+    fx, iref = _grad_helpers()
+    case = grad_case_draw(interp)
+    W, H, B, F, NV = (case[k] for k in ("W", "H", "B", "F", "NV"))
+    x, fc, g = dev(case["verts"]), dev(case["faces"]), dev(case["grad"])
+    fv = np.ascontiguousarray(case["verts"][:, case["faces"].astype(np.int64), :3])
+    try:
+        ops.set_tuning(ops.TUNE_TRI_BAND, case["band"])
+        want = depth_rasterization.forward(W, H, dev(fv))
+        ds, os_ = ops.tri_raster_owner_fwd(W, H, dev(fv))
+        di, oi = ops.tri_raster_indexed_owner_fwd(W, H, x, fc)
+    finally:
+        ops.set_tuning(ops.TUNE_TRI_BAND, -1)
+    why = []
+    if not (np.array_equal(bits(ds.cpu().numpy()), bits(want.cpu().numpy())) and torch.equal(di, ds) and torch.equal(oi, os_)):
+        why.append("owner forward: depth or owners differ from depth_rasterization.forward / between soup and indexed")
+    owner = oi.cpu().numpy()
+    terms = grad_case_terms(case, owner)
+    if not all(t.all_finite() for t in terms.values()):
+        skips += 1
+        return
+    nbits = fx.term_bits(3, W, H)
+    if interp:
+        a = dev(case["attr"])
+        if not np.array_equal(bits(ops.tri_interpolate(a, oi, x, fc).cpu().numpy()), bits(iref.interp32(case["attr"], owner, case["verts"], case["faces"]))):
+            why.append("interpolation forward bits")
+        ga, gv = ops.tri_interpolate_bwd(a, oi, x, fc, g)
+        got = {"vertices": gv.cpu().numpy()[..., :2], "attributes": ga.cpu().numpy()}
+    else:
+        got = {"indexed": ops.tri_raster_indexed_bwd(x, fc, oi, g).cpu().numpy()[..., :3], "soup": ops.tri_raster_bwd(dev(fv), os_, g).cpu().numpy()}
+    for name, t in terms.items():
+        worst, at = fx.worst_ratio(got[name], t, nbits)
+        if not worst <= 1.0:
+            why.append("%s: err / bound %.3g at %s" % (name, worst, at))
+    if why:
+        fails += 1
+        print("INTERP MISMATCH" if interp else "TRIGRAD MISMATCH", {k: v for k, v in case.items() if np.isscalar(v) or isinstance(v, bool)}, why)
+        if os.environ.get("FUZZ_DUMP"):      # (as the sphere family: the failing case, where the caller asks for it)
+            np.savez(os.environ["FUZZ_DUMP"], **case)
+
+def trigrad_case():
+    """the owner raster forward (soup and indexed, any band plan) against depth_rasterization.forward bit for bit; both
+    backwards against the per-accumulator bound of tests/fixed_point_ref.py"""
+    _grad_case(False)
+
+def interp_case():
+    """the attribute interpolation: forward bits against tri_interp_ref.interp32, both gradients against the bound"""
+    _grad_case(True)
+
 
 FAMILIES = (("sphere", sphere_case), ("tri", tri_case), ("d2m", d2m_case), ("mesh", mesh_case), ("fk", fk_case), ("gn", gn_case),
             ("mv", mv_case), ("sa", sa_case), ("pl", pl_case), ("lbs", lbs_case), ("hm", hm_case), ("ks", ks_case),
-            ("band", band_case), ("synth", synth_case))
+            ("band", band_case), ("synth", synth_case), ("trigrad", trigrad_case), ("interp", interp_case))
 
 
 def reset_tuning():
-    """the sphere family varies the launch shapes through shr_set_tuning: back to the launcher's choices"""
+    """the sphere and triangle families vary the launch shapes through shr_set_tuning: back to the launcher's choices"""
     for key, val in ((ops.TUNE_FORCE_GENERAL, 0), (ops.TUNE_FWD_LDS_BYTES, 0), (ops.TUNE_FWD_OWNER_LDS_BYTES, 0),
                      (ops.TUNE_BWD_LDS_BYTES, 128 * 1024), (ops.TUNE_FWD_WAVES, 16), (ops.TUNE_FWD_ZBUF_BYTES, 0),
-                     (ops.TUNE_BWD_WAVES, 0), (ops.TUNE_MSE_BOX, -1)):
+                     (ops.TUNE_BWD_WAVES, 0), (ops.TUNE_MSE_BOX, -1), (ops.TUNE_TRI_BAND, -1)):
         ops.set_tuning(key, val)
 
+
+skipped = {}
 
 def run(families=None, cases=None, seconds=None, seed=0, log=print):
     """Each family until `cases` cases (an int, or {family: int, "*": default}) or `seconds` seconds (whichever comes
     first; None = unbounded by that measure).
-    Returns {family: (cases run, mismatches)}."""
-    global rs, fails
+    Returns {family: (cases run, mismatches)}; `skipped` (module level) then holds {family: cases the family could not
+    judge} for the same run, and every log line names the count."""
+    global rs, fails, skips
     rs = np.random.RandomState(seed)
     torch.manual_seed(seed)      # (the module paths under test draw from torch's generators: same draws per seed)
     out = {}
+    skipped.clear()
     try:
         for name, fn in FAMILIES:
             if families and name not in families:
                 continue
-            before, t0, n = fails, time.time(), 0
+            before, skips0, t0, n = fails, skips, time.time(), 0
             ncase = cases.get(name, cases.get("*")) if isinstance(cases, dict) else cases
             while (ncase is None or n < ncase) and (seconds is None or time.time() - t0 < seconds):
                 fn(); n += 1
             out[name] = (n, fails - before)
-            log("%s: %d cases in %.1f s, %d mismatches" % (name, n, time.time() - t0, fails - before))
+            skipped[name] = skips - skips0
+            log("%s: %d cases in %.1f s, %d mismatches, %d skipped" % (name, n, time.time() - t0, fails - before, skips - skips0))
     finally:
         reset_tuning()
     return out
