@@ -669,6 +669,40 @@ int shr_tri_vertex_normals_bwd(const float *points, const int32_t *faces, const 
 int shr_unit3_maps_fwd(const float *maps, int B, int W, int H, float *out, void *stream);
 int shr_unit3_maps_bwd(const float *maps, const float *grad_out, int B, int W, int H, float *grad_maps, void *stream);
 
+/* Silhouette distance: the exact squared Euclidean distance transform of an image's foreground, and its bilinear
+ * sampler at points (a capability the reference does not have: a term that pulls a model point towards the observed
+ * silhouette from any distance).  Pixel (row i, column j) is the point (x = j, y = i): the sample points the triangle
+ * raster tests (tri_face.h: span_rows evaluates column xi at xf = (float)xi, pixel_weights row yi at yf = (float)yi), so
+ * projected vertices, sphere centres and key points are sampled as they are.
+ *   shr_dt_fwd   depth[B,H,W] fp32 -> d2[B,H,W] int32.  A pixel is a SITE iff depth < fg_max (a NaN depth is not a site;
+ *       a NaN fg_max makes none).  d2[b,i,j] = min over the sites (i', j') of image b of (i - i')^2 + (j - j')^2; an image
+ *       without a site gets H H + W W everywhere, above the largest real value (H-1)^2 + (W-1)^2 and finite.  Integer
+ *       arithmetic only: exact, independent of B and of the launch shape; no atomics, no host synchronisation, no
+ *       allocation.  1 <= H, W <= 2048 (every d2 < 2^24 converts to fp32 exactly) and B <= 65535: SHR_ETOOLARGE beyond.
+ *       workspace: 16-byte aligned, shr_dt_workspace_bytes(B, H, W) bytes (-1 on a negative size), every element that is
+ *       read is written by the call first.  It holds g[B][H][ceil(W/2)][2] uint16, the vertical distance of each pixel to
+ *       its column's nearest site (0xffff: the column has none).  B == 0 is a no-op; NULL or misaligned depth / d2 /
+ *       workspace: SHR_EINVAL.
+ *   shr_dt_sample_fwd   points[B,N,C] fp32, C >= 2, (x, y) first ([B,NV,4] vertices pass as they are); H, W >= 2;
+ *       max_dist >= 0, +inf allowed (SHR_EINVAL otherwise).  Per point, in fp32 with one rounding per written operation:
+ *         1. x or y not finite:  value 0, gradient (0, 0).
+ *         2. xc = min(max(x, 0), W-1);  x0 = min(floor(xc), W-2);  fx = xc - x0;  the same for y with H.
+ *         3. taps t = min(sqrt((float)d2), max_dist) (the IEEE root) at (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1).
+ *         4. top = t00 (1-fx) + t01 fx;  bot = t10 (1-fx) + t11 fx;  value = top (1-fy) + bot fy.
+ *         5. gx = (t01-t00) (1-fy) + (t11-t10) fy;  gy = bot - top.
+ *         6. a component whose coordinate was clamped in 2. (xc != x) gets gradient 0.
+ *       -> value[B,N] and grad_xy[B,N,2], the derivative of value with respect to (x, y) inside the cell.
+ *   shr_dt_sample_bwd   grad_points[B,N,C] = (grad_value grad_xy[0], grad_value grad_xy[1], 0, ...): every element is
+ *       written.
+ *   The sampler is a gather with no reduction: bitwise reproducible.  B <= 65535, N C < 2^31 (SHR_ETOOLARGE beyond);
+ *   B == 0 or N == 0 is a no-op; NULL or misaligned pointers: SHR_EINVAL. */
+long long shr_dt_workspace_bytes(int B, int H, int W);
+int shr_dt_fwd(const float *depth, int B, int H, int W, float fg_max, int32_t *d2, void *workspace, void *stream);
+int shr_dt_sample_fwd(const int32_t *d2, int B, int H, int W, const float *points, int N, int C, float max_dist,
+                      float *value, float *grad_xy, void *stream);
+int shr_dt_sample_bwd(const float *grad_xy, const float *grad_value, int B, int N, int C, float *grad_points,
+                      void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -101,6 +101,10 @@ SIGNATURES = {
                                     _vp], _i),
     "shr_unit3_maps_fwd": ([_vp, _i, _i, _i, _vp, _vp], _i),
     "shr_unit3_maps_bwd": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "shr_dt_workspace_bytes": ([_i, _i, _i], ctypes.c_longlong),
+    "shr_dt_fwd": ([_vp, _i, _i, _i, _f, _vp, _vp, _vp], _i),
+    "shr_dt_sample_fwd": ([_vp, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp], _i),
+    "shr_dt_sample_bwd": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "shr_fk_fwd":([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -1514,6 +1514,84 @@ class Unit3Maps(torch.autograd.Function):
         return unit3_maps_bwd(maps, grad_out.contiguous().float())
 
 
+def distance_transform(depth, fg_max):
+    """The exact squared Euclidean distance transform of the foreground (include/spherehand_hip.h, shr_dt_fwd): depth
+    [B,H,W] fp32 -> int32 [B,H,W], each pixel's squared distance to the nearest pixel with depth < fg_max; H H + W W
+    everywhere in an image that has none."""
+    _check_input(depth, "depth")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise RuntimeError("depth must be [B,H,W] with H, W >= 1")
+    B, H, W = depth.shape
+    lib = _lib.lib()
+    with _on(depth.device):
+        d2 = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
+        ws = torch.empty((max(16, lib.shr_dt_workspace_bytes(B, H, W)),), dtype=torch.uint8, device=depth.device)
+        _lib.check(lib.shr_dt_fwd(_ptr(depth), B, H, W, float(fg_max), _ptr(d2), _ptr(ws), _stream()), "shr_dt_fwd")
+    return d2
+
+
+def _dt_sample_shape(d2, points):
+    _check_input(d2, "d2", torch.int32)
+    _check_input(points, "points")
+    if d2.dim() != 3 or d2.shape[1] < 2 or d2.shape[2] < 2:
+        raise RuntimeError("d2 must be [B,H,W] with H, W >= 2")
+    if points.dim() != 3 or points.shape[2] < 2 or points.shape[0] != d2.shape[0] or points.device != d2.device:
+        raise RuntimeError("points must be [B,N,C] with C >= 2 and d2's B, on its device")
+    return d2.shape[0], d2.shape[1], d2.shape[2], points.shape[1], points.shape[2]
+
+
+def dt_sample(d2, points, max_dist=float("inf")):
+    """Bilinear samples of min(sqrt(d2), max_dist) at points [B,N,C] = (x, y, ...) in pixel coordinates
+    (include/spherehand_hip.h, shr_dt_sample_fwd) -> (value [B,N], grad_xy [B,N,2] = d value / d (x, y)).  Points outside
+    the image sample its border with zero gradient in the clamped component; non-finite points give zeros."""
+    B, H, W, N, C = _dt_sample_shape(d2, points)
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise RuntimeError("max_dist must be >= 0 (inf: no saturation), not %r" % (max_dist,))
+    with _on(d2.device):
+        value = torch.empty((B, N), dtype=torch.float32, device=d2.device)
+        grad_xy = torch.empty((B, N, 2), dtype=torch.float32, device=d2.device)
+        _lib.check(_lib.lib().shr_dt_sample_fwd(_ptr(d2), B, H, W, _ptr(points), N, C, max_dist, _ptr(value),
+                                                _ptr(grad_xy), _stream()), "shr_dt_sample_fwd")
+    return value, grad_xy
+
+
+def dt_sample_bwd(grad_xy, grad_value, C):
+    """dt_sample's backward: grad_xy [B,N,2] (the forward's), grad_value [B,N] -> grad_points [B,N,C], components 0 and 1
+    = grad_value * grad_xy, the others 0."""
+    _check_input(grad_xy, "grad_xy")
+    _check_input(grad_value, "grad_value")
+    if grad_xy.dim() != 3 or grad_xy.shape[2] != 2 or grad_value.shape != grad_xy.shape[:2] or \
+            grad_value.device != grad_xy.device:
+        raise RuntimeError("grad_xy must be [B,N,2] and grad_value [B,N], on one device")
+    if C < 2:
+        raise RuntimeError("C must be >= 2")
+    B, N = grad_value.shape
+    with _on(grad_xy.device):
+        out = torch.empty((B, N, C), dtype=torch.float32, device=grad_xy.device)
+        _lib.check(_lib.lib().shr_dt_sample_bwd(_ptr(grad_xy), _ptr(grad_value), B, N, C, _ptr(out), _stream()),
+                   "shr_dt_sample_bwd")
+    return out
+
+
+class DistanceSample(torch.autograd.Function):
+    """dt_sample with a backward: (points [B,N,C], d2 [B,H,W] int32, max_dist) -> distances [B,N], differentiable w.r.t.
+    points[..., :2] (the bilinear cell's own slope: piecewise constant, zero in a clamped component)."""
+
+    @staticmethod
+    def forward(ctx, points, d2, max_dist=float("inf")):
+        points = points.contiguous()
+        value, grad_xy = dt_sample(d2, points, max_dist)
+        ctx.C = points.shape[2]
+        ctx.save_for_backward(grad_xy)
+        return value
+
+    @staticmethod
+    def backward(ctx, grad_value):
+        grad_xy, = ctx.saved_tensors
+        return dt_sample_bwd(grad_xy, grad_value.contiguous().float(), ctx.C), None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

@@ -11,6 +11,7 @@ signatures and return values), running on the hand-written HIP kernels.
     MeshAttributeRaster      TriangleDepthRaster + per-pixel maps of per-vertex attributes (part maps, correspondences)
     AntialiasedAttributeRaster  the maps and the clamped depth, both antialiased: outline gradients for the maps too
     MeshNormalRaster         a unit normal map from area-weighted vertex normals, and the depth: gradients reach z
+    SilhouetteDistance       the distance of projected points to the observed silhouette: a pull from any distance
 """
 import numpy as np
 import torch
@@ -395,6 +396,36 @@ class MeshNormalRaster(nn.Module):
         maps = ops.TriAntialiasMaps.apply(maps, raw, owner, v, self.faces_i32, self.edges_i32)
         c = torch.clamp(depth, max=self.clamp_max)
         return maps, ops.TriAntialias.apply(c, raw, owner, v, self.faces_i32, self.edges_i32)
+
+
+class SilhouetteDistance(nn.Module):
+    """The silhouette term of model fitting: the distance from projected model points to the observed foreground
+    (ops.distance_transform, ops.DistanceSample; include/spherehand_hip.h states both).  observe(depth[B,H,W]) computes
+    and keeps the exact squared distance transform of the pixels with depth < fg_max, once per observation.
+    forward(points[B,N,>=2], pixel-space x, y first -- vertices, sphere centres and key points as the rasters take them)
+    -> the per-point distances [B,N] in pixels, bilinear between pixel centres and saturated at max_dist; loss(points) is
+    their mean.  Differentiable w.r.t. points[..., :2]: a point outside the observed silhouette gets a gradient of about
+    unit length, however far the silhouette is: d value / d point points away from the nearest observed pixel, so a
+    descent step moves the point towards it; a point inside gets 0.  A
+    point outside the image samples the border, with no gradient in the clamped component."""
+
+    def __init__(self, fg_max, max_dist=float('inf')):
+        super().__init__()
+        self.fg_max = float(fg_max)
+        self.max_dist = float(max_dist)
+        self.d2 = None
+
+    def observe(self, depth):
+        self.d2 = ops.distance_transform(depth.detach().contiguous(), self.fg_max)
+        return self.d2
+
+    def forward(self, points):
+        if self.d2 is None:
+            raise RuntimeError("SilhouetteDistance: observe(depth) first")
+        return ops.DistanceSample.apply(points, self.d2, self.max_dist)
+
+    def loss(self, points):
+        return self.forward(points).mean()
 
 
 class SparseSkinning(nn.Module):
