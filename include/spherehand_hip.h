@@ -703,6 +703,53 @@ int shr_dt_sample_fwd(const int32_t *d2, int B, int H, int W, const float *point
 int shr_dt_sample_bwd(const float *grad_xy, const float *grad_value, int B, int N, int C, float *grad_points,
                       void *stream);
 
+/* Silhouette coverage, the other half of the silhouette term: the distance from every OBSERVED pixel to the RENDERED
+ * silhouette, and its gradient to the vertices -- a pull on the model over observed pixels it does not cover (the
+ * sampler above pulls model points that lie outside the observation; a model inside it gets nothing from that half).
+ *   shr_dt_nearest_fwd   shr_dt_fwd with its argument.  depth[B,H,W] -> d2[B,H,W] int32, the bits of shr_dt_fwd, and
+ *       nearest[B,H,W] int32.  The site rule (depth < fg_max, a NaN is not a site), the limits (1 <= H, W <= 2048,
+ *       B <= 65535: H W <= 2^22, an index fits), the error codes, the alignment rules and the B == 0 no-op are
+ *       shr_dt_fwd's.  nearest[b,i,j] = i' W + j' of a site (i', j') of image b with (i - i')^2 + (j - j')^2 == d2[b,i,j];
+ *       among several such sites the one with the SMALLEST i' W + j'; -1 everywhere in an image without a site; a site
+ *       is its own nearest.  Integer arithmetic only, no atomics: exact, independent of B and of the launch shape; no
+ *       host synchronisation, no allocation.  Two passes: per column the vertically nearest site (an up / down tie:
+ *       the smaller row), then per row the lexicographic minimum of (total, index).
+ *       workspace: 16-byte aligned, shr_dt_nearest_workspace_bytes(B, H, W) bytes (-1 on a negative size), every element
+ *       that is read is written by the call first.  It holds g[B][H][ceil(W/2)][2] uint16: bits 0..14 the vertical
+ *       distance of each pixel to its column's nearest site, bit 15 set when that site lies below the pixel (a larger
+ *       row); 0xffff: the column has none.
+ *   shr_sil_cover_fwd   observed[B,H,W] fp32 (a pixel is OBSERVED iff observed < obs_fg_max; NaN: not observed), d2 the
+ *       transform of the rendered depth -> dist[B,H,W] = fminf(sqrtf((float)d2), max_dist) at an observed pixel, 0
+ *       elsewhere.  fp32, the IEEE root; every element is written; a gather with no reduction: bitwise reproducible.
+ *       max_dist >= 0, +inf allowed (SHR_EINVAL otherwise).
+ *   shr_sil_cover_bwd   d2, nearest: the transform of the rendered depth; owner[B,H,W], vertices[B,NV,4], faces[F,3]: as
+ *       shr_tri_raster_indexed_owner_fwd gave and took them; grad_dist[B,H,W] -> grad_vertices[B,NV,4] = (du, dv, 0, 0),
+ *       every element written.  Pixel p = (x = j, y = i) contributes iff it is observed, d2 > 0,
+ *       sqrtf((float)d2) <= max_dist, grad_dist != 0, q = nearest lies in [0, H W), f = owner[q] lies in [0, F), the
+ *       face's vertex ids lie in [0, NV), and the fp32 sum of the clamped weights of f at q = (xq, yq) is > 0 and
+ *       <= 3e38 (shr_tri_interp_fwd's rule for a live pixel).  It adds to the face's x-sorted corner a
+ *         (-grad_dist (c_a / s) (x - xq) / d,  -grad_dist (c_a / s) (y - yq) / d,  0),   d = sqrt((double)d2) in fp64,
+ *       c_a / s the weights the depth and the attribute maps use at q (shr_tri_interp_bwd's rule: fp32 clamp decisions,
+ *       fp64 values), HELD FIXED -- the envelope rule: q is a material point of face f with weights c / s, and moving it
+ *       by delta changes |p - q| by -u . delta, u = (p - q) / d.  The gradient is the attribute gradient of
+ *       shr_tri_interp_bwd for the attribute (x, y) under the map G[b,:,q] = sum over the pixels p with nearest(p) = q
+ *       of -grad_dist(p) u(p).  No gradient to z, to the weights, or through the choice of q.  An image whose render is
+ *       empty (nearest = -1 everywhere) gets a zero gradient.  The sums are 64-bit fixed point in a per-crop unit
+ *       computed on the device (at most 3 W H terms per accumulator): bitwise reproducible, independent of the batch
+ *       and of the launch shape, no host synchronisation.  workspace: 16-byte aligned,
+ *       shr_sil_cover_bwd_workspace_bytes(B, NV) bytes (-1 on a negative size), cleared by the call itself.
+ *   1 <= H, W <= 2048, B <= 65535 (SHR_ETOOLARGE beyond); B == 0 is a no-op; NULLs (faces may be NULL when F == 0) and
+ *   misaligned pointers (4 bytes; vertices, grad_vertices and workspace 16): SHR_EINVAL. */
+long long shr_dt_nearest_workspace_bytes(int B, int H, int W);
+int shr_dt_nearest_fwd(const float *depth, int B, int H, int W, float fg_max, int32_t *d2, int32_t *nearest,
+                       void *workspace, void *stream);
+int shr_sil_cover_fwd(const float *observed, float obs_fg_max, const int32_t *d2, int B, int H, int W, float max_dist,
+                      float *dist, void *stream);
+long long shr_sil_cover_bwd_workspace_bytes(int B, int NV);
+int shr_sil_cover_bwd(const float *observed, float obs_fg_max, const int32_t *d2, const int32_t *nearest,
+                      const int32_t *owner, const float *vertices, const int32_t *faces, const float *grad_dist, int B,
+                      int NV, int F, int W, int H, float max_dist, float *grad_vertices, void *workspace, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -1,8 +1,9 @@
 // tri_tap.h -- what the differentiable triangle family's backwards share about ONE face at ONE pixel it owns, stated once
-// for mesh_depth_bwd.hip (MeshTaps, PixelTaps), tri_interp.hip (the forward and its three walkers) and tri_antialias.hip
-// (pair_blend's front face):
+// for mesh_depth_bwd.hip (MeshTaps, PixelTaps), tri_interp.hip (the forward and its three walkers), tri_antialias.hip
+// (pair_blend's front face) and sil_cover.hip (CoverTaps):
 //   tri_corners     the checked gather of an indexed face's corners
 //   owned_tap       the forward's fp32 clamp decisions (tri_face.h) and the fp64 weights over the x-sorted corners
+//   live_tap        the two together under the interpolation's rule for a live pixel
 //   weight_chain    d w_a = (d n_a - w_a d den) / den: per-weight coefficients -> the sorted corners' (x, y) gradient
 //   tap_sorted_ids, tap_unsort   between a face's own corner order and the sorted one
 // The rule is mesh_depth_bwd.hip's: decisions in the forward's fp32 arithmetic, derivatives in fp64, a weight clamped
@@ -66,6 +67,18 @@ __device__ __forceinline__ float owned_tap(const float (&fv)[9], int xi, int yi,
     tap.s += tap.c[a];
   }
   return s32;
+}
+
+// Face f of an indexed mesh at pixel (xi, yi), for a walker whose pixel is not the one that reads the owner map
+// (sil_cover.hip's CoverTaps: an observed pixel's tap lies at its nearest rendered pixel): the checked gather and the owned
+// tap under the interpolation's rule for a live pixel, the fp32 sum of the clamped weights in (0, 3e38].  False -- and T
+// undefined -- when the face, a vertex id or the sum fails: the caller skips the tap.  id[k]: the vertex of corner k.
+__device__ __forceinline__ bool live_tap(const float4 *__restrict__ verts, const int *__restrict__ faces, int NV, int F, int f,
+                                         int xi, int yi, OwnedTap &T, int (&id)[3]) {
+  float fv[9];
+  if (!tri_corners(verts, faces, NV, F, f, fv, id)) return false;
+  const float s32 = owned_tap(fv, xi, yi, T);
+  return s32 > 0.f && s32 <= 3.0e38f;
 }
 
 // With w_a = n_a / den, n_a = cross(P_b - P, P_e - P) and den = sum_a n_a: G[.][0..1] += sum over the weights that pass

@@ -1592,6 +1592,104 @@ class DistanceSample(torch.autograd.Function):
         return dt_sample_bwd(grad_xy, grad_value.contiguous().float(), ctx.C), None, None
 
 
+def nearest_site_transform(depth, fg_max):
+    """distance_transform with its argument (include/spherehand_hip.h, shr_dt_nearest_fwd): depth [B,H,W] fp32 ->
+    (d2 int32 [B,H,W], the bits of distance_transform; nearest int32 [B,H,W]: i' W + j' of the nearest pixel with
+    depth < fg_max, the smallest such index among equally near ones, -1 everywhere in an image that has none)."""
+    _check_input(depth, "depth")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise RuntimeError("depth must be [B,H,W] with H, W >= 1")
+    B, H, W = depth.shape
+    lib = _lib.lib()
+    with _on(depth.device):
+        d2 = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
+        nearest = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
+        ws = torch.empty((max(16, lib.shr_dt_nearest_workspace_bytes(B, H, W)),), dtype=torch.uint8, device=depth.device)
+        _lib.check(lib.shr_dt_nearest_fwd(_ptr(depth), B, H, W, float(fg_max), _ptr(d2), _ptr(nearest), _ptr(ws), _stream()),
+                   "shr_dt_nearest_fwd")
+    return d2, nearest
+
+
+def _cover_max_dist(max_dist):
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise RuntimeError("max_dist must be >= 0 (inf: no saturation), not %r" % (max_dist,))
+    return max_dist
+
+
+def _cover_shape(observed, d2):
+    _check_input(observed, "observed")
+    _check_input(d2, "d2", torch.int32)
+    if observed.dim() != 3 or observed.shape[1] < 1 or observed.shape[2] < 1:
+        raise RuntimeError("observed must be [B,H,W] with H, W >= 1")
+    if d2.shape != observed.shape or d2.device != observed.device:
+        raise RuntimeError("d2 must be [B,H,W] as observed, on its device")
+    return observed.shape
+
+
+def sil_cover(observed, obs_fg_max, d2, max_dist=float("inf")):
+    """The coverage distance (include/spherehand_hip.h, shr_sil_cover_fwd): observed [B,H,W] fp32, d2 [B,H,W] int32 the
+    transform of the RENDERED depth -> dist [B,H,W] = min(sqrt(d2), max_dist) where observed < obs_fg_max, 0 elsewhere."""
+    B, H, W = _cover_shape(observed, d2)
+    max_dist = _cover_max_dist(max_dist)
+    with _on(observed.device):
+        dist = torch.empty((B, H, W), dtype=torch.float32, device=observed.device)
+        _lib.check(_lib.lib().shr_sil_cover_fwd(_ptr(observed), float(obs_fg_max), _ptr(d2), B, H, W, max_dist, _ptr(dist),
+                                                _stream()), "shr_sil_cover_fwd")
+    return dist
+
+
+def sil_cover_bwd(observed, obs_fg_max, d2, nearest, owner, vertices, faces, grad_dist, max_dist=float("inf")):
+    """sil_cover's backward to the vertices (include/spherehand_hip.h, shr_sil_cover_bwd): d2, nearest from
+    nearest_site_transform of the rendered depth, owner [B,H,W] int32, vertices [B,NV,4] and faces [F,3] int32 as
+    tri_raster_indexed_owner_fwd gave and took them, grad_dist [B,H,W] -> grad_vertices [B,NV,4] = (du, dv, 0, 0): every
+    uncovered observed pixel pulls its nearest rendered pixel's owner face towards itself; deterministic fixed-point
+    sums."""
+    B, H, W = _cover_shape(observed, d2)
+    max_dist = _cover_max_dist(max_dist)
+    _check_input(nearest, "nearest", torch.int32)
+    _check_input(owner, "owner", torch.int32)
+    _check_input(grad_dist, "grad_dist")
+    Bv, NV, F = _indexed_shape(vertices, faces)
+    for t, name in ((nearest, "nearest"), (owner, "owner"), (grad_dist, "grad_dist")):
+        if t.shape != observed.shape or t.device != observed.device:
+            raise RuntimeError("%s must be [B,H,W] as observed, on its device" % name)
+    if Bv != B or vertices.device != observed.device or faces.device != observed.device:
+        raise RuntimeError("vertices must be [B,NV,4] with observed's B, vertices and faces on its device")
+    lib = _lib.lib()
+    with _on(observed.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=observed.device)
+        ws = torch.empty((max(16, lib.shr_sil_cover_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8,
+                         device=observed.device)
+        _lib.check(lib.shr_sil_cover_bwd(_ptr(observed), float(obs_fg_max), _ptr(d2), _ptr(nearest), _ptr(owner),
+                                         _ptr(vertices), _ptr(faces), _ptr(grad_dist), B, NV, F, W, H, max_dist, _ptr(out),
+                                         _ptr(ws), _stream()), "shr_sil_cover_bwd")
+    return out
+
+
+class SilhouetteCover(torch.autograd.Function):
+    """sil_cover with a backward: (vertices [B,NV,3 or 4] pixel space, faces, owner, d2, nearest, observed, obs_fg_max,
+    max_dist) -> dist [B,H,W].  owner, d2 and nearest are those of the render of these vertices
+    (tri_raster_indexed_owner_fwd, nearest_site_transform).  Differentiable w.r.t. vertices[..., :2] only: the nearest
+    rendered pixel and its weights are held fixed (the z gradient is zero)."""
+
+    @staticmethod
+    def forward(ctx, vertices, faces, owner, d2, nearest, observed, obs_fg_max, max_dist=float("inf")):
+        v4, ctx.width4 = vertices4(vertices)
+        observed = observed.contiguous()
+        dist = sil_cover(observed, obs_fg_max, d2, max_dist)
+        ctx.obs_fg_max, ctx.max_dist = obs_fg_max, max_dist
+        ctx.save_for_backward(v4, faces, owner, d2, nearest, observed)
+        return dist
+
+    @staticmethod
+    def backward(ctx, grad_dist):
+        v4, faces, owner, d2, nearest, observed = ctx.saved_tensors
+        g = sil_cover_bwd(observed, ctx.obs_fg_max, d2, nearest, owner, v4, faces, grad_dist.contiguous().float(),
+                          ctx.max_dist)
+        return _grad_as_given(ctx, g), None, None, None, None, None, None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

@@ -12,6 +12,7 @@ signatures and return values), running on the hand-written HIP kernels.
     AntialiasedAttributeRaster  the maps and the clamped depth, both antialiased: outline gradients for the maps too
     MeshNormalRaster         a unit normal map from area-weighted vertex normals, and the depth: gradients reach z
     SilhouetteDistance       the distance of projected points to the observed silhouette: a pull from any distance
+    SilhouetteCoverage       its complement: the distance of observed pixels to the rendered silhouette, a pull on the mesh
 """
 import numpy as np
 import torch
@@ -426,6 +427,58 @@ class SilhouetteDistance(nn.Module):
 
     def loss(self, points):
         return self.forward(points).mean()
+
+
+class SilhouetteCoverage(nn.Module):
+    """SilhouetteDistance's complement: the distance from every OBSERVED pixel to the RENDERED silhouette
+    (ops.nearest_site_transform, ops.SilhouetteCover; include/spherehand_hip.h states both).  SilhouetteDistance pulls
+    model points that lie outside the observation towards it and gives a model that lies inside nothing -- a mesh shrunk
+    to a dot inside the observed hand is a minimum of that half.  This half pulls the mesh over observed pixels it does
+    not cover.  observe(depth[B,H,W]) keeps the observation (observed: depth < fg_max) and each crop's count of observed
+    pixels.  forward(vertices[B,NV,>=3], pixel-space x, y, z) renders the mesh at width x height with the owner raster
+    (under no_grad), transforms that depth (rendered: depth < render_fg_max) and returns [B]: the mean distance in pixels
+    of each crop's observed pixels to the nearest rendered pixel, saturated at max_dist; loss(vertices) is its mean.
+    Coverage is decided at pixel centres: an observed pixel the render covers has distance 0.  Differentiable w.r.t.
+    vertices[..., :2] only -- a gradient in x and y: every uncovered observed pixel pulls its nearest rendered pixel's
+    owner face towards itself with the weights the depth used there, the nearest pixel and the weights held fixed.
+    `np_faces` gets the right hand's winding swap (mesh/render.py:298-300) and is not modified."""
+
+    def __init__(self, width, height, np_faces, fg_max, max_dist=float('inf'), right_hand=True, render_fg_max=1000.0):
+        super().__init__()
+        self.width = width
+        self.height = height
+        self.fg_max = float(fg_max)
+        self.max_dist = float(max_dist)
+        self.render_fg_max = float(render_fg_max)
+        faces = np.array(np_faces, dtype=np.int64, copy=True)
+        if right_hand:
+            faces[:, [0, 1]] = faces[:, [1, 0]]
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+        self.observed = None
+        self.count = None
+
+    def observe(self, depth):
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.height, self.width):
+            raise RuntimeError("SilhouetteCoverage: observe takes depth [B,%d,%d]" % (self.height, self.width))
+        self.observed = depth.detach().contiguous().float()
+        self.count = (self.observed < self.fg_max).sum((1, 2)).clamp(min=1).float()
+        return self.count
+
+    def forward(self, vertices):
+        if self.observed is None:
+            raise RuntimeError("SilhouetteCoverage: observe(depth) first")
+        if vertices.dim() != 3 or vertices.shape[-1] < 3:
+            raise RuntimeError("SilhouetteCoverage takes vertices [B,NV,>=3]")
+        v = vertices if vertices.shape[-1] in (3, 4) else vertices[..., :3]
+        with torch.no_grad():
+            depth, owner = ops.tri_raster_indexed_owner_fwd(self.width, self.height, ops.vertices4(v.detach())[0],
+                                                            self.faces_i32)
+            d2, nearest = ops.nearest_site_transform(depth, self.render_fg_max)
+        dist = ops.SilhouetteCover.apply(v, self.faces_i32, owner, d2, nearest, self.observed, self.fg_max, self.max_dist)
+        return dist.sum((1, 2)) / self.count
+
+    def loss(self, vertices):
+        return self.forward(vertices).mean()
 
 
 class SparseSkinning(nn.Module):
