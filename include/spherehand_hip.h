@@ -361,6 +361,19 @@ int shr_group_norm_relu_bwd(const float *x, const float *pre_bias, const float *
                             int N, int C, int HW, int G, float *dx,
                             float *dgamma_partial, float *dbeta_partial, float *dpre_partial,
                             float *dgamma, float *dbeta, float *dpre, void *stream);
+/* The same pair for bf16 activations: x, y, dy and dx are bf16 (uint16_t: the upper half of the fp32 pattern),
+ * x[N][HW][C] channels-last; pre_bias, gamma, beta, mean, rstd and every partial and parameter gradient stay fp32.
+ * Every element is widened exactly and all arithmetic is the fp32 entries', in their order; the one added rounding
+ * is the store of y and of dx, round-to-nearest-even.  Same supported (C, G) set, same argument rules and codes
+ * (SHR_EINVAL: NULL, unsupported (C, G), a buffer off 16 bytes; SHR_ETOOLARGE: N > 65535). */
+int shr_group_norm_relu_bf16_fwd(const uint16_t *x, const float *pre_bias, const float *gamma, const float *beta,
+                                 int N, int C, int HW, int G, float eps,
+                                 uint16_t *y, float *mean, float *rstd, void *stream);
+int shr_group_norm_relu_bf16_bwd(const uint16_t *x, const float *pre_bias, const uint16_t *dy, const float *gamma,
+                                 const float *beta, const float *mean, const float *rstd,
+                                 int N, int C, int HW, int G, uint16_t *dx,
+                                 float *dgamma_partial, float *dbeta_partial, float *dpre_partial,
+                                 float *dgamma, float *dbeta, float *dpre, void *stream);
 
 
 /* View-to-view projection of the sphere centres ---------------------------------

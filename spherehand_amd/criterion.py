@@ -31,10 +31,16 @@ class HeatmapEstimationNetwork(nn.Module):
     per-stack lists 'real_uv_hms' [B,V,J,h,w], 'real_d_hms', 'real_xyz' [B,V,J,3]
     and/or 'synt_uv_hms', 'synt_d_hms', 'synt_xyz'; with both inputs one
     concatenated pass (+ 'batch_*_fea' latents).  Training-time scale augmentation
-    of the real crops as in the reference (:41-50, :93-102)."""
+    of the real crops as in the reference (:41-50, :93-102).
+    amp_dtype = torch.bfloat16 (CUDA only): the hourglass alone runs under autocast -- bf16 MIOpen convolutions and
+    the bf16 GroupNorm+ReLU kernels, fp32 parameters -- and its scores and latents are widened to fp32 at once, so
+    the soft-argmax, the heads and every loss see fp32 as without the switch."""
 
-    def __init__(self, heatmap_size, depth_scale, num_joints, num_stacks, real_aug=True):
+    def __init__(self, heatmap_size, depth_scale, num_joints, num_stacks, real_aug=True, amp_dtype=None):
         super().__init__()
+        if amp_dtype not in (None, torch.bfloat16):
+            raise ValueError("amp_dtype must be None or torch.bfloat16, not %r" % (amp_dtype,))
+        self.amp_dtype = amp_dtype
         self.num_joints = num_joints
         self.hg = create_hourglass_network(num_joints * 2, num_stacks)
         self.xyz_recover = RecoverXYZCoordinateFromHeatmap(heatmap_size, heatmap_size, depth_scale)
@@ -69,7 +75,13 @@ class HeatmapEstimationNetwork(nn.Module):
             B, V = real_dms.shape[0], real_dms.shape[1]
             flat, u_scale, v_scale = self._augment(real_dms.reshape(B * V, real_dms.shape[2], real_dms.shape[3]))
             inputs.append(flat)
-        outputs, latents = self.hg(torch.cat(inputs, dim=0) if len(inputs) > 1 else inputs[0])
+        crops = torch.cat(inputs, dim=0) if len(inputs) > 1 else inputs[0]
+        if self.amp_dtype is not None and crops.is_cuda:
+            with torch.autocast("cuda", dtype=self.amp_dtype):
+                outputs, latents = self.hg(crops)
+            outputs, latents = [o.float() for o in outputs], [l.float() for l in latents]
+        else:
+            outputs, latents = self.hg(crops)
         if synt_dms is not None:
             synt_out = [o[:n_synt] for o in outputs]
             uv, d = self._split(synt_out)

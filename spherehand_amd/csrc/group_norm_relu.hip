@@ -12,12 +12,11 @@
 // per access.  A 32-channel block holds whole groups (C/G in {4, 8, 16, 32}).  The sample's
 // slab (<= 256 KB) is read up to three times; passes two and three hit the L2.  All sums are
 // reduced in a fixed order (shuffles inside a wave, waves in order): deterministic.
-#include "common.h"
+#include "group_norm_relu.h"
 
 namespace shr {
 
 constexpr int kGnThreads = 256;
-constexpr int kGnBlockC = 32;
 
 // sum over the 8 pixel slots of a wave (lanes with equal lane & 7), then over the cpg/4
 // neighbouring channel-lanes of a group, then over the 4 waves: every lane ends up with the
@@ -213,6 +212,12 @@ bool gn_supported(int C, int G) {
   return cpg % 4 == 0 && cpg <= kGnBlockC && kGnBlockC % cpg == 0;
 }
 
+void gn_launch_param_grad(const float *dgamma_partial, const float *dbeta_partial, const float *dpre_partial, int N, int C,
+                          float *dgamma, float *dbeta, float *dpre, hipStream_t stream) {
+  hipLaunchKernelGGL(group_norm_param_grad_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, stream, dgamma_partial,
+                     dbeta_partial, dpre_partial, N, C, dgamma, dbeta, dpre);
+}
+
 }  // namespace shr
 
 extern "C" int shr_group_norm_relu_supported(int C, int G) { return shr::gn_supported(C, G) ? 1 : 0; }
@@ -250,7 +255,6 @@ extern "C" int shr_group_norm_relu_bwd(const float *x, const float *pre_bias, co
                      (hipStream_t)stream, x, pre_bias, dy, gamma, beta, mean, rstd, C, HW, G, dx, dgamma_partial,
                      dbeta_partial, dpre_partial);
   if (dgamma && dbeta)
-    hipLaunchKernelGGL(group_norm_param_grad_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
-                       dgamma_partial, dbeta_partial, dpre_partial, N, C, dgamma, dbeta, dpre);
+    gn_launch_param_grad(dgamma_partial, dbeta_partial, dpre_partial, N, C, dgamma, dbeta, dpre, (hipStream_t)stream);
   return (int)hipGetLastError();
 }

@@ -146,13 +146,16 @@ def _unwrap(m):
 
 class Engine:
     """opts: the reference's argparse namespace (network/run_engine.py:10-31) plus the
-    optional attributes image_size, log_every, real_batch, synt_batch, steps_per_epoch, num_workers.
+    optional attributes image_size, log_every, real_batch, synt_batch, steps_per_epoch, num_workers, amp.
     Datasets default to the NYU shards under opts.dataset_dir/{train,test}; any
     Dataset yielding (dms [V,S,S] mm, gt_joints [V,36,3], cam [V,4,4], inv_cam [V,4,4])
     can be passed instead."""
 
     def __init__(self, opts, mesh=None, real_train_dataset=None, real_eval_dataset=None, device=None,
                  prior_loss=None, pose_denoiser=None):
+        amp = getattr(opts, 'amp', None)
+        if amp not in (None, 'bf16'):
+            raise ValueError("opts.amp must be None or 'bf16', not %r" % (amp,))
         self.env = DistEnv(device)
         dev = self.env.device
         if getattr(opts, 'deterministic', False):
@@ -168,7 +171,10 @@ class Engine:
         S = getattr(opts, 'image_size', 64)
         self.constant = Constant(mesh, S)
         c = self.constant
-        self.network = HeatmapEstimationNetwork(c.heatmap_size, c.depth_scale, c.num_joint, opts.num_stacks).to(dev)
+        # opts.amp: None (fp32 throughout) or 'bf16': the hourglass under bf16 autocast (criterion.py).  Parameters,
+        # optimizer state, checkpoints and DDP buckets stay fp32; bf16 has fp32's exponent range, so no gradient scaler.
+        self.network = HeatmapEstimationNetwork(c.heatmap_size, c.depth_scale, c.num_joint, opts.num_stacks,
+                                                amp_dtype=torch.bfloat16 if amp == 'bf16' else None).to(dev)
         if dev.type == 'cuda':
             # MIOpen's NHWC kernels: hourglass fwd+bwd on 123 crops 25.0 -> 14.0 ms on MI355X (fp32, same math)
             self.network = self.network.to(memory_format=torch.channels_last)

@@ -1794,8 +1794,8 @@ def heatmap_render(T, kp_start, kp_bone, kp_wv, right_hand, camera, rand_f, S, s
 
 
 def group_norm_relu_supported(x, num_groups):
-    """True when the NHWC GroupNorm+ReLU kernels take this activation (CUDA fp32, channels-last)."""
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] > 0
+    """True when the NHWC GroupNorm+ReLU kernels take this activation (CUDA fp32 or bf16, channels-last)."""
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 4 and x.shape[0] > 0
             and x.is_contiguous(memory_format=torch.channels_last)
             and bool(_lib.lib().shr_group_norm_relu_supported(int(x.shape[1]), int(num_groups))))
 
@@ -1804,20 +1804,23 @@ class GroupNormReLU(torch.autograd.Function):
     """relu(group_norm(x + pre_bias, G, weight, bias, eps)) on channels-last activations
     (network/hourglass.py:28-31), one kernel per direction.  `pre_bias` [C] (optional) is the bias of the
     convolution that produced x: the convolution is then run WITHOUT its bias, and this op's backward returns
-    the bias gradient with dx (two launches and one reduction less per convolution)."""
+    the bias gradient with dx (two launches and one reduction less per convolution).
+    bf16 x (the hourglass under autocast): the bf16 kernel pair -- y, the saved x, dy and dx are bf16 channels-last,
+    the parameters (fp32 master copies), mean, rstd and the parameter gradients fp32; the arithmetic is fp32.
+    No autocast decorator: the Function reads x.dtype itself and takes the parameters as they are."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, num_groups, eps, pre_bias=None):
         N, C, H, W = x.shape
-        weight, bias = weight.contiguous(), bias.contiguous()
-        pre = None if pre_bias is None else pre_bias.contiguous()
+        weight, bias = weight.float().contiguous(), bias.float().contiguous()
+        pre = None if pre_bias is None else pre_bias.float().contiguous()
+        fwd = _lib.lib().shr_group_norm_relu_bf16_fwd if x.dtype == torch.bfloat16 else _lib.lib().shr_group_norm_relu_fwd
         with _on(x.device):
             y = torch.empty_like(x, memory_format=torch.channels_last)
             mean = torch.empty((N, num_groups), dtype=torch.float32, device=x.device)
             rstd = torch.empty((N, num_groups), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().shr_group_norm_relu_fwd(_ptr(x), _ptr(pre), _ptr(weight), _ptr(bias), N, C, H * W,
-                                                          num_groups, float(eps), _ptr(y), _ptr(mean), _ptr(rstd),
-                                                          _stream()), "shr_group_norm_relu_fwd")
+            _lib.check(fwd(_ptr(x), _ptr(pre), _ptr(weight), _ptr(bias), N, C, H * W, num_groups, float(eps), _ptr(y),
+                           _ptr(mean), _ptr(rstd), _stream()), "shr_group_norm_relu_fwd")
         ctx.save_for_backward(x, weight, bias, mean, rstd, pre)
         ctx.num_groups = num_groups
         return y
@@ -1826,19 +1829,17 @@ class GroupNormReLU(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, bias, mean, rstd, pre = ctx.saved_tensors
         N, C, H, W = x.shape
-        dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        bwd = _lib.lib().shr_group_norm_relu_bf16_bwd if x.dtype == torch.bfloat16 else _lib.lib().shr_group_norm_relu_bwd
         k = 2 if pre is None else 3
         with _on(x.device):
             dx = torch.empty_like(x, memory_format=torch.channels_last)
             part = torch.empty((k, N, C), dtype=torch.float32, device=x.device)     # per-sample partials (workspace)
             dgb = torch.empty((k, C), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().shr_group_norm_relu_bwd(_ptr(x), _ptr(pre), _ptr(dy), _ptr(weight), _ptr(bias),
-                                                          _ptr(mean), _ptr(rstd), N, C, H * W, ctx.num_groups, _ptr(dx),
-                                                          _ptr(part[0]), _ptr(part[1]),
-                                                          _ptr(part[2]) if pre is not None else None,
-                                                          _ptr(dgb[0]), _ptr(dgb[1]),
-                                                          _ptr(dgb[2]) if pre is not None else None,
-                                                          _stream()), "shr_group_norm_relu_bwd")
+            _lib.check(bwd(_ptr(x), _ptr(pre), _ptr(dy), _ptr(weight), _ptr(bias), _ptr(mean), _ptr(rstd), N, C, H * W,
+                           ctx.num_groups, _ptr(dx), _ptr(part[0]), _ptr(part[1]),
+                           _ptr(part[2]) if pre is not None else None, _ptr(dgb[0]), _ptr(dgb[1]),
+                           _ptr(dgb[2]) if pre is not None else None, _stream()), "shr_group_norm_relu_bwd")
         return dx, dgb[0], dgb[1], None, None, (dgb[2] if pre is not None else None)
 
 
@@ -1856,16 +1857,20 @@ def group_norm_relu(x, gn, pre_bias=None):
 
 def conv_then_group_norm_relu(x, conv, gn):
     """relu(gn(conv(x))) with the convolution's bias folded into the normalisation kernel when that kernel will
-    take conv's output (NHWC fp32 on the GPU, supported channel counts): conv runs bias-free."""
+    take conv's output (NHWC fp32 or bf16 on the GPU, supported channel counts): conv runs bias-free.  Under CUDA
+    autocast to bf16 the convolution's output is bf16 whatever x is; it then feeds the bf16 kernels and conv.bias
+    (fp32) rides as their pre_bias."""
     # (F.conv2d below bypasses conv.forward: only for a plain zero-padded convolution without hooks or
     # parametrizations; the kernel reads the bias 16 bytes at a time)
     plain = (conv.padding_mode == 'zeros' and not conv._forward_hooks and not conv._forward_pre_hooks
              and not getattr(conv, 'parametrizations', None) and conv.bias is not None
              and conv.bias.data_ptr() % 16 == 0 and conv.bias.is_contiguous())
-    if (FUSED_GROUP_NORM_RELU and gn.affine and plain and x.is_cuda and x.dtype == torch.float32
+    if (FUSED_GROUP_NORM_RELU and gn.affine and plain and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
             and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
             and bool(_lib.lib().shr_group_norm_relu_supported(int(conv.out_channels), int(gn.num_groups)))):
         y = torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        if y.dtype == torch.bfloat16:      # (a one-channel input leaves the layout to the solver: one copy, not torch's path)
+            y = y.contiguous(memory_format=torch.channels_last)
         if group_norm_relu_supported(y, gn.num_groups):
             return GroupNormReLU.apply(y, gn.weight, gn.bias, gn.num_groups, gn.eps, conv.bias)
         return torch.nn.functional.relu(gn(y + conv.bias.view(1, -1, 1, 1)))

@@ -37,6 +37,8 @@ def build_parser():
                    help='deterministic MIOpen solvers (run-to-run reproducible hourglass gradients)')
     p.add_argument('--miopen_find', default=False, action='store_true',
                    help='let MIOpen time every convolution shape once and keep the fastest solver (~25 s at start-up, -8 %% per step)')
+    p.add_argument('--amp', default=None, choices=['bf16'],
+                   help='run the hourglass under bf16 autocast (training and evaluation); parameters and losses stay fp32')
     return p
 
 
