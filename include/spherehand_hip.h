@@ -763,6 +763,69 @@ int shr_sil_cover_bwd(const float *observed, float obs_fg_max, const int32_t *d2
                       const int32_t *owner, const float *vertices, const int32_t *faces, const float *grad_dist, int B,
                       int NV, int F, int W, int H, float max_dist, float *grad_vertices, void *workspace, void *stream);
 
+/* Mesh data-to-model distance: every observed 3-D point to its closest point on the triangles, at any distance and in
+ * x, y and z -- the ICP term of a mesh fit, the direction DataToModelLoss (mesh/render.py:93-142) runs for spheres.
+ *   shr_mesh_d2m_fwd   observed[B,H,W] fp32; vertices[B,NV,4] fp32 (x, y, z in model space, the 4th float ignored,
+ *       16-byte aligned); faces[F,3] int32 as given (the distance does not depend on winding; `face` indexes these
+ *       rows); ax, bx, ay, by; fg_max; max_dist >= 0, +inf allowed (SHR_EINVAL otherwise).
+ *       Points.  Pixel (row i, column j) is a DATA POINT iff observed < fg_max (a NaN is none: shr_dt_fwd's site rule).
+ *       Its point is p = (ax (float)j + bx, ay (float)i + by, observed), one rounding per written operation.
+ *       (1, 0, 1, 0) is the raster's pixel space (tri_face.h), (300/W, -150, 300/H, -150) the reference's millimetre
+ *       grid, (5, 0, 5, 0) puts a 128 x 128 observation over the 640 x 640 raster.
+ *       Per point and face with corners a, b, c (the vertices of faces[f,0..2]), all fp32, one correctly rounded
+ *       operation per written operator, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z:
+ *         ab = b - a;  ac = c - a;  ap = p - a;  bp = ap - ab;  cp = ap - ac
+ *         d1 = dot(ab, ap);  d2 = dot(ac, ap);  d3 = dot(ab, bp);  d4 = dot(ac, bp);  d5 = dot(ab, cp);  d6 = dot(ac, cp)
+ *         vc = d1 d4 - d3 d2;  vb = d5 d2 - d1 d6;  va = d3 d6 - d5 d4;  e43 = d4 - d3;  e56 = d5 - d6
+ *       The FIRST of the seven regions whose test holds gives (nv, dv, nw, dw):
+ *         A    d1 <= 0 and d2 <= 0                     (0, 1, 0, 1)
+ *         B    d3 >= 0 and d4 <= d3                    (1, 1, 0, 1)
+ *         AB   vc <= 0 and d1 >= 0 and d3 <= 0         (d1, d1 - d3, 0, 1)
+ *         C    d6 >= 0 and d5 <= d6                    (0, 1, 1, 1)
+ *         AC   vb <= 0 and d2 >= 0 and d6 <= 0         (0, 1, d2, d2 - d6)
+ *         BC   va <= 0 and e43 >= 0 and e56 >= 0       (0, 1, e43, e43 + e56), and v below is 1 - w instead
+ *         in   otherwise                               (vb, (va + vb) + vc, vc, (va + vb) + vc)
+ *         v = nv / dv;  w = nw / dw;  (BC: v = 1 - w);  v = v > 1 ? 1 : v;  v = v < 0 ? 0 : v;  the same for w
+ *         e = ap - (v ab + w ac) per component (two products, their sum, the difference);  d2 = dot(e, e)
+ *       The closest point is a + v ab + w ac with v, w in [0, 1] whatever the roundings decided (a NaN passes the
+ *       two selects).  A zero-area face falls into a vertex or an edge region: it gives the distance to its segment or
+ *       point, or -- where the edge's denominator is 0, as with two coincident corners -- 0 / 0, a NaN d2; a NaN
+ *       operand gives a NaN d2, an infinite one a NaN or +inf.  Neither is ever taken.
+ *       Selection.  best = +inf, face = -1; for f ascending, face f is taken iff its three ids lie in [0, NV) and
+ *       d2 < best.  A NaN d2 is never taken, equal distances keep the smallest f.  However the kernels split the
+ *       faces, the result is that of this serial rule: partial results combine by the lexicographic minimum of
+ *       (d2, f).  The kernels skip a face whose bounding sphere cannot beat the current best (DESIGN.md 4.4j states
+ *       the margin); the outputs are bit-identical with and without that.
+ *       -> dist[B,H,W] fp32 = fminf(sqrtf(best), max_dist) at a data point with a face, 0 at a pixel that is no data
+ *       point and at a data point for which no face was taken; face[B,H,W] int32, -1 where dist has no face.  Every
+ *       element is written.  No reduction over memory: bitwise reproducible, independent of B and the launch shape.
+ *       workspace: 16-byte aligned, shr_mesh_d2m_workspace_bytes(B, F) bytes (-1 on a negative size): 48 bytes per
+ *       (crop, face), written by the call before it is read.
+ *   shr_mesh_d2m_bwd   dist, face: the forward's maps (or any maps: every index is checked); grad_dist[B,H,W] ->
+ *       grad_vertices[B,NV,4] = (d/dx, d/dy, d/dz, 0) of sum grad_dist dist, every element written.  A pixel
+ *       contributes iff it is a data point, f = face lies in [0, F), the ids of faces[f] lie in [0, NV),
+ *       grad_dist != 0 and 0 < dist < max_dist (a saturated or a zero distance is a constant).  In fp64 from the fp32
+ *       p (computed as above) and corners: the seven regions above decided in fp64 (A, B, AB, C, AC, BC, in; no
+ *       clamp), the closest point c = (1 - v - w) a + v b + w c as ap - (v ab + w ac) = p - c, n = |p - c|; n == 0 or
+ *       not finite: nothing.  Corner k with weight w_k = (1 - v - w, v, w) takes -grad_dist w_k (p - c) / n: the
+ *       closest point is continuous across the regions, so the fp64 decisions need not agree with the fp32 ones.
+ *       The sums are 64-bit fixed point in a per-crop unit computed on the device (at most 3 W H terms per
+ *       accumulator): bitwise reproducible, independent of the batch and of the launch shape, no host
+ *       synchronisation.  workspace: 16-byte aligned, shr_mesh_d2m_bwd_workspace_bytes(B, NV) bytes (-1 on a negative
+ *       size), cleared by the call itself.
+ *   1 <= H, W <= 2048, B <= 65535, 3 NV and 3 F < 2^31 (SHR_ETOOLARGE beyond); NV >= 1, F >= 0 (F == 0: every dist 0,
+ *   every face -1); B == 0 is a no-op; NULLs (faces may be NULL when F == 0) and misaligned pointers (4 bytes;
+ *   vertices, grad_vertices and workspace 16): SHR_EINVAL. */
+long long shr_mesh_d2m_workspace_bytes(int B, int F);
+int shr_mesh_d2m_fwd(const float *observed, const float *vertices, const int32_t *faces, int B, int NV, int F, int W,
+                     int H, float ax, float bx, float ay, float by, float fg_max, float max_dist, float *dist,
+                     int32_t *face, void *workspace, void *stream);
+long long shr_mesh_d2m_bwd_workspace_bytes(int B, int NV);
+int shr_mesh_d2m_bwd(const float *observed, const float *vertices, const int32_t *faces, const float *dist,
+                     const int32_t *face, const float *grad_dist, int B, int NV, int F, int W, int H, float ax,
+                     float bx, float ay, float by, float fg_max, float max_dist, float *grad_vertices, void *workspace,
+                     void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

@@ -112,6 +112,10 @@ SIGNATURES = {
     "shr_sil_cover_fwd": ([_vp, _f, _vp, _i, _i, _i, _f, _vp, _vp], _i),
     "shr_sil_cover_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "shr_sil_cover_bwd": ([_vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp], _i),
+    "shr_mesh_d2m_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_mesh_d2m_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp], _i),
+    "shr_mesh_d2m_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_mesh_d2m_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp], _i),
     "shr_fk_fwd":([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -1,5 +1,5 @@
 // fixed_point.h -- the deterministic gradient sums of the backward kernels (mesh_depth_bwd.hip, tri_antialias.hip,
-// tri_interp.hip, sil_cover.hip):
+// tri_interp.hip, sil_cover.hip, mesh_d2m.hip):
 // clear, crop maxima, 64-bit fixed-point sums and the conversion to fp32, generic over a tap walker (Taps below).
 //
 // Sums: every (tap, corner, coordinate) term is a 64-bit FIXED-POINT integer in a per-crop power-of-two unit taken from

@@ -1,7 +1,8 @@
 // tri_tap.h -- what the differentiable triangle family's backwards share about ONE face at ONE pixel it owns, stated once
 // for mesh_depth_bwd.hip (MeshTaps, PixelTaps), tri_interp.hip (the forward and its three walkers), tri_antialias.hip
-// (pair_blend's front face) and sil_cover.hip (CoverTaps):
+// (pair_blend's front face), sil_cover.hip (CoverTaps) and mesh_d2m.hip (the face records, D2mTaps):
 //   tri_corners     the checked gather of an indexed face's corners
+//   face_points     the same for a unit that measures 3-D distances to the face (mesh_d2m.hip)
 //   owned_tap       the forward's fp32 clamp decisions (tri_face.h) and the fp64 weights over the x-sorted corners
 //   live_tap        the two together under the interpolation's rule for a live pixel
 //   weight_chain    d w_a = (d n_a - w_a d den) / den: per-weight coefficients -> the sorted corners' (x, y) gradient
@@ -32,6 +33,13 @@ __device__ __forceinline__ bool tri_corners(const float4 *__restrict__ verts, co
     fv[3 * k] = v.x; fv[3 * k + 1] = v.y; fv[3 * k + 2] = v.z;
   }
   return true;
+}
+
+// The same gather for a unit that takes a face's corners as 3-D points and no owned tap (mesh_d2m.hip: the face records
+// of the closest-point search and D2mTaps): the name says that nothing of the raster's pixel rule is implied.
+__device__ __forceinline__ bool face_points(const float4 *__restrict__ verts, const int *__restrict__ faces, int NV, int F,
+                                            int f, float (&fv)[9], int (&id)[3]) {
+  return tri_corners(verts, faces, NV, F, f, fv, id);
 }
 
 // One owned pixel for a backward.  Everything is over the SORTED corners: sorted corner a is corner order[a] of fv.

@@ -1690,6 +1690,84 @@ class SilhouetteCover(torch.autograd.Function):
         return _grad_as_given(ctx, g), None, None, None, None, None, None, None
 
 
+def _d2m_args(observed, vertices, faces, pixel_to_model, max_dist):
+    _check_input(observed, "observed")
+    if observed.dim() != 3 or observed.shape[1] < 1 or observed.shape[2] < 1:
+        raise RuntimeError("observed must be [B,H,W] with H, W >= 1")
+    Bv, NV, F = _indexed_shape(vertices, faces)
+    if Bv != observed.shape[0] or NV < 1 or vertices.device != observed.device or faces.device != observed.device:
+        raise RuntimeError("vertices must be [B,NV,4] with observed's B and NV >= 1, vertices and faces on its device")
+    try:
+        ax, bx, ay, by = (float(t) for t in pixel_to_model)
+    except (TypeError, ValueError):
+        raise RuntimeError("pixel_to_model must be four numbers (ax, bx, ay, by): x = ax j + bx, y = ay i + by")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise RuntimeError("max_dist must be >= 0 (inf: no saturation), not %r" % (max_dist,))
+    return observed.shape[0], observed.shape[1], observed.shape[2], NV, F, (ax, bx, ay, by), max_dist
+
+
+def mesh_data_to_model(observed, vertices, faces, pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf")):
+    """The mesh data-to-model distance (include/spherehand_hip.h, shr_mesh_d2m_fwd): observed [B,H,W] fp32, vertices
+    [B,NV,4] fp32 in model space, faces [F,3] int32 as given, pixel_to_model = (ax, bx, ay, by) -> (dist [B,H,W] fp32, face
+    [B,H,W] int32): at every pixel with observed < fg_max the distance from (ax j + bx, ay i + by, observed) to the closest
+    point of the closest triangle, saturated at max_dist, and that triangle's row in faces; 0 and -1 elsewhere."""
+    B, H, W, NV, F, p2m, max_dist = _d2m_args(observed, vertices, faces, pixel_to_model, max_dist)
+    lib = _lib.lib()
+    with _on(observed.device):
+        dist = torch.empty((B, H, W), dtype=torch.float32, device=observed.device)
+        face = torch.empty((B, H, W), dtype=torch.int32, device=observed.device)
+        ws = torch.empty((max(16, lib.shr_mesh_d2m_workspace_bytes(B, F)),), dtype=torch.uint8, device=observed.device)
+        _lib.check(lib.shr_mesh_d2m_fwd(_ptr(observed), _ptr(vertices), _ptr(faces), B, NV, F, W, H, *p2m, float(fg_max),
+                                        max_dist, _ptr(dist), _ptr(face), _ptr(ws), _stream()), "shr_mesh_d2m_fwd")
+    return dist, face
+
+
+def mesh_data_to_model_bwd(observed, vertices, faces, dist, face, grad_dist, pixel_to_model=(1.0, 0.0, 1.0, 0.0),
+                           fg_max=1000.0, max_dist=float("inf")):
+    """mesh_data_to_model's backward (include/spherehand_hip.h, shr_mesh_d2m_bwd): dist, face its outputs, grad_dist
+    [B,H,W] -> grad_vertices [B,NV,4] = (d/dx, d/dy, d/dz, 0): every data point with 0 < dist < max_dist pushes the three
+    corners of its face away from itself (a descent step pulls them towards it) with the closest point's weights;
+    deterministic fixed-point sums."""
+    B, H, W, NV, F, p2m, max_dist = _d2m_args(observed, vertices, faces, pixel_to_model, max_dist)
+    _check_input(dist, "dist")
+    _check_input(face, "face", torch.int32)
+    _check_input(grad_dist, "grad_dist")
+    for t, name in ((dist, "dist"), (face, "face"), (grad_dist, "grad_dist")):
+        if t.shape != observed.shape or t.device != observed.device:
+            raise RuntimeError("%s must be [B,H,W] as observed, on its device" % name)
+    lib = _lib.lib()
+    with _on(observed.device):
+        out = torch.empty((B, NV, 4), dtype=torch.float32, device=observed.device)
+        ws = torch.empty((max(16, lib.shr_mesh_d2m_bwd_workspace_bytes(B, NV)),), dtype=torch.uint8, device=observed.device)
+        _lib.check(lib.shr_mesh_d2m_bwd(_ptr(observed), _ptr(vertices), _ptr(faces), _ptr(dist), _ptr(face), _ptr(grad_dist),
+                                        B, NV, F, W, H, *p2m, float(fg_max), max_dist, _ptr(out), _ptr(ws), _stream()),
+                   "shr_mesh_d2m_bwd")
+    return out
+
+
+class MeshDataToModel(torch.autograd.Function):
+    """mesh_data_to_model with a backward: (observed [B,H,W], vertices [B,NV,3 or 4] model space, faces [F,3] int32,
+    pixel_to_model, fg_max, max_dist) -> dist [B,H,W].  Differentiable w.r.t. vertices[..., :3]; the closest face of every
+    point and the closest point's weights on it are held fixed (the envelope rule: the distance is a minimum over both)."""
+
+    @staticmethod
+    def forward(ctx, observed, vertices, faces, pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf")):
+        v4, ctx.width4 = vertices4(vertices)
+        observed = observed.contiguous()
+        dist, face = mesh_data_to_model(observed, v4, faces, pixel_to_model, fg_max, max_dist)
+        ctx.args = (tuple(pixel_to_model), fg_max, max_dist)
+        ctx.save_for_backward(observed, v4, faces, dist, face)
+        ctx.mark_non_differentiable(face)
+        return dist, face
+
+    @staticmethod
+    def backward(ctx, grad_dist, _grad_face):
+        observed, v4, faces, dist, face = ctx.saved_tensors
+        g = mesh_data_to_model_bwd(observed, v4, faces, dist, face, grad_dist.contiguous().float(), *ctx.args)
+        return None, _grad_as_given(ctx, g), None, None, None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

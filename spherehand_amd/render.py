@@ -481,6 +481,46 @@ class SilhouetteCoverage(nn.Module):
         return self.forward(vertices).mean()
 
 
+class MeshDataToModelLoss(nn.Module):
+    """DataToModelLoss (mesh/render.py:93-142) for the triangle mesh: the distance from every observed 3-D point to its
+    closest point on the mesh surface, at any distance and in x, y and z (ops.MeshDataToModel; include/spherehand_hip.h
+    states it).  forward(observed[B,H,W], vertices[B,NV,3 or 4] in model space) -> the mean over ALL B H W pixels of the
+    distance saturated at max_dist, a pixel that is no data point counting as 0: the reference's normalisation.
+    distances(observed, vertices) -> (dist [B,H,W], face [B,H,W] int32, rows of np_faces, -1 without one).
+    pixel_to_model = (ax, bx, ay, by): pixel (row i, column j) is the point (ax j + bx, ay i + by, observed);
+    (1, 0, 1, 0) is the raster's pixel space, MeshDataToModelLoss.reference_grid(width, height) the reference's
+    millimetre grid.  A pixel is a data point iff observed < fg_max.  The default fg_max is the fp32 successor of 99,
+    99.00000762939453 = 99 + 2^-17: for every fp32 value, observed < fg_max iff observed <= 99 iff not observed > 99,
+    the reference's background rule (mesh/render.py:138); a NaN is no data point here, where the reference carries it
+    into the mean.  `np_faces` is used as given -- the distance does not depend on winding -- and is not modified."""
+
+    REFERENCE_FG_MAX = float(np.nextafter(np.float32(99.0), np.float32(np.inf)))
+
+    def __init__(self, width, height, np_faces, pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=REFERENCE_FG_MAX, max_dist=50.0):
+        super().__init__()
+        self.width = width
+        self.height = height
+        self.pixel_to_model = tuple(float(t) for t in pixel_to_model)
+        self.fg_max = float(fg_max)
+        self.max_dist = float(max_dist)
+        faces = np.array(np_faces, dtype=np.int64, copy=True).reshape(-1, 3)
+        self.register_buffer('faces_i32', torch.from_numpy(faces.astype(np.int32)).contiguous())
+
+    @staticmethod
+    def reference_grid(width, height):
+        """(ax, bx, ay, by) of mesh/render.py:99-100: x = (j - width / 2) 300 / width, y = (i - height / 2) 300 / height."""
+        return (300.0 / width, -150.0, 300.0 / height, -150.0)
+
+    def distances(self, observed, vertices):
+        if observed.dim() != 3 or tuple(observed.shape[1:]) != (self.height, self.width):
+            raise RuntimeError("MeshDataToModelLoss takes observed [B,%d,%d]" % (self.height, self.width))
+        return ops.MeshDataToModel.apply(observed.detach().float(), vertices.float(), self.faces_i32, self.pixel_to_model,
+                                         self.fg_max, self.max_dist)
+
+    def forward(self, observed, vertices):
+        return self.distances(observed, vertices)[0].mean()
+
+
 class SparseSkinning(nn.Module):
     """LinearBlendSkinning (+ optional orthographic camera) of the full mesh on the
     HIP kernel: forward(T[B,17,4,4], camera=None, rand_f=None) -> [B,NV,4].
