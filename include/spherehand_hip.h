@@ -826,6 +826,39 @@ int shr_mesh_d2m_bwd(const float *observed, const float *vertices, const int32_t
                      float bx, float ay, float by, float fg_max, float max_dist, float *grad_vertices, void *workspace,
                      void *stream);
 
+/* Normal map of a depth image, and its backward to the depth (a capability the reference does not have: the data side
+ * of an orientation term -- render.MeshNormalRaster is its model side -- and, through the backward, an orientation term
+ * for any rendered depth, the spheres' included).
+ *   shr_depth_normals_fwd   depth[B,H,W] fp32 -> normals[B,3,H,W].  In fp32 with one rounding per written operator (no
+ *       contraction), for pixel (row i, column j) with c = depth[i,j]:
+ *         1. SITE iff c < fg_max (shr_dt_fwd's rule: a NaN is no site).  A pixel that is no site gets (0, 0, 0).
+ *         2. a neighbour value n is USABLE iff it lies inside the image, n < fg_max and fabsf(n - c) <= max_step (the
+ *            discontinuity rule; a NaN difference is not usable; max_step = +inf keeps every foreground neighbour).
+ *         3. horizontal difference, l = depth[i,j-1], r = depth[i,j+1]:  both usable: dx = r - l, hx = 2;  only r:
+ *            dx = r - c, hx = 1;  only l: dx = c - l, hx = 1;  neither: the pixel has no normal, (0, 0, 0).
+ *         4. vertical difference, u = depth[i-1,j], d = depth[i+1,j]: the same rule; both usable: dy = d - u, hy = 2.
+ *         5. wx = hx sx, wy = hy sy: the widths of the two differences in model units (exact: h is 1 or 2).
+ *            N = (dx wy, dy wx, -(wx wy)): the cross product of the tangents (wx, 0, dx) and (0, wy, dy), turned towards
+ *            the camera.  On z = a x + b y + c it is proportional to (a, b, -1): MeshNormalRaster's orientation, z <= 0.
+ *         6. n = unit3(N): step 3 of shr_tri_vertex_normals_fwd, the same device function, with its ZERO RULE.
+ *       W == 1 or H == 1 is legal and gives zeros everywhere.  normals must not overlap depth.
+ *   shr_depth_normals_bwd   grad_normals[B,3,H,W] -> grad_depth[B,H,W]: the exact derivative of 1 .. 6 with every fp32
+ *       decision held fixed (site, usable, the case of each axis, the zero rule), evaluated in fp64 from the fp32 depths
+ *       and rounded to fp32 once per element.  A gather, no atomics: grad_depth[p] is the fp64 sum, in this order, of the
+ *       contributions of the normals at p, at its left, right, upper and lower neighbour -- those inside the image that
+ *       have a normal.  For such a pixel q:  N, n = N / |N| in fp64;  G = (g - n (n . g)) / |N| (as shr_unit3_maps_bwd; 0
+ *       when the fp64 |N|^2 is 0 or not finite);  d/d dx = G_x wy,  d/d dy = G_y wx;  dx and dy hand these on to l, r, c
+ *       (u, d, c) with the signs of q's case in 3. and 4.  Every element of grad_depth is written, 0 where nothing
+ *       contributes (every pixel that is no site).  grad_depth must not overlap depth or grad_normals.  Bitwise
+ *       reproducible, independent of B and of the launch shape; no workspace, no host synchronisation.
+ *   sx, sy finite and > 0; fg_max and max_step not NaN, max_step >= 0 (+inf allowed): SHR_EINVAL otherwise.  1 <= W, H
+ *   and B, W, H <= 65535 (SHR_ETOOLARGE beyond); B == 0 is a no-op; NULL, misaligned (4 bytes) or overlapping pointers:
+ *   SHR_EINVAL. */
+int shr_depth_normals_fwd(const float *depth, int B, int W, int H, float fg_max, float sx, float sy, float max_step,
+                          float *normals /* [B,3,H,W] */, void *stream);
+int shr_depth_normals_bwd(const float *depth, const float *grad_normals /* [B,3,H,W] */, int B, int W, int H,
+                          float fg_max, float sx, float sy, float max_step, float *grad_depth /* [B,H,W] */, void *stream);
+
 /* Key-point skinning -> sphere records -----------------------------------------------------
  * Replaces, inside HandBallPrimitiveRender (mesh/render.py:65-88), the LinearBlendSkinning of the key-points (each
  * bound to ONE bone with weight 1: mesh/pointTransformation.py:39-46 reduces to p = T[bone[j]] @ wv[j], x -> -x for

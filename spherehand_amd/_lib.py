@@ -116,6 +116,8 @@ SIGNATURES = {
     "shr_mesh_d2m_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp], _i),
     "shr_mesh_d2m_bwd_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "shr_mesh_d2m_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp], _i),
+    "shr_depth_normals_fwd": ([_vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp], _i),
+    "shr_depth_normals_bwd": ([_vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp], _i),
     "shr_fk_fwd":([_vp, _i, _vp, _vp, _vp, _vp], _i),
     "shr_fk_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_pose_spheres_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp], _i),

@@ -12,22 +12,11 @@
 //                  the two cross products in fp64, one rounding to fp32.
 //   unit3 maps     one thread per pixel (four with 16-byte aligned planes): one read and one write of the planes.
 #include "common.h"
+#include "unit3.h"   // unit3 and its zero rule
 
 namespace shr {
 
 constexpr int kNrmThreads = 256;
-constexpr float kNrmMaxFinite = 3.4028234663852886e38f;
-
-// n = N / sqrt((Nx Nx + Ny Ny) + Nz Nz) with the IEEE root and three IEEE divisions; false (n = 0, nothing flows back)
-// unless the sum of squares is positive and finite
-__device__ __forceinline__ bool unit3(const float (&N)[3], float (&n)[3]) {
-  const float s = (N[0] * N[0] + N[1] * N[1]) + N[2] * N[2];
-  const bool live = s > 0.f && s <= kNrmMaxFinite;
-  const float r = sqrtf(live ? s : 1.f);
-#pragma unroll
-  for (int d = 0; d < 3; d++) n[d] = live ? N[d] / r : 0.f;
-  return live;
-}
 
 struct NormalTables {
   const int *faces;        // [F][3]

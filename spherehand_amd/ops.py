@@ -1768,6 +1768,74 @@ class MeshDataToModel(torch.autograd.Function):
         return None, _grad_as_given(ctx, g), None, None, None, None
 
 
+def _depth_normals_args(depth, scale, max_step):
+    _check_input(depth, "depth")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise RuntimeError("depth must be [B,H,W] with H, W >= 1")
+    try:
+        sx, sy = (float(t) for t in scale)
+    except (TypeError, ValueError):
+        raise RuntimeError("scale must be two numbers (sx, sy): the model-space width of a pixel step in x and in y")
+    return depth.shape[0], depth.shape[1], depth.shape[2], sx, sy, float(max_step)
+
+
+def depth_normals(depth, fg_max, scale=(1.0, 1.0), max_step=float("inf"), out=None):
+    """The unit normal map of a depth image (include/spherehand_hip.h, shr_depth_normals_fwd): depth [B,H,W] fp32 ->
+    [B,3,H,W].  A pixel with depth < fg_max gets the normalised (dx wy, dy wx, -(wx wy)) of its central -- at a border, a
+    hole or a depth step above max_step one-sided -- differences over widths of scale = (sx, sy) model units per pixel;
+    every other pixel, and one with no usable neighbour along an axis, gets (0, 0, 0).  z <= 0: towards the camera.
+    The entry refuses a scale that is not positive and finite, a NaN fg_max or max_step, a negative max_step, and an
+    `out` ([B,3,H,W], where to write) that overlaps depth."""
+    B, H, W, sx, sy, max_step = _depth_normals_args(depth, scale, max_step)
+    if out is not None:
+        _check_input(out, "out")
+        if tuple(out.shape) != (B, 3, H, W) or out.device != depth.device:
+            raise RuntimeError("out must be [B,3,H,W] for depth [B,H,W], on its device")
+    with _on(depth.device):
+        if out is None:
+            out = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
+        _lib.check(_lib.lib().shr_depth_normals_fwd(_ptr(depth), B, W, H, float(fg_max), sx, sy, max_step, _ptr(out),
+                                                    _stream()), "shr_depth_normals_fwd")
+    return out
+
+
+def depth_normals_bwd(depth, grad_normals, fg_max, scale=(1.0, 1.0), max_step=float("inf"), out=None):
+    """depth_normals's backward (include/spherehand_hip.h, shr_depth_normals_bwd): grad_normals [B,3,H,W] -> grad_depth
+    [B,H,W], the exact derivative with the forward's decisions held fixed; 0 at every pixel that is no site.  `out`: where
+    to write (overlapping neither input)."""
+    B, H, W, sx, sy, max_step = _depth_normals_args(depth, scale, max_step)
+    _check_input(grad_normals, "grad_normals")
+    if tuple(grad_normals.shape) != (B, 3, H, W) or grad_normals.device != depth.device:
+        raise RuntimeError("grad_normals must be [B,3,H,W] for depth [B,H,W], on its device")
+    if out is not None:
+        _check_input(out, "out")
+        if out.shape != depth.shape or out.device != depth.device:
+            raise RuntimeError("out must be [B,H,W] as depth, on its device")
+    with _on(depth.device):
+        if out is None:
+            out = torch.empty_like(depth)
+        _lib.check(_lib.lib().shr_depth_normals_bwd(_ptr(depth), _ptr(grad_normals), B, W, H, float(fg_max), sx, sy,
+                                                    max_step, _ptr(out), _stream()), "shr_depth_normals_bwd")
+    return out
+
+
+class DepthNormals(torch.autograd.Function):
+    """depth_normals with a backward: (depth [B,H,W], fg_max, scale, max_step) -> normals [B,3,H,W], differentiable
+    w.r.t. depth; which pixels have a normal and which neighbours each uses are held fixed."""
+
+    @staticmethod
+    def forward(ctx, depth, fg_max, scale=(1.0, 1.0), max_step=float("inf")):
+        depth = depth.contiguous()
+        ctx.args = (fg_max, tuple(scale), max_step)
+        ctx.save_for_backward(depth)
+        return depth_normals(depth, *ctx.args)
+
+    @staticmethod
+    def backward(ctx, grad_normals):
+        depth, = ctx.saved_tensors
+        return depth_normals_bwd(depth, grad_normals.contiguous().float(), *ctx.args), None, None, None
+
+
 def hand_synth(params, offset, offset_inv, rng_state, rand_scale, lbs, faces, camera, out_size, depth_scale, noise,
                sigma_xy, sigma_z, heat=None, src_size=640, clamp_max=100.0):
     """HandSynthesizer.forward in ONE launch (shr_hand_synth_fwd), or None where that kernel does not apply (the caller

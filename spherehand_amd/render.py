@@ -13,6 +13,8 @@ signatures and return values), running on the hand-written HIP kernels.
     MeshNormalRaster         a unit normal map from area-weighted vertex normals, and the depth: gradients reach z
     SilhouetteDistance       the distance of projected points to the observed silhouette: a pull from any distance
     SilhouetteCoverage       its complement: the distance of observed pixels to the rendered silhouette, a pull on the mesh
+    DepthNormalMap           a unit normal map from a depth image, differentiable in the depth: observed or rendered
+    NormalConsistencyLoss    1 - m . o between two normal maps: the orientation term
 """
 import numpy as np
 import torch
@@ -519,6 +521,49 @@ class MeshDataToModelLoss(nn.Module):
 
     def forward(self, observed, vertices):
         return self.distances(observed, vertices)[0].mean()
+
+
+class DepthNormalMap(nn.Module):
+    """The unit normal map of a depth image (ops.DepthNormals; include/spherehand_hip.h, shr_depth_normals_fwd states
+    it): forward(depth[B,H,W]) -> [B,3,H,W].  A pixel is foreground iff depth < fg_max; differences do not cross a
+    background pixel, the image border or a depth step above max_step (one-sided there), and a pixel without a usable
+    neighbour along an axis gets (0, 0, 0), as every background pixel does.  pixel_to_model = (ax, bx, ay, by) has
+    MeshDataToModelLoss's meaning; only ax and ay are used, as the model-space widths of a pixel step: (1, 0, 1, 0) gives
+    the pixel-space normals MeshNormalRaster produces by default, MeshDataToModelLoss.reference_grid metric ones.
+    Orientation as MeshNormalRaster: z <= 0, towards the camera.  Differentiable w.r.t. depth, so it serves an observation
+    (detached) and any rendered depth alike: BallRender, TriangleDepthRaster, AntialiasedDepthRaster,
+    DepthRender(..., differentiable=True)."""
+
+    def __init__(self, fg_max, pixel_to_model=(1.0, 0.0, 1.0, 0.0), max_step=float('inf')):
+        super().__init__()
+        self.fg_max = float(fg_max)
+        ax, _, ay, _ = (float(t) for t in pixel_to_model)
+        self.scale = (ax, ay)
+        self.max_step = float(max_step)
+
+    def forward(self, depth):
+        if depth.dim() != 3:
+            raise RuntimeError("DepthNormalMap takes depth [B,H,W]")
+        return ops.DepthNormals.apply(depth.float(), self.fg_max, self.scale, self.max_step)
+
+
+class NormalConsistencyLoss(nn.Module):
+    """The orientation term of model fitting: forward(model_map[B,3,H,W], observed_map[B,3,H,W]) -> [B], per crop the
+    mean of 1 - m . o over the pixels where both maps are non-zero (0 for a crop without one); loss(...) is the mean over
+    crops.  The maps are MeshNormalRaster's or DepthNormalMap's.  An antialiased outline pixel, shorter than 1, weighs by
+    its coverage.  observed_map gets no gradient.  A composition of torch operations: DESIGN.md 4.4k has its cost next to
+    the normal kernels'."""
+
+    def forward(self, model_map, observed_map):
+        if model_map.dim() != 4 or model_map.shape[1] != 3 or model_map.shape != observed_map.shape:
+            raise RuntimeError("NormalConsistencyLoss takes two maps [B,3,H,W] of one shape")
+        o = observed_map.detach()
+        both = ((model_map.detach() != 0).any(1) & (o != 0).any(1)).to(model_map.dtype)
+        term = (1.0 - (model_map * o).sum(1)) * both
+        return term.sum((1, 2)) / both.sum((1, 2)).clamp(min=1.0)
+
+    def loss(self, model_map, observed_map):
+        return self.forward(model_map, observed_map).mean()
 
 
 class SparseSkinning(nn.Module):
