@@ -901,6 +901,41 @@ int shr_pose_spheres_bwd(const float *params, int B, const float *offset, const 
                          const int32_t *bone_start, const int32_t *bone_points, const float *wv,
                          int right_hand, const float *grad_spheres, float *grad_params, void *stream);
 
+/* Differentiable skinning of the mesh: bone transforms or pose -> vertices, and back ---------
+ * The backward of LinearBlendSkinning.forward (mesh/pointTransformation.py:39-46) and OthographicalProjection.forward
+ * (:84-99) in both modes of shr_lbs_project, and the chain HandTransformationMat.forward
+ * (mesh/kinematicsTransformation.py:157-177) -> skinning -> camera as one launch per direction.  The skin table and the
+ * camera arguments are shr_lbs_project's; rand_f and the table get no gradient.
+ *   shr_lbs_vertices_bwd   grad_vertices[B,NV,4] -> grad_T[B,NB,4,4], shr_lbs_project_bwd's arguments plus `project`.
+ *                          project = 1: shr_lbs_project_bwd's result bit for bit (the same kernel).  project = 0: the
+ *                          derivative of the skinned points, d acc = (+-g.x, g.y, g.z, g.w) (- for the right hand); cx, cy,
+ *                          fx, fy and rand_f are ignored.  Summation order (the contract): one wave per bone, lane l takes
+ *                          the vertices l + 64 n in ascending order and a vertex's entries of the bone in table order, fp64
+ *                          partial sums, the xor butterfly 32, 16 .. 1 over the lanes, one rounding to fp32: bitwise
+ *                          reproducible, independent of the batch.  A bone without an entry gets zeros.
+ *   shr_pose_vertices_fwd  params[B,26] -> vertices[B,NV,4]: the bits of shr_fk_fwd followed by shr_lbs_project, the bone
+ *                          transforms formed in LDS by every workgroup for its crops.  NB is the hand's 17 (offset,
+ *                          offset_inv [17,4,4] as for shr_fk_fwd); a bone number of the table outside [0, 17) is clamped
+ *                          into it.  T: NULL, or [B,17,4,4] (16-byte aligned) to receive shr_fk_fwd's bits as well,
+ *                          written by one workgroup per group of crops.
+ *   shr_pose_vertices_bwd  grad_vertices[B,NV,4] -> grad_params[B,26]: the bits of shr_lbs_vertices_bwd followed by
+ *                          shr_fk_bwd, one workgroup per crop: the skinning sums above (rows 0..2 of each bone, rounded to
+ *                          fp32) stay in LDS and one wave runs shr_fk_bwd's reverse row chain on them.
+ * skin_wv, vertices, grad_vertices 16-byte aligned, grad_params 8-byte aligned, NULL pointers: SHR_EINVAL.  B * NV above
+ * 2^30, B above 2^24 (shr_lbs_vertices_bwd: 2^30): SHR_ETOOLARGE.  B == 0 or NV == 0: SHR_OK, nothing is launched and
+ * nothing written. */
+int shr_lbs_vertices_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
+                         const int32_t *skin_bone, const float *skin_wv, int right_hand, int project, float cx, float cy,
+                         float fx, float fy, const float *rand_f, float *grad_T, void *stream);
+int shr_pose_vertices_fwd(const float *params, int B, const float *offset, const float *offset_inv, int NV,
+                          const int32_t *skin_vertex_start, const int32_t *skin_bone, const float *skin_wv,
+                          int right_hand, int project, float cx, float cy, float fx, float fy, const float *rand_f,
+                          float *vertices, float *T /* may be NULL */, void *stream);
+int shr_pose_vertices_bwd(const float *params, int B, const float *offset, const float *offset_inv, int NV,
+                          const int32_t *skin_vertex_start, const int32_t *skin_bone, const float *skin_wv,
+                          int right_hand, int project, float cx, float cy, float fx, float fy, const float *rand_f,
+                          const float *grad_vertices, float *grad_params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

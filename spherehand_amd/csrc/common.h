@@ -208,6 +208,67 @@ __device__ __forceinline__ float4 lbs_finish(const float (&acc)[4], int right_ha
   if (!has_rand) return make_float4(fx * a0 + cx * acc[3], fy * acc[1] + cy * acc[3], acc[2], acc[3]);
   return make_float4(a0 * rf * fx + cx, acc[1] * rf * fy + cy, acc[2], 1.0f);
 }
+// crops whose bone matrices a skinning workgroup stages in LDS (lbs_project.hip, pose_vertices.hip)
+constexpr int kLbsCrops = 4;
+
+// The skinning + camera backward of ONE bone by ONE wave, shared by lbs_project_bwd_kernel (lbs_project.hip) and the
+// one-launch pose backward (pose_vertices.hip): a[4 r + c] = sum over the skin entries e of bone k of dacc_v(e)[r] *
+// wv_e[c], dacc = d out / d acc of lbs_finish.  Lanes stride over the vertices (v = lane + 64 n), fp64 partial sums, the
+// xor butterfly 32 .. 1: every lane returns the 16 totals, the same bits whatever the batch or the launch.
+struct LbsCamera {
+  int right_hand, project;
+  float cx, cy, fx, fy;
+  bool has_rand;
+  float rf;                           // rand_f[b] (has_rand)
+};
+__device__ __forceinline__ void lbs_bone_grad_wave(double (&a)[16], int k, int lane, const float4 *__restrict__ gv, int NV,
+                                                   const int *__restrict__ vstart, const int *__restrict__ sbone,
+                                                   const float4 *__restrict__ swv, const LbsCamera cam) {
+  const double sgn = cam.right_hand ? -1.0 : 1.0;
+  const double rf = cam.has_rand ? (double)cam.rf : 1.0;
+  const float cx = cam.cx, cy = cam.cy, fx = cam.fx, fy = cam.fy;
+#pragma unroll
+  for (int j = 0; j < 16; j++) a[j] = 0.0;
+  for (int v = lane; v < NV; v += 64) {
+    const int e0 = vstart[v], e1 = vstart[v + 1];
+    int e = e0;
+    while (e < e1 && sbone[e] != k) e++;
+    if (e == e1) continue;
+    const float4 g = gv[v];
+    // d out / d acc (lbs_finish)
+    double d[4];
+    if (!cam.project) {
+      d[0] = sgn * g.x; d[1] = g.y; d[2] = g.z; d[3] = g.w;
+    } else if (!cam.has_rand) {
+      d[0] = sgn * (double)fx * g.x; d[1] = (double)fy * g.y; d[2] = g.z;
+      d[3] = (double)cx * g.x + (double)cy * g.y + (double)g.w;
+    } else {
+      d[0] = sgn * rf * (double)fx * g.x; d[1] = rf * (double)fy * g.y; d[2] = g.z; d[3] = 0.0;
+    }
+    for (; e < e1; e++) {
+      if (sbone[e] != k) continue;
+      const float4 q = swv[e];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        a[4 * r] += d[r] * q.x; a[4 * r + 1] += d[r] * q.y; a[4 * r + 2] += d[r] * q.z; a[4 * r + 3] += d[r] * q.w;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    double t = a[j];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
+    a[j] = t;
+  }
+}
+// entry `lane` (< 16) of the totals, rounded once to fp32
+__device__ __forceinline__ float lbs_bone_grad_entry(const double (&a)[16], int lane) {
+  double t = 0.0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) t = (lane == j) ? a[j] : t;
+  return (float)t;
+}
 
 // inclusive prefix sum over the 64 lanes (4 DPP steps inside each row of 16, then the row totals)
 __device__ __forceinline__ int wave_scan_incl(int v, int lane) {

@@ -1,5 +1,6 @@
 // fk_rows.h -- the row-chain arithmetic of the hand's forward kinematics (fk.hip documents the scheme), shared by the
-// pose kernels (fk.hip) and the one-launch synthesizer (mesh_depth.hip: the rasterizer's workgroup runs its crop's FK).
+// pose kernels (fk.hip), the one-launch synthesizer (mesh_depth.hip: the rasterizer's workgroup runs its crop's FK) and
+// the pose -> vertices pair (pose_vertices.hip: forward and reverse chains around the mesh skinning).
 #pragma once
 #include "common.h"
 
@@ -168,4 +169,100 @@ __device__ __forceinline__ void pose_transforms_wave(const float *__restrict__ p
   }
 }
 
+// The reverse row chain of ONE sample by ONE wave: grad_params[26] (gp) from gT [kBones * 3] = d loss / d T[bone, row < 3, :]
+// in LDS.  Shared by pose_bwd_kernel (fk.hip) and the one-launch pose -> vertices backward (pose_vertices.hip): the same
+// operations, the same bits.  k1 .. k3, t: the lane's bone constants and translation component as the forward loads them;
+// sc [kAngles]: the sample's sincos table, complete and visible to the wave; pbar [6 * 3]: LDS scratch.  `sync` orders the
+// wave's pbar writes before its reads (the caller's choice: a workgroup barrier where the wave is the workgroup).
+template <class Sync>
+__device__ __forceinline__ void pose_reverse_rows(int lane, const BoneConst &k1, const BoneConst &k2, const BoneConst &k3,
+                                                  float t, const Rot *sc, const float4 *gT, float4 *pbar,
+                                                  float *__restrict__ gp, Sync sync) {
+  const int g = lane >> 2, i = lane & 3;
+  const bool chain = lane < 24 && i < 3, finger = chain && g < 5;
+  const int b0 = 2 + 3 * (finger ? g : 0);
+  PalmRow P;
+  float ga0 = 0.f, ga1 = 0.f, ga2 = 0.f, ga3 = 0.f;
+  if (chain) {
+    P = palm_row(i, sc[0], sc[1], sc[2], t);
+    if (!finger) {
+      const float4 x = gT[i], y = gT[3 + i];
+      pbar[15 + i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+    } else {
+      const int a0 = 3 + 4 * g;
+      const bool yaxis = g == 2 || g == 3;
+      const Rot ra = sc[a0], rb = sc[a0 + 1], r2 = sc[a0 + 2], r3 = sc[a0 + 3];
+      // forward, keeping what the adjoints read
+      const float4 w1 = swap_yz(rot_z(swap_yz(row_times(P.r, k1.i0, k1.i1, k1.i2), yaxis), ra), yaxis);
+      const float4 v1 = rot_x(w1, rb);
+      const float4 G1 = row_times(v1, k1.o0, k1.o1, k1.o2);
+      const float4 v2 = rot_x(row_times(G1, k2.i0, k2.i1, k2.i2), r2);
+      const float4 G2 = row_times(v2, k2.o0, k2.o1, k2.o2);
+      const float4 v3 = rot_x(row_times(G2, k3.i0, k3.i1, k3.i2), r3);
+      // reverse
+      float4 Gb = gT[3 * b0 + 6 + i];
+      float4 vb = row_times_adj(Gb, k3.o0, k3.o1, k3.o2);
+      ga3 = rot_x_dangle(vb, v3);
+      float4 ub = row_times_adj(rot_x_adj(vb, r3), k3.i0, k3.i1, k3.i2);
+      Gb = gT[3 * b0 + 3 + i];
+      Gb = make_float4(Gb.x + ub.x, Gb.y + ub.y, Gb.z + ub.z, Gb.w + ub.w);
+      vb = row_times_adj(Gb, k2.o0, k2.o1, k2.o2);
+      ga2 = rot_x_dangle(vb, v2);
+      ub = row_times_adj(rot_x_adj(vb, r2), k2.i0, k2.i1, k2.i2);
+      Gb = gT[3 * b0 + i];
+      Gb = make_float4(Gb.x + ub.x, Gb.y + ub.y, Gb.z + ub.z, Gb.w + ub.w);
+      vb = row_times_adj(Gb, k1.o0, k1.o1, k1.o2);
+      ga1 = rot_x_dangle(vb, v1);
+      const float4 wb = swap_yz(rot_x_adj(vb, rb), yaxis);     // adjoint of w1, in the swapped frame
+      ga0 = rot_z_dangle(wb, swap_yz(w1, yaxis));
+      ub = row_times_adj(swap_yz(rot_z_adj(wb, ra), yaxis), k1.i0, k1.i1, k1.i2);
+      pbar[3 * g + i] = ub;
+    }
+  }
+  // an angle's gradient: the sum over the three rows (lanes 4 g + 0..2; lane 4 g + 3 holds zeros)
+  ga0 = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(ga0));
+  ga1 = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(ga1));
+  ga2 = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(ga2));
+  ga3 = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(ga3));
+  if (lane < 20 && i == 0) {
+    float2 *o = reinterpret_cast<float2 *>(gp + 6 + 4 * g);    // 8-byte aligned: 26 floats per sample
+    o[0] = make_float2(ga0, ga1);
+    o[1] = make_float2(ga2, ga3);
+  }
+  sync();
+  // palm: d loss / d P row i = the palm bones' own gradient + the five fingers', in fixed order
+  float gx = 0.f, gy = 0.f, gz = 0.f;
+  if (chain && g == 5) {
+    float4 Pb = pbar[15 + i];
+#pragma unroll
+    for (int f = 0; f < 5; f++) {
+      const float4 c = pbar[3 * f + i];
+      Pb = make_float4(Pb.x + c.x, Pb.y + c.y, Pb.z + c.z, Pb.w + c.w);
+    }
+    gp[3 + i] = Pb.w;                                           // P = Trans * R: the translation column
+    const Rot rx = sc[0], ry = sc[1], rz = sc[2];
+    Pb.w = 0.f;
+    gx = rot_x_dangle(Pb, P.r);
+    const float4 bb = rot_x_adj(Pb, rx);
+    gy = rot_y_dangle(bb, P.b);
+    const float4 ab = rot_y_adj(bb, ry);
+    // row i of Rz: (c,-s,0) | (s,c,0) | (0,0,d): d/dz = (-s,-c,0) | (c,-s,0) | 0
+    gz = i == 0 ? -(ab.x * rz.s) - ab.y * rz.c : i == 1 ? ab.x * rz.c - ab.y * rz.s : 0.f;
+  }
+  gx = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(gx));
+  gy = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(gy));
+  gz = dpp_add<0x4E, 0xF>(dpp_add<0xB1, 0xF>(gz));
+  if (lane == 20) {
+    gp[0] = gx; gp[1] = gy; gp[2] = gz;
+  }
+}
+
 }  // namespace shr
+
+// the pose entries' common argument rules (fk.hip, pose_vertices.hip)
+static inline int fk_check(const void *params, int B, const void *offset, const void *offset_inv) {
+  if (!params || !offset || !offset_inv || B < 0) return SHR_EINVAL;
+  if ((((uintptr_t)offset | (uintptr_t)offset_inv) & 15u) != 0) return SHR_EINVAL;
+  if (B > (1 << 24)) return SHR_ETOOLARGE;
+  return SHR_OK;
+}

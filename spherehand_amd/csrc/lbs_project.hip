@@ -3,7 +3,8 @@
 // Replaces (reference file:line):
 //   mesh/pointTransformation.py:39-46 LinearBlendSkinning.forward and :84-99
 //   OthographicalProjection.forward                           -> shr_lbs_project
-//   their autograd backward down to the bone transforms       -> shr_lbs_project_bwd
+//   their autograd backward down to the bone transforms       -> shr_lbs_project_bwd (project = 1),
+//                                                                shr_lbs_vertices_bwd (either mode)
 // The per-entry arithmetic (lbs_add_entry, lbs_finish) is common.h's, shared with the fused mesh_lattice_kernel
 // (mesh_depth.hip) and the heat-map renderer (synth_post.hip).
 #include "common.h"
@@ -17,7 +18,6 @@ typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
 // re-read the shared 0.5-MB table for every sample: 21 -> 1x us for 256 crops, round 3).  Visits only the non-zero
 // (bone, vertex) pairs of the reference's dense sum, in ascending bone order (association documented in DESIGN.md);
 // per sample the arithmetic is unchanged.
-constexpr int kLbsCrops = 4;
 __global__ void __launch_bounds__(256)
 lbs_project_kernel(const float *__restrict__ T, int B, int NB, int NV, const int *__restrict__ vstart,
                    const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, int project,
@@ -57,56 +57,20 @@ lbs_project_kernel(const float *__restrict__ T, int B, int NB, int NV, const int
 
 // Skinning + camera backward: grad_T[b][k] = sum over the skin entries e of bone k of dacc_v(e) (x) wv_e.  One workgroup
 // per crop, one wave per bone (bones dealt round robin), lanes striding over the vertices in a fixed assignment, fp64
-// partial sums and a fixed butterfly: the same order whatever the batch -- bitwise reproducible.
+// partial sums and a fixed butterfly (common.h lbs_bone_grad_wave): the same order whatever the batch -- bitwise
+// reproducible.  project = 0: the derivative of the skinned points alone (the camera arguments and rand_f unused).
 __global__ void __launch_bounds__(1024)
 lbs_project_bwd_kernel(const float4 *__restrict__ grad_vertices, int NB, int NV, const int *__restrict__ vstart,
-                       const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, float cx, float cy,
-                       float fx, float fy, const float *__restrict__ rand_f, float *__restrict__ grad_T) {
+                       const int *__restrict__ sbone, const float4 *__restrict__ swv, int right_hand, int project, float cx,
+                       float cy, float fx, float fy, const float *__restrict__ rand_f, float *__restrict__ grad_T) {
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
   const float4 *gv = grad_vertices + (size_t)b * NV;
-  const double sgn = right_hand ? -1.0 : 1.0;
-  const bool has_rand = rand_f != nullptr;
-  const double rf = has_rand ? (double)rand_f[b] : 1.0;
+  const bool has_rand = project && rand_f != nullptr;
+  const LbsCamera cam = {right_hand, project, cx, cy, fx, fy, has_rand, has_rand ? rand_f[b] : 1.0f};
   for (int k = wave; k < NB; k += waves) {
     double a[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) a[j] = 0.0;
-    for (int v = lane; v < NV; v += 64) {
-      const int e0 = vstart[v], e1 = vstart[v + 1];
-      int e = e0;
-      while (e < e1 && sbone[e] != k) e++;
-      if (e == e1) continue;
-      const float4 g = gv[v];
-      // d out / d acc (common.h lbs_finish)
-      double d[4];
-      if (!has_rand) {
-        d[0] = sgn * (double)fx * g.x; d[1] = (double)fy * g.y; d[2] = g.z;
-        d[3] = (double)cx * g.x + (double)cy * g.y + (double)g.w;
-      } else {
-        d[0] = sgn * rf * (double)fx * g.x; d[1] = rf * (double)fy * g.y; d[2] = g.z; d[3] = 0.0;
-      }
-      for (; e < e1; e++) {
-        if (sbone[e] != k) continue;
-        const float4 q = swv[e];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          a[4 * r] += d[r] * q.x; a[4 * r + 1] += d[r] * q.y; a[4 * r + 2] += d[r] * q.z; a[4 * r + 3] += d[r] * q.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      double t = a[j];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
-      a[j] = t;
-    }
-    if (lane < 16) {
-      double t = 0.0;
-#pragma unroll
-      for (int j = 0; j < 16; j++) t = (lane == j) ? a[j] : t;
-      grad_T[((size_t)b * NB + k) * 16 + lane] = (float)t;
-    }
+    lbs_bone_grad_wave(a, k, lane, gv, NV, vstart, sbone, swv, cam);
+    if (lane < 16) grad_T[((size_t)b * NB + k) * 16 + lane] = lbs_bone_grad_entry(a, lane);
   }
 }
 
@@ -128,16 +92,33 @@ extern "C" int shr_lbs_project(const float *T, int B, int NB, int NV, const int3
   return (int)hipGetLastError();
 }
 
+static int lbs_bwd_launch(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
+                          const int32_t *skin_bone, const float *skin_wv, int right_hand, int project, float cx, float cy,
+                          float fx, float fy, const float *rand_f, float *grad_T, void *stream) {
+  if ((((uintptr_t)grad_vertices | (uintptr_t)skin_wv) & 15u) != 0) return SHR_EINVAL;
+  if (B > (1 << 30)) return SHR_ETOOLARGE;
+  hipLaunchKernelGGL(lbs_project_bwd_kernel, dim3((unsigned)B), dim3(NB >= 16 ? 1024 : 64 * NB), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4 *>(grad_vertices), NB, NV, skin_vertex_start, skin_bone,
+                     reinterpret_cast<const float4 *>(skin_wv), right_hand, project, cx, cy, fx, fy, rand_f, grad_T);
+  return (int)hipGetLastError();
+}
+
 extern "C" int shr_lbs_project_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
                                    const int32_t *skin_bone, const float *skin_wv, int right_hand, float cx, float cy,
                                    float fx, float fy, const float *rand_f, float *grad_T, void *stream) {
   if (B == 0) return SHR_OK;
   if (!grad_vertices || !skin_vertex_start || !skin_bone || !skin_wv || !grad_T || B < 0 || NB <= 0 || NV <= 0)
     return SHR_EINVAL;
-  if ((((uintptr_t)grad_vertices | (uintptr_t)skin_wv) & 15u) != 0) return SHR_EINVAL;
-  if (B > (1 << 30)) return SHR_ETOOLARGE;
-  hipLaunchKernelGGL(lbs_project_bwd_kernel, dim3((unsigned)B), dim3(NB >= 16 ? 1024 : 64 * NB), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4 *>(grad_vertices), NB, NV, skin_vertex_start, skin_bone,
-                     reinterpret_cast<const float4 *>(skin_wv), right_hand, cx, cy, fx, fy, rand_f, grad_T);
-  return (int)hipGetLastError();
+  return lbs_bwd_launch(grad_vertices, B, NB, NV, skin_vertex_start, skin_bone, skin_wv, right_hand, 1, cx, cy, fx, fy,
+                        rand_f, grad_T, stream);
+}
+
+extern "C" int shr_lbs_vertices_bwd(const float *grad_vertices, int B, int NB, int NV, const int32_t *skin_vertex_start,
+                                    const int32_t *skin_bone, const float *skin_wv, int right_hand, int project, float cx,
+                                    float cy, float fx, float fy, const float *rand_f, float *grad_T, void *stream) {
+  if (B == 0 || NV == 0) return SHR_OK;
+  if (!grad_vertices || !skin_vertex_start || !skin_bone || !skin_wv || !grad_T || B < 0 || NB <= 0 || NV < 0)
+    return SHR_EINVAL;
+  return lbs_bwd_launch(grad_vertices, B, NB, NV, skin_vertex_start, skin_bone, skin_wv, right_hand, project ? 1 : 0, cx,
+                        cy, fx, fy, rand_f, grad_T, stream);
 }

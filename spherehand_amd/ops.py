@@ -868,6 +868,105 @@ def lbs_project_bwd(grad_vertices, NB, skin_vertex_start, skin_bone, skin_wv, ri
     return grad_T
 
 
+def _skin_tables(skin_vertex_start, skin_bone, skin_wv, rand_f):
+    _check_input(skin_vertex_start, "skin_vertex_start", torch.int32)
+    _check_input(skin_bone, "skin_bone", torch.int32)
+    _check_input(skin_wv, "skin_wv")
+    if rand_f is not None:
+        _check_input(rand_f, "rand_f")
+    if skin_wv.dim() != 2 or skin_wv.shape[1] != 4 or skin_bone.numel() != skin_wv.shape[0] or skin_vertex_start.numel() < 1:
+        raise RuntimeError("the skin table is skin_vertex_start [NV+1], skin_bone [NS], skin_wv [NS,4]")
+    return skin_vertex_start.numel() - 1
+
+
+def lbs_vertices_bwd(grad_vertices, NB, skin_vertex_start, skin_bone, skin_wv, right_hand, camera=None, rand_f=None):
+    """lbs_project's backward in either mode (camera=None: the skinned points): grad_vertices [B,NV,4] -> grad_T
+    [B,NB,4,4]; with a camera the bits of lbs_project_bwd.  rand_f gets none."""
+    _check_input(grad_vertices, "grad_vertices")
+    NV = _skin_tables(skin_vertex_start, skin_bone, skin_wv, rand_f)
+    if grad_vertices.dim() != 3 or tuple(grad_vertices.shape[1:]) != (NV, 4):
+        raise RuntimeError("grad_vertices must be [B,NV,4] with the skin table's NV")
+    B = grad_vertices.shape[0]
+    cx, cy, fx, fy = camera if camera is not None else (0.0, 0.0, 1.0, 1.0)
+    with _on(grad_vertices.device):
+        make = torch.zeros if B == 0 or NV == 0 else torch.empty
+        grad_T = make((B, NB, 4, 4), dtype=torch.float32, device=grad_vertices.device)
+        _lib.check(_lib.lib().shr_lbs_vertices_bwd(_ptr(grad_vertices), B, NB, NV, _ptr(skin_vertex_start), _ptr(skin_bone),
+                                                   _ptr(skin_wv), int(bool(right_hand)), int(camera is not None), cx, cy,
+                                                   fx, fy, _ptr(rand_f), _ptr(grad_T), _stream()), "shr_lbs_vertices_bwd")
+    return grad_T
+
+
+class SkinVertices(torch.autograd.Function):
+    """T [B,NB,4,4] (or [B,NB,1,4,4]) -> the mesh's vertices [B,NV,4]: lbs_project (LinearBlendSkinning.forward,
+    mesh/pointTransformation.py:39-46, and with camera=(cx,cy,fx,fy) OthographicalProjection.forward, :84-99), the same
+    bits, with the backward to T (shr_lbs_vertices_bwd).  camera=None: the skinned points in model space.  rand_f and
+    the tables get no gradient."""
+
+    @staticmethod
+    def forward(ctx, T, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, rand_f):
+        _check_input(T, "transformation matrices")
+        if T.dim() == 5 and T.shape[2] == 1:
+            T = T.squeeze(2)
+        if T.dim() != 4 or T.shape[2:] != (4, 4):
+            raise RuntimeError("transformation matrices must be [B,NB,4,4]")
+        _skin_tables(skin_vertex_start, skin_bone, skin_wv, rand_f)
+        camera = None if camera is None else tuple(float(c) for c in camera)
+        verts = lbs_project(T, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, rand_f)
+        ctx.save_for_backward(skin_vertex_start, skin_bone, skin_wv, rand_f)
+        ctx.meta = (T.shape[1], bool(right_hand), camera)
+        return verts
+
+    @staticmethod
+    def backward(ctx, grad_vertices):
+        start, bone, wv, rand_f = ctx.saved_tensors
+        NB, right_hand, camera = ctx.meta
+        g = grad_vertices.contiguous().float()
+        return (lbs_vertices_bwd(g, NB, start, bone, wv, right_hand, camera, rand_f),) + (None,) * 6
+
+
+class PoseVertices(torch.autograd.Function):
+    """params [B,26] -> the mesh's vertices [B,NV,4]: ForwardKinematics followed by SkinVertices as ONE launch per
+    direction (shr_pose_vertices_fwd / _bwd): the bone transforms stay in LDS.  Vertices and pose gradient are
+    bit-identical to the two Functions chained.  camera=None: model space.  rand_f and the tables get no gradient."""
+
+    @staticmethod
+    def forward(ctx, params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, right_hand, camera, rand_f):
+        for t, name in ((params, "parameters"), (offset, "offset"), (offset_inv, "offset_inv")):
+            _check_input(t, name)
+        if params.dim() != 2 or params.shape[1] != 26:
+            raise RuntimeError("parameters must be [B,26]")
+        if tuple(offset.shape) != (17, 4, 4) or tuple(offset_inv.shape) != (17, 4, 4):
+            raise RuntimeError("offset and offset_inv must be [17,4,4]")
+        NV = _skin_tables(skin_vertex_start, skin_bone, skin_wv, rand_f)
+        B = params.shape[0]
+        camera = None if camera is None else tuple(float(c) for c in camera)
+        cx, cy, fx, fy = camera if camera is not None else (0.0, 0.0, 1.0, 1.0)
+        right, project = int(bool(right_hand)), int(camera is not None)
+        with _on(params.device):
+            verts = torch.empty((B, NV, 4), dtype=torch.float32, device=params.device)
+            _lib.check(_lib.lib().shr_pose_vertices_fwd(_ptr(params), B, _ptr(offset), _ptr(offset_inv), NV,
+                                                        _ptr(skin_vertex_start), _ptr(skin_bone), _ptr(skin_wv), right,
+                                                        project, cx, cy, fx, fy, _ptr(rand_f), _ptr(verts), None, _stream()),
+                       "shr_pose_vertices_fwd")
+        ctx.save_for_backward(params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, rand_f)
+        ctx.meta = (B, NV, right, project, cx, cy, fx, fy)
+        return verts
+
+    @staticmethod
+    def backward(ctx, grad_vertices):
+        params, offset, offset_inv, start, bone, wv, rand_f = ctx.saved_tensors
+        B, NV, right, project, cx, cy, fx, fy = ctx.meta
+        g = grad_vertices.contiguous().float()
+        with _on(g.device):
+            make = torch.zeros if B == 0 or NV == 0 else torch.empty
+            out = make((B, 26), dtype=torch.float32, device=g.device)
+            _lib.check(_lib.lib().shr_pose_vertices_bwd(_ptr(params), B, _ptr(offset), _ptr(offset_inv), NV, _ptr(start),
+                                                        _ptr(bone), _ptr(wv), right, project, cx, cy, fx, fy, _ptr(rand_f),
+                                                        _ptr(g), _ptr(out), _stream()), "shr_pose_vertices_bwd")
+        return (out,) + (None,) * 8
+
+
 class MeshDepthRaster(torch.autograd.Function):
     """vertices [B,NV,4] (pixel space) -> depth [B,S,S] of the fused raster + clamp + resize, differentiable w.r.t.
     (u, v, z) of the vertices.  Same contract as SphereDepthRaster: the gradient routes to each tap's owner face and

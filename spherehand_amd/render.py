@@ -15,6 +15,7 @@ signatures and return values), running on the hand-written HIP kernels.
     SilhouetteCoverage       its complement: the distance of observed pixels to the rendered silhouette, a pull on the mesh
     DepthNormalMap           a unit normal map from a depth image, differentiable in the depth: observed or rendered
     NormalConsistencyLoss    1 - m . o between two normal maps: the orientation term
+    MeshVertices             bone transforms or pose -> the mesh's vertices, differentiable: the mesh terms' way to the pose
 """
 import numpy as np
 import torch
@@ -570,7 +571,9 @@ class SparseSkinning(nn.Module):
     """LinearBlendSkinning (+ optional orthographic camera) of the full mesh on the
     HIP kernel: forward(T[B,17,4,4], camera=None, rand_f=None) -> [B,NV,4].
     distinct=True: only the mesh's DISTINCT vertices (hand_model.unique_skin: 1 721 of 10 144 -- the reference stores
-    each face's corners separately) -> [B,NU,4]; `vertex_index` [NV] maps a mesh vertex to its row."""
+    each face's corners separately) -> [B,NU,4]; `vertex_index` [NV] maps a mesh vertex to its row.
+    Where grad is enabled and T requires grad the result is differentiable w.r.t. T (ops.SkinVertices: the same bits;
+    rand_f gets no gradient); MeshVertices is the module that fixes the camera and goes on to the pose."""
 
     def __init__(self, mesh, right_hand=True, distinct=False):
         super().__init__()
@@ -587,9 +590,62 @@ class SparseSkinning(nn.Module):
         self.num_vertices = len(start) - 1
 
     def forward(self, transformation_mats, camera=None, rand_f=None):
-        return ops.lbs_project(transformation_mats.contiguous().float(), self.skin_vertex_start, self.skin_bone,
-                               self.skin_wv, self.right_hand, camera,
-                               None if rand_f is None else rand_f.contiguous().float())
+        T = transformation_mats
+        rand_f = None if rand_f is None else rand_f.detach().contiguous().float()
+        if T.requires_grad and torch.is_grad_enabled():            # differentiable w.r.t. T: the same vertices, bit for bit
+            return ops.SkinVertices.apply(T.contiguous().float(), self.skin_vertex_start, self.skin_bone, self.skin_wv,
+                                          self.right_hand, camera, rand_f)
+        return ops.lbs_project(T.contiguous().float(), self.skin_vertex_start, self.skin_bone,
+                               self.skin_wv, self.right_hand, camera, rand_f)
+
+
+class MeshVertices(nn.Module):
+    """The triangle mesh's vertices from bone transforms or from the pose, differentiable: what carries the gradient of
+    the mesh terms (TriangleDepthRaster, AntialiasedDepthRaster, MeshAttributeRaster, MeshNormalRaster,
+    SilhouetteDistance, SilhouetteCoverage, MeshDataToModelLoss) from the vertices on to the hand.
+    forward(T[B,17,4,4], rand_f=None) -> [B,NV,4] (ops.SkinVertices); pose_vertices(fk, params[B,26], rand_f=None) -> the
+    same vertices and the pose gradient of fk followed by forward, bit for bit, in one launch per direction
+    (ops.PoseVertices), `fk` being the kinematicsTransformation.HandTransformationMat whose offset matrices the bones carry.
+    camera = (cx, cy, fx, fy): pixel-space vertices as the rasters take them, pixel_camera(W, H) for a W x H image;
+    camera=None: model-space vertices (millimetres), which pair with MeshDataToModelLoss.reference_grid.
+    distinct=True skins the mesh's 1 721 distinct vertices (hand_model.unique_skin), otherwise all 10 144 records.
+    `faces`: np.int64 [F,3] indexing this module's rows, winding as the mesh stores it (the term modules swap it for the
+    right hand themselves); `rest_vertices`: np.float32 [NV,3], the module's rows at the rest pose in model space, the
+    np_vertices= welding argument of the antialias and normal modules.  rand_f (a random draw) gets no gradient."""
+
+    def __init__(self, mesh, camera=(320.0, 320.0, 640 / 300, 640 / 300), right_hand=True, distinct=True):
+        super().__init__()
+        self.lbs = SparseSkinning(mesh, right_hand=right_hand, distinct=distinct)
+        self.camera = None if camera is None else tuple(float(c) for c in camera)
+        self.num_vertices = self.lbs.num_vertices
+        faces = np.asarray(mesh['faces'], np.int64)
+        self.faces = self.lbs.vertex_index[faces] if distinct else faces.copy()
+        rest = np.asarray(mesh['vertices'], np.float32)[:, :3]
+        if distinct:
+            first = np.full(self.num_vertices, -1, np.int64)
+            index = self.lbs.vertex_index
+            first[index[::-1]] = np.arange(len(index))[::-1]          # the first mesh vertex of each row
+            rest = rest[first]
+        if right_hand:
+            rest = rest * np.array([-1.0, 1.0, 1.0], np.float32)     # (mesh/pointTransformation.py:44-45)
+        self.rest_vertices = np.ascontiguousarray(rest, np.float32)
+
+    @staticmethod
+    def pixel_camera(width, height):
+        """(cx, cy, fx, fy) of the orthographic camera that maps the reference's 300 mm window onto width x height pixels
+        (mesh/render.py:325 at 640 x 640, DepthRender's camera)."""
+        return (width / 2, height / 2, width / 300, height / 300)
+
+    def forward(self, transformation_mats, rand_f=None):
+        return self.lbs(transformation_mats, self.camera, rand_f)
+
+    def pose_vertices(self, hand_transformation_mat, parameters, rand_f=None):
+        fk, lbs = hand_transformation_mat, self.lbs
+        if not (parameters.is_cuda and parameters.dtype == torch.float32 and fk.offset.shape[0] == 17):
+            return self.forward(fk(parameters), rand_f)
+        return ops.PoseVertices.apply(parameters.contiguous(), fk.offset, fk.offset_inv, lbs.skin_vertex_start, lbs.skin_bone,
+                                      lbs.skin_wv, lbs.right_hand, self.camera,
+                                      None if rand_f is None else rand_f.detach().contiguous().float())
 
 
 class DepthRender(nn.Module):
