@@ -936,6 +936,44 @@ int shr_pose_vertices_bwd(const float *params, int B, const float *offset, const
                           int right_hand, int project, float cx, float cy, float fx, float fy, const float *rand_f,
                           const float *grad_vertices, float *grad_params, void *stream);
 
+/* Pose from keypoints: the inverse of shr_pose_spheres_fwd, as a refinement from a start pose ---------
+ * Inverts HandTransformationMat.forward (mesh/kinematicsTransformation.py:157-177) followed by the key-point skinning of
+ * HandBallPrimitiveRender (mesh/render.py:65-88); the reference has no counterpart.  offset, offset_inv [17,4,4], bone[J],
+ * wv[J,4] and right_hand are shr_pose_spheres_fwd's (a bone number outside [0, 17) is clamped into it, as there);
+ * 1 <= J <= 64.  Keypoints, targets and the Jacobian are in the frame shr_pose_spheres_fwd outputs: model millimetres, x
+ * negated for the right hand.  One wave per crop, no workspace, no host synchronisation: capturable in a hipGraph.
+ *   shr_pose_keypoints_jacobian  params[B,26] -> keypoints[B,J,4] = (shr_pose_spheres_fwd's xyz bit for bit, 1) and
+ *                          jac[B,3J,26], row 3 j + c = d keypoint j component c / d params, fp32.
+ *   shr_pose_ik_fwd        Levenberg-Marquardt on cost(p) = sum_j w_j |k_j(p) - target_j|^2 + sum_i mu_i (p_i - params0_i)^2
+ *                          from p = params0.  target[B,J,3]; weights: NULL (all 1), [J] (weight_stride 0) or [B,J]
+ *                          (weight_stride J), each >= 0; stiffness: NULL (all 0) or mu[26], each >= 0; iters >= 0,
+ *                          lambda0 > 0.  Each iteration forms A = J^T W J + diag(mu) and g = J^T W r + mu (p - params0),
+ *                          solves (A + lambda diag(A)) delta = -g by Cholesky, evaluates the cost at p + delta and accepts
+ *                          iff it is lower; lambda <- 0.3 lambda on accept, 10 lambda on reject, clamped to [1e-9, 1e6].  A
+ *                          pivot that is not positive, or a trial cost that is not finite, is a rejected step.  Always
+ *                          `iters` iterations.  Outputs params[B,26], cost0[B] (at params0) and cost[B] (at params);
+ *                          iters = 0: params = params0 and cost = cost0.  Arithmetic: keypoints, residuals and the
+ *                          Jacobian fp32; A, g, the factor, the solves, lambda and the costs fp64 (the costs leave rounded to
+ *                          fp32).  Every sum runs in a fixed order: bitwise reproducible, and a crop's result does not
+ *                          depend on the batch it is in.
+ *   shr_pose_ik_bwd        the implicit-function gradient at the returned pose in Gauss-Newton form:
+ *                          grad_target[B,J,3] = w_j J_j(params) (J^T W J + diag(mu))^-1 grad_params (exact where the residual
+ *                          is 0).  A crop whose matrix is not positive definite gets zeros.  params0, the weights and the
+ *                          stiffness get no gradient.
+ * wv and keypoints 16-byte aligned, every other array 4-byte aligned, NULL pointers (other than weights, stiffness), J < 1,
+ * iters < 0, lambda0 <= 0, a weight_stride other than 0 or J: SHR_EINVAL.  J above 64, B above 2^24: SHR_ETOOLARGE.  B == 0:
+ * SHR_OK, nothing is launched and nothing written. */
+int shr_pose_keypoints_jacobian(const float *params, int B, const float *offset, const float *offset_inv, int J,
+                                const int32_t *bone, const float *wv, int right_hand, float *keypoints, float *jac,
+                                void *stream);
+int shr_pose_ik_fwd(const float *target, const float *params0, int B, const float *offset, const float *offset_inv, int J,
+                    const int32_t *bone, const float *wv, int right_hand, const float *weights /* may be NULL */,
+                    int weight_stride, const float *stiffness /* may be NULL */, int iters, float lambda0, float *params,
+                    float *cost0, float *cost, void *stream);
+int shr_pose_ik_bwd(const float *params, const float *grad_params, int B, const float *offset, const float *offset_inv,
+                    int J, const int32_t *bone, const float *wv, int right_hand, const float *weights /* may be NULL */,
+                    int weight_stride, const float *stiffness /* may be NULL */, float *grad_target, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,9 @@ SIGNATURES = {
     "shr_lbs_vertices_bwd": ([_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp], _i),
     "shr_pose_vertices_fwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp], _i),
     "shr_pose_vertices_bwd": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp], _i),
+    "shr_pose_keypoints_jacobian": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "shr_pose_ik_fwd": ([_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "shr_pose_ik_bwd": ([_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp], _i),
     "shr_selftest_sqrt":([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_division": ([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_launch_floor": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),

@@ -1,6 +1,7 @@
 // fk_rows.h -- the row-chain arithmetic of the hand's forward kinematics (fk.hip documents the scheme), shared by the
 // pose kernels (fk.hip), the one-launch synthesizer (mesh_depth.hip: the rasterizer's workgroup runs its crop's FK) and
-// the pose -> vertices pair (pose_vertices.hip: forward and reverse chains around the mesh skinning).
+// the pose -> vertices pair (pose_vertices.hip: forward and reverse chains around the mesh skinning) and the keypoint
+// pose solver (pose_ik.hip: the forward chain and its forward-mode tangents).
 #pragma once
 #include "common.h"
 
@@ -257,9 +258,47 @@ __device__ __forceinline__ void pose_reverse_rows(int lane, const BoneConst &k1,
   }
 }
 
+// The forward-mode companion of the finger chains for ONE sample by ONE wave (pose_ik.hip): lane 4 g + i leaves row i of
+// d T[bone] / d angle for finger g's four angles in dT[(9 g + n) * 3 + i], n = tangent_slot(angle, level): abduct and
+// flex1 move the finger's three bones, flex2 two, flex3 one.  A rotation's derivative is the rotated pair exchanged
+// (rot_*_dangle's pair); behind it a tangent row runs the chain's own linear maps (w: the translation's derivative).
+// p: the sample's 26 parameters; sc [kAngles]: its sincos table, complete and visible to the wave.
+constexpr int kFingerTangents = 9;
+__device__ __forceinline__ int tangent_slot(int angle, int level) { return angle < 2 ? 3 * angle + level : angle == 2 ? 5 + level : 8; }
+__device__ __forceinline__ void pose_finger_tangents_wave(const float *p, const float *__restrict__ offset,
+                                                          const float *__restrict__ offset_inv, int lane, const Rot *sc,
+                                                          float4 *dT) {
+  const int g = lane >> 2, i = lane & 3;
+  if (!(lane < 20 && i < 3)) return;
+  const int b0 = 2 + 3 * g, a0 = 3 + 4 * g;
+  const BoneConst k1 = load_bone(offset, offset_inv, b0), k2 = load_bone(offset, offset_inv, b0 + 1),
+                  k3 = load_bone(offset, offset_inv, b0 + 2);
+  const bool yaxis = g == 2 || g == 3;
+  const Rot ra = sc[a0], rb = sc[a0 + 1], r2 = sc[a0 + 2], r3 = sc[a0 + 3];
+  const PalmRow P = palm_row(i, sc[0], sc[1], sc[2], p[3 + i]);
+  // forward, as pose_transforms_wave runs it
+  const float4 w1s = rot_z(swap_yz(row_times(P.r, k1.i0, k1.i1, k1.i2), yaxis), ra);   // (in the swapped frame)
+  const float4 v1 = rot_x(swap_yz(w1s, yaxis), rb);
+  const float4 G1 = row_times(v1, k1.o0, k1.o1, k1.o2);
+  const float4 v2 = rot_x(row_times(G1, k2.i0, k2.i1, k2.i2), r2);
+  const float4 G2 = row_times(v2, k2.o0, k2.o1, k2.o2);
+  const float4 v3 = rot_x(row_times(G2, k3.i0, k3.i1, k3.i2), r3);
+  auto next = [](const float4 dG, const BoneConst &k, const Rot r) {
+    return row_times(rot_x(row_times(dG, k.i0, k.i1, k.i2), r), k.o0, k.o1, k.o2);
+  };
+  float4 *o = dT + (kFingerTangents * g) * 3 + i;
+  float4 d = row_times(rot_x(swap_yz(make_float4(w1s.y, -w1s.x, 0.f, 0.f), yaxis), rb), k1.o0, k1.o1, k1.o2);   // abduct
+  o[0] = d; d = next(d, k2, r2); o[3] = d; o[6] = next(d, k3, r3);
+  d = row_times(make_float4(0.f, v1.z, -v1.y, 0.f), k1.o0, k1.o1, k1.o2);                                        // flex1
+  o[9] = d; d = next(d, k2, r2); o[12] = d; o[15] = next(d, k3, r3);
+  d = row_times(make_float4(0.f, v2.z, -v2.y, 0.f), k2.o0, k2.o1, k2.o2);                                        // flex2
+  o[18] = d; o[21] = next(d, k3, r3);
+  o[24] = row_times(make_float4(0.f, v3.z, -v3.y, 0.f), k3.o0, k3.o1, k3.o2);                                    // flex3
+}
+
 }  // namespace shr
 
-// the pose entries' common argument rules (fk.hip, pose_vertices.hip)
+// the pose entries' common argument rules (fk.hip, pose_vertices.hip, pose_ik.hip)
 static inline int fk_check(const void *params, int B, const void *offset, const void *offset_inv) {
   if (!params || !offset || !offset_inv || B < 0) return SHR_EINVAL;
   if ((((uintptr_t)offset | (uintptr_t)offset_inv) & 15u) != 0) return SHR_EINVAL;

@@ -967,6 +967,107 @@ class PoseVertices(torch.autograd.Function):
         return (out,) + (None,) * 8
 
 
+def _ik_tables(params, offset, offset_inv, bone, wv, name="parameters"):
+    for t, what in ((params, name), (offset, "offset"), (offset_inv, "offset_inv"), (wv, "key-points")):
+        _check_input(t, what)
+    _check_input(bone, "key-point bones", torch.int32)
+    if params.dim() != 2 or params.shape[1] != 26:
+        raise RuntimeError("%s must be [B,26]" % name)
+    if tuple(offset.shape) != (17, 4, 4) or tuple(offset_inv.shape) != (17, 4, 4):
+        raise RuntimeError("offset and offset_inv must be [17,4,4]")
+    J = bone.shape[0]
+    if bone.dim() != 1 or tuple(wv.shape) != (J, 4) or not 1 <= J <= 64:
+        raise RuntimeError("key-point tables must be bone [J] and wv [J,4] with 1 <= J <= 64")
+    return params.shape[0], J
+
+
+def _ik_weights(weights, stiffness, B, J):
+    """(weights or None, weight_stride, stiffness or None) as the entries take them."""
+    stride = 0
+    if weights is not None:
+        _check_input(weights, "weights")
+        if tuple(weights.shape) == (B, J):
+            stride = J
+        elif tuple(weights.shape) != (J,):
+            raise RuntimeError("weights must be [J] or [B,J]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    return weights, stride, stiffness
+
+
+def pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand=True):
+    """params [B,26] -> (keypoints [B,J,4], jac [B,3J,26]): ops.PoseSpheres' xyz bit for bit (w = 1) and their derivative,
+    row 3 j + c = d keypoint j component c / d params, in the frame PoseSpheres outputs (shr_pose_keypoints_jacobian)."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv)
+    with _on(params.device):
+        kp = torch.empty((B, J, 4), dtype=torch.float32, device=params.device)
+        jac = torch.empty((B, 3 * J, 26), dtype=torch.float32, device=params.device)
+        _lib.check(_lib.lib().shr_pose_keypoints_jacobian(_ptr(params), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone),
+                                                          _ptr(wv), int(bool(right_hand)), _ptr(kp), _ptr(jac), _stream()),
+                   "shr_pose_keypoints_jacobian")
+    return kp, jac
+
+
+def pose_ik(target, params0, offset, offset_inv, bone, wv, right_hand=True, weights=None, stiffness=None, iters=12,
+            lambda0=1e-3):
+    """Levenberg-Marquardt refinement of params0 [B,26] towards the keypoints target [B,J,3] (shr_pose_ik_fwd has the
+    iteration): -> (params [B,26], cost0 [B], cost [B]).  weights [J] or [B,J], stiffness [26]: optional, each >= 0."""
+    B, J = _ik_tables(params0, offset, offset_inv, bone, wv, "start parameters")
+    _check_input(target, "target keypoints")
+    if tuple(target.shape) != (B, J, 3):
+        raise RuntimeError("target keypoints must be [B,J,3]")
+    if int(iters) < 0 or not float(lambda0) > 0:
+        raise RuntimeError("iters must be >= 0 and lambda0 > 0")
+    weights, stride, stiffness = _ik_weights(weights, stiffness, B, J)
+    with _on(params0.device):
+        params = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
+        cost0 = torch.empty((B,), dtype=torch.float32, device=params0.device)
+        cost = torch.empty((B,), dtype=torch.float32, device=params0.device)
+        _lib.check(_lib.lib().shr_pose_ik_fwd(_ptr(target), _ptr(params0), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone),
+                                              _ptr(wv), int(bool(right_hand)), _ptr(weights), stride, _ptr(stiffness),
+                                              int(iters), float(lambda0), _ptr(params), _ptr(cost0), _ptr(cost), _stream()),
+                   "shr_pose_ik_fwd")
+    return params, cost0, cost
+
+
+def pose_ik_bwd(params, grad_params, offset, offset_inv, bone, wv, right_hand=True, weights=None, stiffness=None):
+    """grad_target [B,J,3] = w_j J_j (J^T W J + diag(mu))^-1 grad_params at `params` (shr_pose_ik_bwd); zeros for a crop
+    whose matrix is not positive definite."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv)
+    _check_input(grad_params, "parameter gradient")
+    if tuple(grad_params.shape) != (B, 26):
+        raise RuntimeError("parameter gradient must be [B,26]")
+    weights, stride, stiffness = _ik_weights(weights, stiffness, B, J)
+    with _on(params.device):
+        out = torch.empty((B, J, 3), dtype=torch.float32, device=params.device)
+        _lib.check(_lib.lib().shr_pose_ik_bwd(_ptr(params), _ptr(grad_params), B, _ptr(offset), _ptr(offset_inv), J,
+                                              _ptr(bone), _ptr(wv), int(bool(right_hand)), _ptr(weights), stride,
+                                              _ptr(stiffness), _ptr(out), _stream()), "shr_pose_ik_bwd")
+    return out
+
+
+class PoseFromKeypoints(torch.autograd.Function):
+    """target keypoints [B,J,3], start pose [B,26] -> pose [B,26]: the solver pose_ik as a differentiable node.  Backward
+    is the implicit-function gradient in Gauss-Newton form (pose_ik_bwd), to `target` only: the start pose, the weights
+    and the stiffness get none."""
+
+    @staticmethod
+    def forward(ctx, target, params0, offset, offset_inv, bone, wv, right_hand, weights, stiffness, iters, lambda0):
+        params, _, _ = pose_ik(target, params0, offset, offset_inv, bone, wv, right_hand, weights, stiffness, iters, lambda0)
+        ctx.save_for_backward(params, offset, offset_inv, bone, wv, weights, stiffness)
+        ctx.right_hand = bool(right_hand)
+        return params
+
+    @staticmethod
+    def backward(ctx, grad_params):
+        params, offset, offset_inv, bone, wv, weights, stiffness = ctx.saved_tensors
+        g = pose_ik_bwd(params, grad_params.contiguous().float(), offset, offset_inv, bone, wv, ctx.right_hand, weights,
+                        stiffness)
+        return (g,) + (None,) * 10
+
+
 class MeshDepthRaster(torch.autograd.Function):
     """vertices [B,NV,4] (pixel space) -> depth [B,S,S] of the fused raster + clamp + resize, differentiable w.r.t.
     (u, v, z) of the vertices.  Same contract as SphereDepthRaster: the gradient routes to each tap's owner face and
