@@ -974,6 +974,75 @@ int shr_pose_ik_bwd(const float *params, const float *grad_params, int B, const 
                     int J, const int32_t *bone, const float *wv, int right_hand, const float *weights /* may be NULL */,
                     int weight_stride, const float *stiffness /* may be NULL */, float *grad_target, void *stream);
 
+/* Pose from observed depth points: Gauss-Newton / Levenberg-Marquardt ICP on the mesh ---------------
+ * Inverts HandTransformationMat.forward (mesh/kinematicsTransformation.py:157-177) followed by LinearBlendSkinning.forward
+ * (mesh/pointTransformation.py:39-46), against the observation of DataToModelLoss (mesh/render.py:93-142) taken to the
+ * triangles by shr_mesh_d2m_fwd; the reference has no counterpart.  One evaluation of a fit is
+ *   shr_pose_vertices_fwd(trial, project = 0) -> shr_mesh_d2m_fwd -> shr_pose_icp_normal -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_pose_icp_normal    the normal equations of 1/2 sum dist^2 over the contributing data points with respect to the
+ *       26 pose parameters.  observed, vertices, faces, dist, face, ax .. max_dist: shr_mesh_d2m_bwd's, with its meaning and
+ *       checks (dist and face the forward's maps, or any maps: every index is checked); params[B,26], offset, offset_inv
+ *       [17,4,4]: shr_fk_fwd's; skin_vertex_start[NV+1], skin_bone, skin_wv, right_hand: shr_pose_vertices_fwd's table (a
+ *       bone number outside [0, 17) is clamped into it).  vertices MUST be those shr_pose_vertices_fwd(params, project = 0)
+ *       writes for this table: this is NOT checked, and other vertices give the equations of no function.
+ *       A pixel contributes a row under shr_mesh_d2m_bwd's rule without its grad_dist test: a data point, its face in
+ *       [0, F) with ids in [0, NV), 0 < dist < max_dist, and the recomputed distance d finite and not zero.  On the saved
+ *       face, as there (the same device code): the fp64 regions without a clamp give the corner weights w_k, e = p - c,
+ *       d = |e|, u = e / d.  With the weights held (the envelope theorem), row J = d d / d params =
+ *       -u^T sum_k w_k d v_k / d params, where a vertex is the sum over its table entries of T_bone wv: the palm angles
+ *       by omega x (T_bone wv - wv.w t) about the palm translation t, omega = P e_x, Rz e_y, e_z, the translation by wv.w,
+ *       a finger angle by the forward-mode tangent of T_bone (shr_pose_keypoints_jacobian's columns); component x of the
+ *       right hand negated.  No assumption about which fingers a point touches: every entry of every corner adds to the
+ *       columns of its own bone.  Transforms, tangents and the entries of J are fp32; w_k, u, d and every sum are fp64.
+ *       -> A[B,26,26] fp64 = sum J^T J, both triangles written from one sum (bit-symmetric); g[B,26] fp64 = sum d J, the
+ *       gradient of 1/2 sum dist^2; cost[B] fp64 = sum dist^2 over ALL pixels of the fp32 map `dist`, each promoted to
+ *       fp64 before it is squared (a saturated point counts max_dist^2: a truncated quadratic); count[B] int32, the rows.
+ *       A crop without a row gets A = 0, g = 0, count = 0.
+ *       Summation order (the contract): the pixels of a crop in row-major order form tiles of 1024; within a tile every
+ *       entry is one fp64 chain from 0 over the tile's pixels in ascending order (fma(J_a, J_c, .) for A, fma(d, J_a, .)
+ *       for g, a sum for cost); the tiles' values are then added from 0 in ascending tile order.  Bitwise reproducible;
+ *       a crop's result does not depend on the batch it is in or on the launch shape.
+ *       workspace: 16-byte aligned, shr_pose_icp_normal_workspace_bytes(B, W, H) bytes (-1 on a negative size): 3072
+ *       bytes per (crop, tile), written by the call before it is read.
+ *       Argument rules: shr_mesh_d2m_bwd's and shr_pose_vertices_fwd's -- 1 <= H, W <= 2048, B <= 65535, 3 NV and 3 F <
+ *       2^31, B NV <= 2^30 (SHR_ETOOLARGE beyond); NV >= 1, F >= 0; B == 0 is a no-op; NULLs (faces may be NULL when
+ *       F == 0) and misaligned pointers (4 bytes; A, g, cost 8; vertices, offset, offset_inv, skin_wv, workspace 16):
+ *       SHR_EINVAL.
+ *   shr_pose_lm_begin, shr_pose_lm_step   the Levenberg-Marquardt bookkeeping of shr_pose_ik_fwd's iteration, kept on the
+ *       device; `state`: shr_pose_lm_state_bytes(B) bytes (-1 for B < 0), 8-byte aligned, per crop the accepted pose, its
+ *       total cost, its A and g, params0, lambda, and counters of accepted and rejected steps: 760 doubles per crop --
+ *       A [0, 676), g [676, 702), the pose [702, 728), params0 [728, 754), cost 754, lambda 755, 756: no step since
+ *       begin, 757: a step has been accepted since begin, 758 and 759: the accepted and the rejected steps.
+ *       begin(params0[B,26], lambda0 > 0): pose <- params0, cost <- +inf, lambda <- lambda0, A and g <- 0, the counters
+ *       <- 0, and trial[B,26] <- params0: the pose to evaluate first.
+ *       step(A, g, cost_data of the pose `trial`; prior[B,26] or NULL = params0; stiffness mu[26] >= 0 or NULL = 0):
+ *         total = cost_data + mu_0 (trial_0 - prior_0)^2 + ... + mu_25 (trial_25 - prior_25)^2, added in this order;
+ *         the trial is ACCEPTED iff total is finite and below the state's cost; the state then takes trial, A, g, total;
+ *         lambda <- 0.3 lambda on an accepted step -- except the first accepted one after begin, which leaves it as it
+ *         is -- and 10 lambda on a rejected one; then lambda is clamped to [1e-9, 1e6];
+ *         params[B,26] <- the accepted pose, cost[B] <- its total (fp32; +inf while nothing has been accepted), and on
+ *         the first step after begin cost0[B] <- total (fp32), accepted or not;
+ *         solve != 0: with p, A, g the accepted pose's and M = A + diag(mu), the step solves
+ *         (M + lambda diag M) delta = -(g + mu (p - prior)) by Cholesky and writes trial_out[B,26] = fp32(p + delta); a
+ *         pivot that is not positive and finite writes trial_out = p (evaluated next, it costs the same, is rejected, and
+ *         lambda rises: no special case).  solve == 0 writes no trial_out (it may be NULL).  trial_out may be trial.
+ *       All arithmetic fp64, every sum in index order, one wave per crop, the factor and the substitutions those of
+ *       shr_pose_ik_fwd: bitwise reproducible, a crop does not depend on its batch.
+ *       NULLs (other than prior, stiffness), lambda0 <= 0, misaligned pointers (state, A, g, cost_data 8; others 4):
+ *       SHR_EINVAL.  B above 2^24: SHR_ETOOLARGE.  B == 0: SHR_OK, nothing is launched and nothing written. */
+long long shr_pose_icp_normal_workspace_bytes(int B, int W, int H);
+int shr_pose_icp_normal(const float *observed, const float *vertices, const int32_t *faces, const float *dist,
+                        const int32_t *face, const float *params, const float *offset, const float *offset_inv,
+                        const int32_t *skin_vertex_start, const int32_t *skin_bone, const float *skin_wv, int right_hand,
+                        int B, int NV, int F, int W, int H, float ax, float bx, float ay, float by, float fg_max,
+                        float max_dist, double *A, double *g, double *cost, int32_t *count, void *workspace, void *stream);
+long long shr_pose_lm_state_bytes(int B);
+int shr_pose_lm_begin(const float *params0, int B, float lambda0, void *state, float *trial, void *stream);
+int shr_pose_lm_step(void *state, const double *A, const double *g, const double *cost_data, const float *trial,
+                     const float *prior /* may be NULL */, const float *stiffness /* may be NULL */, int solve, int B,
+                     float *trial_out, float *params, float *cost, float *cost0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

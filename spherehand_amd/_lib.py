@@ -128,6 +128,11 @@ SIGNATURES = {
     "shr_pose_keypoints_jacobian": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "shr_pose_ik_fwd": ([_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp], _i),
     "shr_pose_ik_bwd": ([_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp], _i),
+    "shr_pose_icp_normal_workspace_bytes": ([_i, _i, _i], ctypes.c_longlong),
+    "shr_pose_icp_normal": ([_vp] * 11 + [_i] * 6 + [_f] * 6 + [_vp] * 6, _i),
+    "shr_pose_lm_state_bytes": ([_i], ctypes.c_longlong),
+    "shr_pose_lm_begin": ([_vp, _i, _f, _vp, _vp, _vp], _i),
+    "shr_pose_lm_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "shr_selftest_sqrt":([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_division": ([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_launch_floor": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),

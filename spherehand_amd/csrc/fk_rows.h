@@ -1,7 +1,7 @@
 // fk_rows.h -- the row-chain arithmetic of the hand's forward kinematics (fk.hip documents the scheme), shared by the
 // pose kernels (fk.hip), the one-launch synthesizer (mesh_depth.hip: the rasterizer's workgroup runs its crop's FK) and
 // the pose -> vertices pair (pose_vertices.hip: forward and reverse chains around the mesh skinning) and the keypoint
-// pose solver (pose_ik.hip: the forward chain and its forward-mode tangents).
+// pose solver (pose_ik.hip: the forward chain and its forward-mode tangents) and the mesh pose fit (pose_icp.hip: the same).
 #pragma once
 #include "common.h"
 

@@ -16,12 +16,11 @@
 //              that rule would take (cull_root below).
 //   backward   fixed_point.h's passes over D2mTaps: one tap per contributing pixel, on its saved face, the closest point
 //              again in fp64.
+#include "d2m_tap.h"
 #include "fixed_point.h"
-#include "tri_tap.h"
 
 namespace shr {
 
-constexpr int kD2mMaxSide = 2048;
 constexpr int kD2mThreads = 256;      // search: four waves
 constexpr int kD2mTilePix = 1024;     // ... pixels of a workgroup (a data point's offset fits 16 bits)
 constexpr int kD2mSubs = kD2mTilePix / kD2mThreads;
@@ -194,25 +193,8 @@ d2m_search_kernel(const float *__restrict__ observed, const float4 *__restrict__
   }
 }
 
-// The closest point of the triangle (a, a + ab, a + ac) to a + ap in fp64: the seven regions, (v, w) of a + v ab + w ac.
-__device__ __forceinline__ void closest64(const double (&ab)[3], const double (&ac)[3], const double (&ap)[3], double &v,
-                                          double &w) {
-  auto dot = [](const double (&u)[3], const double (&t)[3]) { return (u[0] * t[0] + u[1] * t[1]) + u[2] * t[2]; };
-  const double bp[3] = {ap[0] - ab[0], ap[1] - ab[1], ap[2] - ab[2]}, cp[3] = {ap[0] - ac[0], ap[1] - ac[1], ap[2] - ac[2]};
-  const double d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
-  const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-  const double e43 = d4 - d3, e56 = d5 - d6, den = (va + vb) + vc;
-  if (d1 <= 0.0 && d2 <= 0.0) { v = 0.0; w = 0.0; }
-  else if (d3 >= 0.0 && d4 <= d3) { v = 1.0; w = 0.0; }
-  else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) { v = d1 / (d1 - d3); w = 0.0; }
-  else if (d6 >= 0.0 && d5 <= d6) { v = 0.0; w = 1.0; }
-  else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) { v = 0.0; w = d2 / (d2 - d6); }
-  else if (va <= 0.0 && e43 >= 0.0 && e56 >= 0.0) { w = e43 / (e43 + e56); v = 1.0 - w; }
-  else { v = vb / den; w = vc / den; }
-}
-
 // D2mTaps: the W x H pixels, ONE tap each (CoverTaps' pattern, sil_cover.hip) -- on the pixel's saved face.  face is
-// checked here through face_points, with the face's vertex ids: every index that comes from memory is checked before it
+// checked in d2m_tap.h's d2m_closest, with the face's vertex ids: every index that comes from memory is checked before it
 // indexes anything.
 template <bool RUNS>
 struct D2mTaps {
@@ -235,43 +217,24 @@ struct D2mTaps {
       const size_t i = PixelWalk<RUNS>::pixel(k);
       if (i >= npix) break;
       const float z = observed[(size_t)b * npix + i];
-      if (!(z < fg_max)) continue;
+      if (!(z < fg_max)) continue;                          // (d2m_measured's first test, here to save the other loads)
       const float d = dist[(size_t)b * npix + i];
-      if (!(d > 0.f && d < max_dist)) continue;            // (zero or saturated: a constant)
+      if (!d2m_measured(z, d, fg_max, max_dist)) continue;  // (zero or saturated: a constant)
       const float gd = grad_dist[(size_t)b * npix + i];
       if (gd == 0.f) continue;
-      float fv[9];
-      int pid[3];
-      if (!face_points(vertices + (size_t)b * NV, faces, NV, F, face[(size_t)b * npix + i], fv, pid)) continue;
-      const int row = (int)(i / W), col = (int)(i - (size_t)row * W);
-      const float px = ax * (float)col + bx, py = ay * (float)row + by;
-      const double ab[3] = {(double)fv[3] - fv[0], (double)fv[4] - fv[1], (double)fv[5] - fv[2]};
-      const double ac[3] = {(double)fv[6] - fv[0], (double)fv[7] - fv[1], (double)fv[8] - fv[2]};
-      const double ap[3] = {(double)px - fv[0], (double)py - fv[1], (double)z - fv[2]};
-      double v, w;
-      closest64(ab, ac, ap, v, w);
-      const double e[3] = {ap[0] - (v * ab[0] + w * ac[0]), ap[1] - (v * ab[1] + w * ac[1]), ap[2] - (v * ab[2] + w * ac[2])};
-      const double n = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-      if (!(n > 0.0 && n <= 1.7976931348623157e308)) continue;            // (on the face, or not finite)
-      const double wk[3] = {(1.0 - v) - w, v, w};
+      D2mClosest t;
+      if (!d2m_closest(vertices + (size_t)b * NV, faces, NV, F, face[(size_t)b * npix + i], i, W, ax, bx, ay, by, z, t)) continue;
       double g[3][3];
 #pragma unroll
       for (int a = 0; a < 3; a++)
 #pragma unroll
-        for (int c = 0; c < 3; c++) g[a][c] = -(double)gd * wk[a] * (e[c] / n);
-      fn(g, pid);
+        for (int c = 0; c < 3; c++) g[a][c] = -(double)gd * t.wk[a] * (t.e[c] / t.n);
+      fn(g, t.pid);
     }
   }
 };
 
 }  // namespace shr
-
-static int d2m_check(int B, int NV, int F, int W, int H, float max_dist) {
-  if (!(max_dist >= 0.f) || B < 0 || NV <= 0 || F < 0 || H < 1 || W < 1) return SHR_EINVAL;
-  if (B > 65535 || H > shr::kD2mMaxSide || W > shr::kD2mMaxSide) return SHR_ETOOLARGE;
-  if ((long long)NV * 3 >= (1LL << 31) || 3LL * F >= (1LL << 31)) return SHR_ETOOLARGE;
-  return SHR_OK;
-}
 
 // rec[B][F][3] float4
 extern "C" long long shr_mesh_d2m_workspace_bytes(int B, int F) {

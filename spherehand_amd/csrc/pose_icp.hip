@@ -1,0 +1,330 @@
+// pose_icp.hip -- the pose fitted to observed depth points: the Gauss-Newton normal equations of the mesh data-to-model
+// distance with respect to the 26 pose parameters (shr_pose_icp_normal), and the Levenberg-Marquardt bookkeeping around
+// them, kept on the device (shr_pose_lm_begin / shr_pose_lm_step).
+//
+// Inverts (reference file:line): HandTransformationMat.forward (mesh/kinematicsTransformation.py:157-177) followed by
+// LinearBlendSkinning.forward (mesh/pointTransformation.py:39-46), against the observation of DataToModelLoss
+// (mesh/render.py:93-142) taken to the triangles (shr_mesh_d2m_fwd).  The reference has no counterpart.
+//
+//   tiles    a workgroup of 256 threads owns kIcpTilePix consecutive pixels of one crop.  Wave 0 forms the crop's bone
+//            transforms and the finger tangents in LDS (fk_rows.h: pose_ik.hip's machinery).  Four rounds of 256 pixels:
+//            a thread takes one pixel, recomputes the closest point on its saved face in fp64 (d2m_tap.h: what
+//            shr_mesh_d2m_bwd does) and leaves the row J = d dist / d params in LDS, fp32: with cm = -w_k u in the model
+//            frame, a skin entry (bone, wv) of corner k at pos = T_bone wv adds cm . (omega x (pos - wv.w t)) to a palm
+//            angle (as omega . ((pos - wv.w t) x cm): one cross product per entry), wv.w cm to the translation and
+//            cm . (dT wv) to the bone's finger angles.  Nothing is assumed about which fingers a row touches.  Then thread
+//            t sums entry t (and t + 256) of [A's lower triangle | g | cost | count] over the round's pixels in pixel order.
+//   reduce   one workgroup per crop adds the tiles' sums in tile order and writes A (both triangles), g, cost, count.
+//   lm       one wave per crop: the accept test, lambda, and lm_solve.h's damped solve -- pose_ik.hip's iteration, split
+//            where the cost evaluation needs other kernels.
+#include "d2m_tap.h"
+#include "fk_rows.h"
+#include "lm_solve.h"
+
+namespace shr {
+
+constexpr int kIcpThreads = 256;
+constexpr int kIcpRounds = 4;
+constexpr int kIcpTilePix = kIcpThreads * kIcpRounds;   // the unit of the summation order: part of the contract
+constexpr int kIcpTri = kLmN * (kLmN + 1) / 2;          // 351
+constexpr int kIcpSlots = 384;                          // doubles of a tile's record in the workspace: A's lower triangle, g,
+static_assert(kIcpTri + kLmN + 2 <= kIcpSlots, "");     // cost, count (379), one thread of the reduction each
+constexpr int kIcpRow = kLmN + 1;                       // a row's stride in LDS (27: the threads' rows start in different banks)
+
+struct IcpLds {
+  Rot sc[kAngles];
+  float4 T[kBones * 4];
+  float4 dT[5 * kFingerTangents * 3];
+  float jac[kIcpThreads * kIcpRow];
+  double d[kIcpThreads];                                // the row's distance, 0: the pixel has no row
+  double c2[kIcpThreads];                               // the pixel's dist^2 of the forward's map
+};
+
+enum { kIcpA = 0, kIcpG = 1, kIcpCost = 2, kIcpCount = 3, kIcpNone = 4 };
+
+// entry idx of a tile's record: (kind, a, c)
+__device__ __forceinline__ int icp_entry(int idx, int &a, int &c) {
+  a = c = 0;
+  if (idx < kIcpTri) {
+    while ((a + 1) * (a + 2) / 2 <= idx) a++;
+    c = idx - a * (a + 1) / 2;                          // a >= c
+    return kIcpA;
+  }
+  if (idx < kIcpTri + kLmN) { a = idx - kIcpTri; return kIcpG; }
+  return idx == kIcpTri + kLmN ? kIcpCost : idx == kIcpTri + kLmN + 1 ? kIcpCount : kIcpNone;
+}
+
+__global__ void __launch_bounds__(kIcpThreads)
+pose_icp_tiles_kernel(const float *__restrict__ observed, const float4 *__restrict__ vertices, const int *__restrict__ faces,
+                      const float *__restrict__ dist, const int *__restrict__ face, const float *__restrict__ params,
+                      const float *__restrict__ offset, const float *__restrict__ offset_inv, const int *__restrict__ vstart,
+                      const int *__restrict__ sbone, const float4 *__restrict__ swv, float sx, int NV, int F, int W, int H,
+                      float ax, float bx, float ay, float by, float fg_max, float max_dist, double *__restrict__ part) {
+  __shared__ IcpLds s;
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const size_t npix = (size_t)H * W, base = (size_t)blockIdx.x * kIcpTilePix;
+  if (tid < 64) pose_transforms_wave<false>(params, offset, offset_inv, b, tid, s.sc, nullptr, s.T, SynthDraws{});
+  __syncthreads();
+  if (tid < 64) pose_finger_tangents_wave(params + (size_t)b * kLmN, offset, offset_inv, tid, s.sc, s.dT);
+  int a0, c0, a1, c1;
+  icp_entry(tid, a0, c0);                               // (tid < 256 < 351: an entry of A)
+  const int kind1 = icp_entry(tid + kIcpThreads, a1, c1);
+  double acc0 = 0.0, acc1 = 0.0;
+  float *row = s.jac + tid * kIcpRow;
+#pragma unroll 1
+  for (int r = 0; r < kIcpRounds; r++) {
+    const size_t i = base + (size_t)(r * kIcpThreads + tid);
+    double dn = 0.0, c2 = 0.0;
+    bool live = false;
+    D2mClosest t;
+    if (i < npix) {
+      const float z = observed[(size_t)b * npix + i], d = dist[(size_t)b * npix + i];
+      c2 = (double)d * (double)d;
+      if (d2m_measured(z, d, fg_max, max_dist))
+        live = d2m_closest(vertices + (size_t)b * NV, faces, NV, F, face[(size_t)b * npix + i], i, W, ax, bx, ay, by, z, t);
+    }
+    // (a barrier: the last round's sums have read the rows, and the first round's tangents are in LDS)
+    if (__syncthreads_or(live || c2 != 0.0) == 0) continue;
+    for (int q = 0; q < kLmN; q++) row[q] = 0.f;
+    if (live) {
+      dn = t.n;
+      const double u[3] = {t.e[0] / t.n, t.e[1] / t.n, t.e[2] / t.n};
+      const float4 r0 = s.T[0], r1 = s.T[1], r2 = s.T[2];
+      double mx = 0.0, my = 0.0, mz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const double cx = (double)sx * -(t.wk[k] * u[0]), cy = -(t.wk[k] * u[1]), cz = -(t.wk[k] * u[2]);
+        const int v = t.pid[k];                         // in [0, NV): d2m_closest checked it
+#pragma unroll 1
+        for (int e = vstart[v]; e < vstart[v + 1]; e++) {
+          const int bone = min(max(sbone[e], 0), kBones - 1);   // (as shr_pose_vertices_fwd: a matrix of the table)
+          const float4 q = swv[e];
+          const float4 m0 = s.T[4 * bone], m1 = s.T[4 * bone + 1], m2 = s.T[4 * bone + 2];
+          const float px = ((m0.x * q.x + m0.y * q.y) + m0.z * q.z) + m0.w * q.w;
+          const float py = ((m1.x * q.x + m1.y * q.y) + m1.z * q.z) + m1.w * q.w;
+          const float pz = ((m2.x * q.x + m2.y * q.y) + m2.z * q.z) + m2.w * q.w;
+          const double rx = (double)(px - q.w * r0.w), ry = (double)(py - q.w * r1.w), rz = (double)(pz - q.w * r2.w);
+          mx += ry * cz - rz * cy; my += rz * cx - rx * cz; mz += rx * cy - ry * cx;
+          tx += (double)q.w * cx; ty += (double)q.w * cy; tz += (double)q.w * cz;
+          if (bone >= 2) {
+            const int f = (bone - 2) / 3, level = (bone - 2) - 3 * f;
+            float *fr = row + 6 + 4 * f;
+            for (int a = 0; a < 4; a++) {
+              if (a > level + 1) break;
+              const float4 *d = s.dT + (kFingerTangents * f + tangent_slot(a, level)) * 3;
+              const float dx = ((d[0].x * q.x + d[0].y * q.y) + d[0].z * q.z) + d[0].w * q.w;
+              const float dy = ((d[1].x * q.x + d[1].y * q.y) + d[1].z * q.z) + d[1].w * q.w;
+              const float dz = ((d[2].x * q.x + d[2].y * q.y) + d[2].z * q.z) + d[2].w * q.w;
+              fr[a] += (float)((cx * (double)dx + cy * (double)dy) + cz * (double)dz);
+            }
+          }
+        }
+      }
+      // omega . m for omega = P e_x, Rz e_y = (-s, c, 0), e_z (pose_ik.hip's palm columns)
+      const Rot az = s.sc[2];
+      row[0] = (float)(((double)r0.x * mx + (double)r1.x * my) + (double)r2.x * mz);
+      row[1] = (float)((double)az.c * my - (double)az.s * mx);
+      row[2] = (float)mz;
+      row[3] = (float)tx; row[4] = (float)ty; row[5] = (float)tz;
+    }
+    s.d[tid] = dn;
+    s.c2[tid] = c2;
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < kIcpThreads; j++) {
+      const double dj = s.d[j], cj = s.c2[j];
+      if (dj == 0.0 && cj == 0.0) continue;             // (uniform; a NaN c2 is carried into the cost)
+      const float *rj = s.jac + j * kIcpRow;
+      acc0 = fma((double)rj[a0], (double)rj[c0], acc0);
+      if (kind1 == kIcpA) acc1 = fma((double)rj[a1], (double)rj[c1], acc1);
+      else if (kind1 == kIcpG) acc1 = fma(dj, (double)rj[a1], acc1);
+      else if (kind1 == kIcpCost) acc1 += cj;
+      else if (kind1 == kIcpCount) acc1 += dj != 0.0 ? 1.0 : 0.0;
+    }
+  }
+  double *out = part + ((size_t)b * gridDim.x + blockIdx.x) * kIcpSlots;
+  out[tid] = acc0;
+  if (kind1 != kIcpNone) out[tid + kIcpThreads] = acc1;
+}
+
+__global__ void __launch_bounds__(kIcpSlots)
+pose_icp_reduce_kernel(const double *__restrict__ part, int tiles, double *__restrict__ A, double *__restrict__ g,
+                       double *__restrict__ cost, int *__restrict__ count) {
+  const int idx = threadIdx.x, b = blockIdx.x;
+  int a, c;
+  const int kind = icp_entry(idx, a, c);
+  if (kind == kIcpNone) return;
+  const double *in = part + (size_t)b * tiles * kIcpSlots + idx;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int t = 0; t < tiles; t++) acc += in[(size_t)t * kIcpSlots];
+  if (kind == kIcpA) {
+    A[((size_t)b * kLmN + a) * kLmN + c] = acc;
+    A[((size_t)b * kLmN + c) * kLmN + a] = acc;
+  } else if (kind == kIcpG) {
+    g[(size_t)b * kLmN + a] = acc;
+  } else if (kind == kIcpCost) {
+    cost[b] = acc;
+  } else {
+    count[b] = (int)acc;
+  }
+}
+
+// A crop's state, in doubles: the accepted pose's A [26 x 26] and g [26], the pose itself, params0, its total cost, lambda,
+// `fresh` (no step since begin), `moved` (a trial has been accepted since begin), the accept and reject counters.
+constexpr int kLmA = 0, kLmG = kLmN * kLmN, kLmP = kLmG + kLmN, kLmP0 = kLmP + kLmN, kLmCost = kLmP0 + kLmN, kLmLambda = kLmCost + 1,
+              kLmFresh = kLmCost + 2, kLmMoved = kLmCost + 3, kLmAccepts = kLmCost + 4, kLmRejects = kLmCost + 5, kLmState = 760;
+static_assert(kLmRejects < kLmState, "the state's fields");
+
+__global__ void __launch_bounds__(64)
+pose_lm_begin_kernel(const float *__restrict__ params0, float lambda0, double *__restrict__ state, float *__restrict__ trial) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double *st = state + (size_t)b * kLmState;
+  for (int e = lane; e < kLmP; e += 64) st[e] = 0.0;
+  if (lane < kLmN) {
+    const float p = params0[(size_t)b * kLmN + lane];
+    st[kLmP + lane] = st[kLmP0 + lane] = (double)p;
+    trial[(size_t)b * kLmN + lane] = p;
+  }
+  if (lane == 0) {
+    st[kLmCost] = __builtin_inf();
+    st[kLmLambda] = (double)lambda0;
+    st[kLmFresh] = 1.0;
+    st[kLmMoved] = st[kLmAccepts] = st[kLmRejects] = 0.0;
+  }
+}
+
+struct LmLds {
+  double A[kLmN * kLmN], L[kLmN * kLmN], x[kLmN], piv;
+};
+
+__global__ void __launch_bounds__(64)
+pose_lm_step_kernel(double *__restrict__ state, const double *__restrict__ A, const double *__restrict__ g,
+                    const double *__restrict__ cost_data, const float *trial, const float *__restrict__ prior,
+                    const float *__restrict__ stiffness, int solve, float *trial_out, float *__restrict__ params,
+                    float *__restrict__ cost, float *__restrict__ cost0) {
+  __shared__ LmLds s;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double *st = state + (size_t)b * kLmState;
+  const bool own = lane < kLmN;
+  const float tq = own ? trial[(size_t)b * kLmN + lane] : 0.f;
+  const double pr = !own ? 0.0 : prior ? (double)prior[(size_t)b * kLmN + lane] : st[kLmP0 + lane];
+  const double mu = own && stiffness ? (double)stiffness[lane] : 0.0;
+  if (own) {
+    const double d = (double)tq - pr;
+    s.x[lane] = mu * (d * d);
+  }
+  const double cur = st[kLmCost], lam0 = st[kLmLambda];
+  const bool fresh = st[kLmFresh] != 0.0, moved = st[kLmMoved] != 0.0;
+  const double accepts = st[kLmAccepts], rejects = st[kLmRejects];
+  __syncthreads();
+  double total = cost_data[b];
+#pragma unroll 1
+  for (int i = 0; i < kLmN; i++) total += s.x[i];
+  const bool accept = total < cur && total > -__builtin_inf();        // (false for a NaN, and for +inf)
+  const double lam = fmin(fmax(lam0 * (accept ? (moved ? 0.3 : 1.0) : 10.0), 1e-9), 1e6);
+  // the accepted pose and its equations: the trial's where it is accepted, the state's otherwise -- all read before the state is written
+  const double *As = accept ? A + (size_t)b * kLmN * kLmN : st + kLmA;
+  for (int e = lane; e < kLmN * kLmN; e += 64) s.A[e] = As[e];
+  const double pa = !own ? 0.0 : accept ? (double)tq : st[kLmP + lane];
+  const double ga = !own ? 0.0 : accept ? g[(size_t)b * kLmN + lane] : st[kLmG + lane];
+  __syncthreads();
+  if (accept) {
+    for (int e = lane; e < kLmN * kLmN; e += 64) st[kLmA + e] = s.A[e];
+    if (own) { st[kLmG + lane] = ga; st[kLmP + lane] = pa; }
+  }
+  if (lane == 0) {
+    st[kLmCost] = accept ? total : cur;
+    st[kLmLambda] = lam;
+    st[kLmFresh] = 0.0;
+    st[kLmMoved] = (moved || accept) ? 1.0 : 0.0;
+    st[kLmAccepts] = accepts + (accept ? 1.0 : 0.0);
+    st[kLmRejects] = rejects + (accept ? 0.0 : 1.0);
+    cost[b] = (float)(accept ? total : cur);
+    if (fresh) cost0[b] = (float)total;
+  }
+  if (own) params[(size_t)b * kLmN + lane] = (float)pa;
+  if (!solve) return;
+  __syncthreads();
+  if (own) s.A[lane * kLmN + lane] += mu;                              // M = A + diag(mu)
+  __syncthreads();
+  const bool ok = lm_cholesky(s, lam, lane);
+  __syncthreads();
+  if (ok) lm_solve(s, -(ga + mu * (pa - pr)), lane);
+  if (own) trial_out[(size_t)b * kLmN + lane] = ok ? (float)(pa + s.x[lane]) : (float)pa;
+}
+
+}  // namespace shr
+
+using namespace shr;
+
+static long long icp_tiles(int W, int H) { return ((long long)W * H + kIcpTilePix - 1) / kIcpTilePix; }
+
+extern "C" long long shr_pose_icp_normal_workspace_bytes(int B, int W, int H) {
+  if (B < 0 || W < 0 || H < 0) return -1;
+  return (long long)B * icp_tiles(W, H) * kIcpSlots * 8;
+}
+
+extern "C" int shr_pose_icp_normal(const float *observed, const float *vertices, const int32_t *faces, const float *dist,
+                                   const int32_t *face, const float *params, const float *offset, const float *offset_inv,
+                                   const int32_t *skin_vertex_start, const int32_t *skin_bone, const float *skin_wv,
+                                   int right_hand, int B, int NV, int F, int W, int H, float ax, float bx, float ay, float by,
+                                   float fg_max, float max_dist, double *A, double *g, double *cost, int32_t *count,
+                                   void *workspace, void *stream) {
+  if (int rc = d2m_check(B, NV, F, W, H, max_dist)) return rc;
+  if (B == 0) return SHR_OK;
+  if (!observed || !vertices || (!faces && F > 0) || !dist || !face || !skin_vertex_start || !skin_bone || !skin_wv || !A || !g ||
+      !cost || !count || !workspace)
+    return SHR_EINVAL;
+  if (int rc = fk_check(params, B, offset, offset_inv)) return rc;
+  if ((((uintptr_t)observed | (uintptr_t)faces | (uintptr_t)dist | (uintptr_t)face | (uintptr_t)params |
+        (uintptr_t)skin_vertex_start | (uintptr_t)skin_bone | (uintptr_t)count) & 3u) != 0)
+    return SHR_EINVAL;
+  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost) & 7u) != 0) return SHR_EINVAL;
+  if ((((uintptr_t)vertices | (uintptr_t)skin_wv | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if ((long long)B * NV > (1LL << 30)) return SHR_ETOOLARGE;
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles = (int)icp_tiles(W, H);
+  double *part = reinterpret_cast<double *>(workspace);
+  hipLaunchKernelGGL(pose_icp_tiles_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(kIcpThreads), 0, s, observed,
+                     reinterpret_cast<const float4 *>(vertices), faces, dist, face, params, offset, offset_inv,
+                     skin_vertex_start, skin_bone, reinterpret_cast<const float4 *>(skin_wv), right_hand ? -1.0f : 1.0f, NV, F,
+                     W, H, ax, bx, ay, by, fg_max, max_dist, part);
+  hipLaunchKernelGGL(pose_icp_reduce_kernel, dim3((unsigned)B), dim3(kIcpSlots), 0, s, part, tiles, A, g, cost, count);
+  return (int)hipGetLastError();
+}
+
+extern "C" long long shr_pose_lm_state_bytes(int B) {
+  if (B < 0) return -1;
+  return (long long)B * kLmState * 8;
+}
+
+static int lm_check(const void *state, int B) {
+  if (!state || B < 0 || (((uintptr_t)state) & 7u) != 0) return SHR_EINVAL;
+  if (B > (1 << 24)) return SHR_ETOOLARGE;
+  return SHR_OK;
+}
+
+extern "C" int shr_pose_lm_begin(const float *params0, int B, float lambda0, void *state, float *trial, void *stream) {
+  if (B == 0) return SHR_OK;
+  if (int rc = lm_check(state, B)) return rc;
+  if (!params0 || !trial || !(lambda0 > 0.0f) || (((uintptr_t)params0 | (uintptr_t)trial) & 3u) != 0) return SHR_EINVAL;
+  hipLaunchKernelGGL(pose_lm_begin_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, params0, lambda0,
+                     reinterpret_cast<double *>(state), trial);
+  return (int)hipGetLastError();
+}
+
+extern "C" int shr_pose_lm_step(void *state, const double *A, const double *g, const double *cost_data, const float *trial,
+                                const float *prior, const float *stiffness, int solve, int B, float *trial_out, float *params,
+                                float *cost, float *cost0, void *stream) {
+  if (B == 0) return SHR_OK;
+  if (int rc = lm_check(state, B)) return rc;
+  if (!A || !g || !cost_data || !trial || !params || !cost || !cost0 || (solve && !trial_out)) return SHR_EINVAL;
+  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost_data) & 7u) != 0) return SHR_EINVAL;
+  if ((((uintptr_t)trial | (uintptr_t)prior | (uintptr_t)stiffness | (uintptr_t)trial_out | (uintptr_t)params | (uintptr_t)cost |
+        (uintptr_t)cost0) & 3u) != 0)
+    return SHR_EINVAL;
+  hipLaunchKernelGGL(pose_lm_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<double *>(state),
+                     A, g, cost_data, trial, prior, stiffness, solve ? 1 : 0, trial_out, params, cost, cost0);
+  return (int)hipGetLastError();
+}

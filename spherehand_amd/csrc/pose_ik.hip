@@ -13,14 +13,15 @@
 //     would show as 5e-5 mm/rad); row x of the right hand negated;
 //   * the normal equations, the Cholesky factor, both solves and the costs in fp64 (the fp32 Jacobian and residuals are
 //     the only fp32 roundings of an iteration), every sum in a fixed order: lane `idx mod 64` sums entry idx over the
-//     points in index order, the factor goes column by column, lane i owning row i.
+//     points in index order, the factor goes column by column, lane i owning row i (lm_solve.h, shared with pose_icp.hip).
 // Lane-uniform control: every lane derives lambda, the costs and the accept decision from the same LDS values.
 #include "fk_rows.h"
+#include "lm_solve.h"
 
 namespace shr {
 
 constexpr int kIkPoints = 64;        // key-points per crop (lane j owns point j)
-constexpr int kIkN = 26;             // pose parameters
+constexpr int kIkN = kLmN;           // pose parameters
 constexpr int kIkTri = kIkN * (kIkN + 1) / 2;
 
 struct IkPoint {                     // lane j's point: bone, rest position, weight and the keypoint at the last evaluation
@@ -166,49 +167,6 @@ __device__ __forceinline__ void ik_normal(IkLds &s, const float *p, int lane, in
   __syncthreads();
 }
 
-// L L^T = A + lam diag(A), column by column, lane i owning row i.  false: a pivot that is not positive and finite.
-__device__ __forceinline__ bool ik_cholesky(IkLds &s, double lam, int lane) {
-#pragma unroll 1
-  for (int k = 0; k < kIkN; k++) {
-    double v = 0.0;
-    if (lane >= k && lane < kIkN) {
-      v = s.A[lane * kIkN + k];
-      if (lane == k) v += lam * v;
-#pragma unroll 2
-      for (int m = 0; m < k; m++) v -= s.L[lane * kIkN + m] * s.L[k * kIkN + m];
-      if (lane == k) s.piv = v;
-    }
-    __syncthreads();
-    const double d = s.piv;
-    if (!(d > 0.0 && d < __builtin_inf())) return false;
-    const double root = sqrt(d);
-    if (lane >= k && lane < kIkN) s.L[lane * kIkN + k] = lane == k ? root : v / root;
-    __syncthreads();
-  }
-  return true;
-}
-
-// s.x = (L L^T)^-1 rhs (lane i < 26 brings rhs_i): forward then backward substitution, one unknown per step
-__device__ __forceinline__ void ik_solve(IkLds &s, double rhs, int lane) {
-  double acc = 0.0;
-#pragma unroll 1
-  for (int k = 0; k < kIkN; k++) {
-    if (lane == k) s.x[k] = (rhs - acc) / s.L[k * kIkN + k];
-    __syncthreads();
-    if (lane > k && lane < kIkN) acc += s.L[lane * kIkN + k] * s.x[k];
-  }
-  const double z = lane < kIkN ? s.x[lane] : 0.0;
-  acc = 0.0;
-  __syncthreads();
-#pragma unroll 1
-  for (int k = kIkN - 1; k >= 0; k--) {
-    if (lane == k) s.x[k] = (z - acc) / s.L[k * kIkN + k];
-    __syncthreads();
-    if (lane < k) acc += s.L[k * kIkN + lane] * s.x[k];
-  }
-  __syncthreads();
-}
-
 __global__ void __launch_bounds__(64)
 pose_keypoints_jacobian_kernel(const float *__restrict__ params, const float *__restrict__ offset,
                                const float *__restrict__ offset_inv, int J, const int *__restrict__ bone,
@@ -269,10 +227,10 @@ pose_ik_fwd_kernel(const float *__restrict__ target, const float *__restrict__ p
       ik_jacobian(s, pt, s.p, sx, offset, offset_inv, lane, J);
       ik_normal<true>(s, s.p, lane, J);
     }
-    tried = ik_cholesky(s, lam, lane);
+    tried = lm_cholesky(s, lam, lane);
     __syncthreads();
     if (tried) {
-      ik_solve(s, lane < kIkN ? -s.g[lane] : 0.0, lane);
+      lm_solve(s, lane < kIkN ? -s.g[lane] : 0.0, lane);
       if (lane < kIkN) s.q[lane] = (float)((double)s.p[lane] + s.x[lane]);
       __syncthreads();
     }
@@ -298,9 +256,9 @@ pose_ik_bwd_kernel(const float *__restrict__ params, const float *__restrict__ g
   ik_keypoints(s, pt, params, b, offset, offset_inv, lane, J);
   ik_jacobian(s, pt, params + (size_t)b * kIkN, sx, offset, offset_inv, lane, J);
   ik_normal<false>(s, nullptr, lane, J);
-  const bool ok = ik_cholesky(s, 0.0, lane);
+  const bool ok = lm_cholesky(s, 0.0, lane);
   __syncthreads();
-  if (ok) ik_solve(s, gp, lane);
+  if (ok) lm_solve(s, gp, lane);
   if (lane < J) {
     float *o = grad_target + ((size_t)b * J + lane) * 3;
     const float *row = s.jac + 3 * lane * kIkN;

@@ -1968,6 +1968,161 @@ class MeshDataToModel(torch.autograd.Function):
         return None, _grad_as_given(ctx, g), None, None, None, None
 
 
+def _icp_args(observed, vertices, faces, params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, pixel_to_model,
+              max_dist, name="parameters"):
+    B, H, W, NV, F, p2m, max_dist = _d2m_args(observed, vertices, faces, pixel_to_model, max_dist)
+    for t, what in ((params, name), (offset, "offset"), (offset_inv, "offset_inv")):
+        _check_input(t, what)
+    if tuple(params.shape) != (B, 26) or params.device != observed.device:
+        raise RuntimeError("%s must be [B,26] with observed's B, on its device" % name)
+    if tuple(offset.shape) != (17, 4, 4) or tuple(offset_inv.shape) != (17, 4, 4):
+        raise RuntimeError("offset and offset_inv must be [17,4,4]")
+    if _skin_tables(skin_vertex_start, skin_bone, skin_wv, None) != NV:
+        raise RuntimeError("the skin table must have the vertices' NV rows")
+    return B, H, W, NV, F, p2m, max_dist
+
+
+def pose_icp_normal(observed, vertices, faces, dist, face, params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv,
+                    right_hand=True, pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf")):
+    """The Gauss-Newton normal equations of 1/2 sum dist^2 of the mesh data-to-model distance with respect to the pose
+    (include/spherehand_hip.h, shr_pose_icp_normal): dist, face = mesh_data_to_model(observed, vertices, ...) and vertices
+    those of `params` in model space (PoseVertices with camera=None; NOT checked) -> (A [B,26,26] fp64, g [B,26] fp64,
+    cost [B] fp64 = sum dist^2 over all pixels, count [B] int32 = the contributing points)."""
+    B, H, W, NV, F, p2m, max_dist = _icp_args(observed, vertices, faces, params, offset, offset_inv, skin_vertex_start,
+                                              skin_bone, skin_wv, pixel_to_model, max_dist)
+    _check_input(dist, "dist")
+    _check_input(face, "face", torch.int32)
+    for t, name in ((dist, "dist"), (face, "face")):
+        if t.shape != observed.shape or t.device != observed.device:
+            raise RuntimeError("%s must be [B,H,W] as observed, on its device" % name)
+    lib = _lib.lib()
+    dev = observed.device
+    with _on(dev):
+        A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+        cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(16, lib.shr_pose_icp_normal_workspace_bytes(B, W, H)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.shr_pose_icp_normal(_ptr(observed), _ptr(vertices), _ptr(faces), _ptr(dist), _ptr(face), _ptr(params),
+                                           _ptr(offset), _ptr(offset_inv), _ptr(skin_vertex_start), _ptr(skin_bone),
+                                           _ptr(skin_wv), int(bool(right_hand)), B, NV, F, W, H, *p2m, float(fg_max), max_dist,
+                                           _ptr(A), _ptr(g), _ptr(cost), _ptr(count), _ptr(ws), _stream()),
+                   "shr_pose_icp_normal")
+    return A, g, cost, count
+
+
+def pose_lm_begin(params0, lambda0=1e-3):
+    """Start a Levenberg-Marquardt loop on the device (shr_pose_lm_begin): params0 [B,26] -> (state, trial [B,26]): the
+    opaque per-crop state pose_lm_step takes and the first pose to evaluate, params0."""
+    _check_input(params0, "start parameters")
+    if params0.dim() != 2 or params0.shape[1] != 26:
+        raise RuntimeError("start parameters must be [B,26]")
+    if not float(lambda0) > 0:
+        raise RuntimeError("lambda0 must be > 0")
+    B = params0.shape[0]
+    lib = _lib.lib()
+    with _on(params0.device):
+        state = torch.empty((max(1, lib.shr_pose_lm_state_bytes(B) // 8),), dtype=torch.float64, device=params0.device)
+        trial = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
+        _lib.check(lib.shr_pose_lm_begin(_ptr(params0), B, float(lambda0), _ptr(state), _ptr(trial), _stream()),
+                   "shr_pose_lm_begin")
+    return state, trial
+
+
+def pose_lm_step(state, A, g, cost_data, trial, prior=None, stiffness=None, solve=True, out=None):
+    """One step of the loop (shr_pose_lm_step): A [B,26,26], g [B,26], cost_data [B] fp64 of the pose `trial` [B,26] ->
+    (trial_out [B,26] or None without `solve`, params [B,26], cost [B], cost0 [B]).  prior [B,26] (default: the start
+    pose) and stiffness [26] add sum_i stiffness_i (p_i - prior_i)^2.  cost0 is written by the first step after
+    pose_lm_begin only.  out = (trial_out, params, cost, cost0): buffers to write instead of new ones."""
+    _check_input(trial, "trial")
+    B = trial.shape[0]
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost_data, "cost_data", (B,))):
+        _check_input(t, name, torch.float64)
+        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    lib = _lib.lib()
+    if state.numel() * 8 < lib.shr_pose_lm_state_bytes(B):
+        raise RuntimeError("state is pose_lm_begin's, for the same B")
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    with _on(trial.device):
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
+            out = (new(B, 26) if solve else None, new(B, 26), new(B), new(B))
+        trial_out, params, cost, cost0 = out
+        _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                        _ptr(stiffness), int(bool(solve)), B, _ptr(trial_out) if solve else None, _ptr(params),
+                                        _ptr(cost), _ptr(cost0), _stream()), "shr_pose_lm_step")
+    return (trial_out if solve else None), params, cost, cost0
+
+
+def pose_icp(observed, params0, faces, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, right_hand=True,
+             pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+             stiffness=None, prior=None):
+    """Fit the pose to an observed depth image through the mesh: `iters` Levenberg-Marquardt iterations on
+    sum dist^2 + sum_i stiffness_i (p_i - prior_i)^2 from params0 [B,26], dist the mesh data-to-model distance of
+    mesh_data_to_model saturated at max_dist -> (params [B,26], cost0 [B], cost [B]).  Each of the iters + 1 evaluations
+    is shr_pose_vertices_fwd (model space) -> shr_mesh_d2m_fwd -> shr_pose_icp_normal -> shr_pose_lm_step on torch's
+    current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a graph.
+    iters = 0 returns params0 and cost = cost0."""
+    _check_input(observed, "observed")
+    _check_input(faces, "faces", torch.int32)
+    if observed.dim() != 3 or observed.shape[1] < 1 or observed.shape[2] < 1 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("observed must be [B,H,W] with H, W >= 1 and faces [F,3]")
+    dev = observed.device
+    B, H, W = observed.shape
+    NV, F = _skin_tables(skin_vertex_start, skin_bone, skin_wv, None), faces.shape[0]
+    verts = torch.empty((B, NV, 4), dtype=torch.float32, device=dev)
+    _, _, _, _, _, p2m, max_dist = _icp_args(observed, verts, faces, params0, offset, offset_inv, skin_vertex_start, skin_bone,
+                                             skin_wv, pixel_to_model, max_dist, "start parameters")
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    state, trial = pose_lm_begin(params0, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        dist, face = f32(B, H, W), torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        params, cost0, cost = f32(B, 26), f32(B), f32(B)
+        ws_d2m = torch.empty((max(16, lib.shr_mesh_d2m_workspace_bytes(B, F)),), dtype=torch.uint8, device=dev)
+        ws_icp = torch.empty((max(16, lib.shr_pose_icp_normal_workspace_bytes(B, W, H)),), dtype=torch.uint8, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_vertices_fwd(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), NV, _ptr(skin_vertex_start),
+                                                 _ptr(skin_bone), _ptr(skin_wv), right, 0, 0.0, 0.0, 1.0, 1.0, None,
+                                                 _ptr(verts), None, stream), "shr_pose_vertices_fwd")
+            _lib.check(lib.shr_mesh_d2m_fwd(_ptr(observed), _ptr(verts), _ptr(faces), B, NV, F, W, H, *p2m, fg_max, max_dist,
+                                            _ptr(dist), _ptr(face), _ptr(ws_d2m), stream), "shr_mesh_d2m_fwd")
+            _lib.check(lib.shr_pose_icp_normal(_ptr(observed), _ptr(verts), _ptr(faces), _ptr(dist), _ptr(face), _ptr(trial),
+                                               _ptr(offset), _ptr(offset_inv), _ptr(skin_vertex_start), _ptr(skin_bone),
+                                               _ptr(skin_wv), right, B, NV, F, W, H, *p2m, fg_max, max_dist, _ptr(A), _ptr(g),
+                                               _ptr(cost_data), _ptr(count), _ptr(ws_icp), stream), "shr_pose_icp_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
+                                            _ptr(cost0), stream), "shr_pose_lm_step")
+    return params, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

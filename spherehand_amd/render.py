@@ -17,6 +17,7 @@ signatures and return values), running on the hand-written HIP kernels.
     NormalConsistencyLoss    1 - m . o between two normal maps: the orientation term
     MeshVertices             bone transforms or pose -> the mesh's vertices, differentiable: the mesh terms' way to the pose
     KeypointPoseSolver       the 41 keypoints -> the pose, by Levenberg-Marquardt from a start pose: the way INTO the mesh path
+    MeshPoseFitter           the pose fitted to an observed depth image: Gauss-Newton ICP on the mesh, from such a start
 """
 import numpy as np
 import torch
@@ -728,6 +729,63 @@ class KeypointPoseSolver(nn.Module):
         p = K.new_zeros(B, 26)
         p[:, 0], p[:, 1], p[:, 2], p[:, 3:6] = ax, ay, az, t
         return p.to(keypoints.dtype)
+
+
+class MeshPoseFitter(nn.Module):
+    """The pose fitted to an observed depth image through the triangle mesh: `iters` Gauss-Newton / Levenberg-Marquardt
+    iterations on sum dist^2 + sum_i stiffness_i (p_i - prior_i)^2, dist being MeshDataToModelLoss's distance of every
+    observed point to its closest point on the mesh, saturated at max_dist (ops.pose_icp; include/spherehand_hip.h,
+    shr_pose_icp_normal and shr_pose_lm_step, has the equations and the iteration).  Each iteration is one closest-point
+    search, where a first-order step through MeshDataToModelLoss and MeshVertices.pose_vertices needs the same search for
+    a far smaller gain.  A REFINEMENT from a start pose: the intended start is KeypointPoseSolver's pose from the
+    network's keypoints, or the previous frame's pose.
+        solve(observed[B,H,W], params0[B,26], prior=None) -> (params, cost0, cost)
+        normal_equations(observed, params) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32)
+    There is NO autograd through the solve: the observation is data, and nothing here is differentiable.
+    pixel_to_model, fg_max, max_dist: MeshDataToModelLoss's.  stiffness: [26], each >= 0 (a buffer); prior: [B,26], default
+    the start pose.  One depth view does not determine an occluded finger: without stiffness the matrix of such a crop
+    is singular up to rounding and the damping alone bounds the step (DESIGN.md 4.4n has what was measured)."""
+
+    def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
+                 fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0):
+        super().__init__()
+        from .kinematicsTransformation import HandTransformationMat
+        self.vertices = MeshVertices(mesh, camera=None, right_hand=right_hand, distinct=True)
+        self.fk = HandTransformationMat([np.asarray(b['offset_matrix']).astype(np.float32) for b in mesh['bones']])
+        self.register_buffer('faces_i32', torch.from_numpy(np.ascontiguousarray(self.vertices.faces, np.int32)))
+        self.register_buffer('stiffness', None if stiffness is None else
+                             torch.as_tensor(np.asarray(stiffness, np.float32)).reshape(26).clone())
+        self.width, self.height = int(width), int(height)
+        p2m = MeshDataToModelLoss.reference_grid(width, height) if pixel_to_model is None else pixel_to_model
+        self.pixel_to_model = tuple(float(t) for t in p2m)
+        self.right_hand = bool(right_hand)
+        self.iters = int(iters)
+        self.lambda0 = float(lambda0)
+        self.fg_max = float(fg_max)
+        self.max_dist = float(max_dist)
+
+    def _observed(self, observed):
+        if observed.dim() != 3 or tuple(observed.shape[1:]) != (self.height, self.width):
+            raise RuntimeError("MeshPoseFitter takes observed [B,%d,%d]" % (self.height, self.width))
+        return observed.detach().contiguous().float()
+
+    @torch.no_grad()
+    def solve(self, observed, params0, prior=None):
+        lbs = self.vertices.lbs
+        return ops.pose_icp(self._observed(observed), params0.detach().contiguous().float(), self.faces_i32, self.fk.offset,
+                            self.fk.offset_inv, lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, self.right_hand,
+                            self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                            None if prior is None else prior.detach().contiguous().float())
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params):
+        lbs = self.vertices.lbs
+        observed, params = self._observed(observed), params.detach().contiguous().float()
+        verts = self.vertices.pose_vertices(self.fk, params)
+        dist, face = ops.mesh_data_to_model(observed, verts, self.faces_i32, self.pixel_to_model, self.fg_max, self.max_dist)
+        return ops.pose_icp_normal(observed, verts, self.faces_i32, dist, face, params, self.fk.offset, self.fk.offset_inv,
+                                   lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, self.right_hand, self.pixel_to_model,
+                                   self.fg_max, self.max_dist)
 
 
 class DepthRender(nn.Module):
