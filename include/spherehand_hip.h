@@ -1043,6 +1043,51 @@ int shr_pose_lm_step(void *state, const double *A, const double *g, const double
                      const float *prior /* may be NULL */, const float *stiffness /* may be NULL */, int solve, int B,
                      float *trial_out, float *params, float *cost, float *cost0, void *stream);
 
+/* One pose fitted to several depth views: multi-view ICP on the mesh ---------------
+ * One pose per sample in the model frame, V observed depth images per sample, one rigid transform per view: view[B,V,4,4]
+ * fp32, row-major, maps the model frame to view v's frame, x_v = R x + t (the top-left 3 x 3 and the last column; the
+ * fourth row is not read).  With camera poses as MutualTransformation takes them (mesh/multiview_utility.py:13-30),
+ * view[:, v] = inv_camera_poses[:, v] @ camera_poses[:, ref]: its (ref, v) entry.  All views share W, H, ax .. by, fg_max
+ * and max_dist.  An iteration is one Levenberg-Marquardt step on the sum of all views' point-to-mesh costs:
+ *   shr_pose_vertices_fwd(trial, project = 0) -> shr_view_vertices_fwd -> shr_mesh_d2m_fwd (B V crops)
+ *   -> shr_pose_icp_normal_views -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.  The reference has no counterpart.
+ *   shr_view_vertices_fwd  vertices[B,NV,4] in model space (shr_pose_vertices_fwd's with project = 0) and view -> out
+ *       [B,V,NV,4] fp32: out.x = ((R00 x + R01 y) + R02 z) + t0, and y, z alike with rows 1 and 2 -- the three products and
+ *       the sums in exactly this association, each operation rounded to fp32 once (no fused multiply-add); the 4th float is
+ *       copied.  For the identity view, out holds the bits of its input (a -0 becomes +0).
+ *   shr_pose_icp_normal_views  shr_pose_icp_normal's equations, summed over the views.  observed, dist, face: [B,V,H,W],
+ *       crop b V + v being view v of sample b; view_vertices[B,V,NV,4]: shr_view_vertices_fwd's (as for `vertices` there:
+ *       they MUST be those of params under view, which is NOT checked); dist, face: shr_mesh_d2m_fwd's maps of the B V
+ *       crops; params[B,26], offset, offset_inv, the skin table, right_hand, faces, ax .. max_dist: shr_pose_icp_normal's.
+ *       The top-left 3 x 3 of a view is read as a rotation: it is NOT checked to be orthonormal, and another matrix gives
+ *       the equations of no function.
+ *       Row rule: a pixel of view v gives a row under shr_pose_icp_normal's rule (a data point, its face in [0, F) with ids
+ *       in [0, NV), 0 < dist < max_dist, the recomputed distance finite and not zero); its closest point is recomputed in
+ *       fp64 on the VIEW-frame vertices, on the saved face: corner weights w_k, e = p - c, d = |e|, u_v = e / d; the unit
+ *       direction is taken back to the model frame in fp64, u_j = (R0j u_v0 + R1j u_v1) + R2j u_v2 (u = R^T u_v: a distance
+ *       does not change under a rigid map, so the row with respect to the pose needs nothing else of the view); from there
+ *       the row is shr_pose_icp_normal's with this u, the same device code: the cross products for the palm angles, w_k u
+ *       for the translation, the finger tangents, component x negated for the right hand.
+ *       -> A[B,26,26], g[B,26], cost[B] fp64 and count[B] int32 as there, over all pixels of all views: cost = sum dist^2
+ *       over the B V maps.  A view without a data point (a missing camera: an all-background image) adds nothing.
+ *       Summation order (the contract): pixels ascending inside a tile of 1024 (one fp64 chain from 0, as there), tiles
+ *       ascending inside a view, views ascending: the V tiles values of a sample are added from 0 in this order.  Bitwise
+ *       reproducible; a sample's result does not depend on the batch it is in or on the launch shape.  For V = 1 and the
+ *       identity view it is shr_pose_icp_normal's result bit for bit.
+ *       workspace: 16-byte aligned, shr_pose_icp_normal_views_workspace_bytes(B, V, W, H) bytes (-1 on a negative size):
+ *       3072 bytes per (sample, view, tile), written by the call before it is read.
+ *   Argument rules (both entries): shr_pose_icp_normal's limits, alignments (view, view_vertices, out: 16 bytes) and error
+ *   codes; V < 1: SHR_EINVAL; B V above 65535 or B V NV above 2^30: SHR_ETOOLARGE; B == 0 is a no-op. */
+int shr_view_vertices_fwd(const float *vertices, const float *view, int B, int V, int NV, float *out, void *stream);
+long long shr_pose_icp_normal_views_workspace_bytes(int B, int V, int W, int H);
+int shr_pose_icp_normal_views(const float *observed, const float *view_vertices, const int32_t *faces, const float *dist,
+                              const int32_t *face, const float *view, const float *params, const float *offset,
+                              const float *offset_inv, const int32_t *skin_vertex_start, const int32_t *skin_bone,
+                              const float *skin_wv, int right_hand, int B, int V, int NV, int F, int W, int H, float ax,
+                              float bx, float ay, float by, float fg_max, float max_dist, double *A, double *g, double *cost,
+                              int32_t *count, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

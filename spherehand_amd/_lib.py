@@ -133,6 +133,9 @@ SIGNATURES = {
     "shr_pose_lm_state_bytes": ([_i], ctypes.c_longlong),
     "shr_pose_lm_begin": ([_vp, _i, _f, _vp, _vp, _vp], _i),
     "shr_pose_lm_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "shr_view_vertices_fwd": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "shr_pose_icp_normal_views_workspace_bytes": ([_i, _i, _i, _i], ctypes.c_longlong),
+    "shr_pose_icp_normal_views": ([_vp] * 12 + [_i] * 7 + [_f] * 6 + [_vp] * 6, _i),
     "shr_selftest_sqrt":([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_division": ([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_launch_floor": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),

@@ -15,44 +15,12 @@
 //            cm . (dT wv) to the bone's finger angles.  Nothing is assumed about which fingers a row touches.  Then thread
 //            t sums entry t (and t + 256) of [A's lower triangle | g | cost | count] over the round's pixels in pixel order.
 //   reduce   one workgroup per crop adds the tiles' sums in tile order and writes A (both triangles), g, cost, count.
+//            (Both bodies are icp_tile.h's, which the multi-view entry of pose_icp_views.hip shares.)
 //   lm       one wave per crop: the accept test, lambda, and lm_solve.h's damped solve -- pose_ik.hip's iteration, split
 //            where the cost evaluation needs other kernels.
-#include "d2m_tap.h"
-#include "fk_rows.h"
-#include "lm_solve.h"
+#include "icp_tile.h"
 
 namespace shr {
-
-constexpr int kIcpThreads = 256;
-constexpr int kIcpRounds = 4;
-constexpr int kIcpTilePix = kIcpThreads * kIcpRounds;   // the unit of the summation order: part of the contract
-constexpr int kIcpTri = kLmN * (kLmN + 1) / 2;          // 351
-constexpr int kIcpSlots = 384;                          // doubles of a tile's record in the workspace: A's lower triangle, g,
-static_assert(kIcpTri + kLmN + 2 <= kIcpSlots, "");     // cost, count (379), one thread of the reduction each
-constexpr int kIcpRow = kLmN + 1;                       // a row's stride in LDS (27: the threads' rows start in different banks)
-
-struct IcpLds {
-  Rot sc[kAngles];
-  float4 T[kBones * 4];
-  float4 dT[5 * kFingerTangents * 3];
-  float jac[kIcpThreads * kIcpRow];
-  double d[kIcpThreads];                                // the row's distance, 0: the pixel has no row
-  double c2[kIcpThreads];                               // the pixel's dist^2 of the forward's map
-};
-
-enum { kIcpA = 0, kIcpG = 1, kIcpCost = 2, kIcpCount = 3, kIcpNone = 4 };
-
-// entry idx of a tile's record: (kind, a, c)
-__device__ __forceinline__ int icp_entry(int idx, int &a, int &c) {
-  a = c = 0;
-  if (idx < kIcpTri) {
-    while ((a + 1) * (a + 2) / 2 <= idx) a++;
-    c = idx - a * (a + 1) / 2;                          // a >= c
-    return kIcpA;
-  }
-  if (idx < kIcpTri + kLmN) { a = idx - kIcpTri; return kIcpG; }
-  return idx == kIcpTri + kLmN ? kIcpCost : idx == kIcpTri + kLmN + 1 ? kIcpCount : kIcpNone;
-}
 
 __global__ void __launch_bounds__(kIcpThreads)
 pose_icp_tiles_kernel(const float *__restrict__ observed, const float4 *__restrict__ vertices, const int *__restrict__ faces,
@@ -60,114 +28,15 @@ pose_icp_tiles_kernel(const float *__restrict__ observed, const float4 *__restri
                       const float *__restrict__ offset, const float *__restrict__ offset_inv, const int *__restrict__ vstart,
                       const int *__restrict__ sbone, const float4 *__restrict__ swv, float sx, int NV, int F, int W, int H,
                       float ax, float bx, float ay, float by, float fg_max, float max_dist, double *__restrict__ part) {
-  __shared__ IcpLds s;
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const size_t npix = (size_t)H * W, base = (size_t)blockIdx.x * kIcpTilePix;
-  if (tid < 64) pose_transforms_wave<false>(params, offset, offset_inv, b, tid, s.sc, nullptr, s.T, SynthDraws{});
-  __syncthreads();
-  if (tid < 64) pose_finger_tangents_wave(params + (size_t)b * kLmN, offset, offset_inv, tid, s.sc, s.dT);
-  int a0, c0, a1, c1;
-  icp_entry(tid, a0, c0);                               // (tid < 256 < 351: an entry of A)
-  const int kind1 = icp_entry(tid + kIcpThreads, a1, c1);
-  double acc0 = 0.0, acc1 = 0.0;
-  float *row = s.jac + tid * kIcpRow;
-#pragma unroll 1
-  for (int r = 0; r < kIcpRounds; r++) {
-    const size_t i = base + (size_t)(r * kIcpThreads + tid);
-    double dn = 0.0, c2 = 0.0;
-    bool live = false;
-    D2mClosest t;
-    if (i < npix) {
-      const float z = observed[(size_t)b * npix + i], d = dist[(size_t)b * npix + i];
-      c2 = (double)d * (double)d;
-      if (d2m_measured(z, d, fg_max, max_dist))
-        live = d2m_closest(vertices + (size_t)b * NV, faces, NV, F, face[(size_t)b * npix + i], i, W, ax, bx, ay, by, z, t);
-    }
-    // (a barrier: the last round's sums have read the rows, and the first round's tangents are in LDS)
-    if (__syncthreads_or(live || c2 != 0.0) == 0) continue;
-    for (int q = 0; q < kLmN; q++) row[q] = 0.f;
-    if (live) {
-      dn = t.n;
-      const double u[3] = {t.e[0] / t.n, t.e[1] / t.n, t.e[2] / t.n};
-      const float4 r0 = s.T[0], r1 = s.T[1], r2 = s.T[2];
-      double mx = 0.0, my = 0.0, mz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const double cx = (double)sx * -(t.wk[k] * u[0]), cy = -(t.wk[k] * u[1]), cz = -(t.wk[k] * u[2]);
-        const int v = t.pid[k];                         // in [0, NV): d2m_closest checked it
-#pragma unroll 1
-        for (int e = vstart[v]; e < vstart[v + 1]; e++) {
-          const int bone = min(max(sbone[e], 0), kBones - 1);   // (as shr_pose_vertices_fwd: a matrix of the table)
-          const float4 q = swv[e];
-          const float4 m0 = s.T[4 * bone], m1 = s.T[4 * bone + 1], m2 = s.T[4 * bone + 2];
-          const float px = ((m0.x * q.x + m0.y * q.y) + m0.z * q.z) + m0.w * q.w;
-          const float py = ((m1.x * q.x + m1.y * q.y) + m1.z * q.z) + m1.w * q.w;
-          const float pz = ((m2.x * q.x + m2.y * q.y) + m2.z * q.z) + m2.w * q.w;
-          const double rx = (double)(px - q.w * r0.w), ry = (double)(py - q.w * r1.w), rz = (double)(pz - q.w * r2.w);
-          mx += ry * cz - rz * cy; my += rz * cx - rx * cz; mz += rx * cy - ry * cx;
-          tx += (double)q.w * cx; ty += (double)q.w * cy; tz += (double)q.w * cz;
-          if (bone >= 2) {
-            const int f = (bone - 2) / 3, level = (bone - 2) - 3 * f;
-            float *fr = row + 6 + 4 * f;
-            for (int a = 0; a < 4; a++) {
-              if (a > level + 1) break;
-              const float4 *d = s.dT + (kFingerTangents * f + tangent_slot(a, level)) * 3;
-              const float dx = ((d[0].x * q.x + d[0].y * q.y) + d[0].z * q.z) + d[0].w * q.w;
-              const float dy = ((d[1].x * q.x + d[1].y * q.y) + d[1].z * q.z) + d[1].w * q.w;
-              const float dz = ((d[2].x * q.x + d[2].y * q.y) + d[2].z * q.z) + d[2].w * q.w;
-              fr[a] += (float)((cx * (double)dx + cy * (double)dy) + cz * (double)dz);
-            }
-          }
-        }
-      }
-      // omega . m for omega = P e_x, Rz e_y = (-s, c, 0), e_z (pose_ik.hip's palm columns)
-      const Rot az = s.sc[2];
-      row[0] = (float)(((double)r0.x * mx + (double)r1.x * my) + (double)r2.x * mz);
-      row[1] = (float)((double)az.c * my - (double)az.s * mx);
-      row[2] = (float)mz;
-      row[3] = (float)tx; row[4] = (float)ty; row[5] = (float)tz;
-    }
-    s.d[tid] = dn;
-    s.c2[tid] = c2;
-    __syncthreads();
-#pragma unroll 2
-    for (int j = 0; j < kIcpThreads; j++) {
-      const double dj = s.d[j], cj = s.c2[j];
-      if (dj == 0.0 && cj == 0.0) continue;             // (uniform; a NaN c2 is carried into the cost)
-      const float *rj = s.jac + j * kIcpRow;
-      acc0 = fma((double)rj[a0], (double)rj[c0], acc0);
-      if (kind1 == kIcpA) acc1 = fma((double)rj[a1], (double)rj[c1], acc1);
-      else if (kind1 == kIcpG) acc1 = fma(dj, (double)rj[a1], acc1);
-      else if (kind1 == kIcpCost) acc1 += cj;
-      else if (kind1 == kIcpCount) acc1 += dj != 0.0 ? 1.0 : 0.0;
-    }
-  }
-  double *out = part + ((size_t)b * gridDim.x + blockIdx.x) * kIcpSlots;
-  out[tid] = acc0;
-  if (kind1 != kIcpNone) out[tid + kIcpThreads] = acc1;
+  const int b = blockIdx.y;
+  icp_tile_body<false>(observed, vertices, faces, dist, face, params, offset, offset_inv, vstart, sbone, swv, sx, NV, F, W, H, ax,
+                       bx, ay, by, fg_max, max_dist, b, (size_t)b, nullptr, part);
 }
 
 __global__ void __launch_bounds__(kIcpSlots)
 pose_icp_reduce_kernel(const double *__restrict__ part, int tiles, double *__restrict__ A, double *__restrict__ g,
                        double *__restrict__ cost, int *__restrict__ count) {
-  const int idx = threadIdx.x, b = blockIdx.x;
-  int a, c;
-  const int kind = icp_entry(idx, a, c);
-  if (kind == kIcpNone) return;
-  const double *in = part + (size_t)b * tiles * kIcpSlots + idx;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int t = 0; t < tiles; t++) acc += in[(size_t)t * kIcpSlots];
-  if (kind == kIcpA) {
-    A[((size_t)b * kLmN + a) * kLmN + c] = acc;
-    A[((size_t)b * kLmN + c) * kLmN + a] = acc;
-  } else if (kind == kIcpG) {
-    g[(size_t)b * kLmN + a] = acc;
-  } else if (kind == kIcpCost) {
-    cost[b] = acc;
-  } else {
-    count[b] = (int)acc;
-  }
+  icp_reduce_body(part, tiles, (int)blockIdx.x, (int)threadIdx.x, A, g, cost, count);
 }
 
 // A crop's state, in doubles: the accepted pose's A [26 x 26] and g [26], the pose itself, params0, its total cost, lambda,
@@ -257,8 +126,6 @@ pose_lm_step_kernel(double *__restrict__ state, const double *__restrict__ A, co
 }  // namespace shr
 
 using namespace shr;
-
-static long long icp_tiles(int W, int H) { return ((long long)W * H + kIcpTilePix - 1) / kIcpTilePix; }
 
 extern "C" long long shr_pose_icp_normal_workspace_bytes(int B, int W, int H) {
   if (B < 0 || W < 0 || H < 0) return -1;

@@ -1971,15 +1971,19 @@ class MeshDataToModel(torch.autograd.Function):
 def _icp_args(observed, vertices, faces, params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, pixel_to_model,
               max_dist, name="parameters"):
     B, H, W, NV, F, p2m, max_dist = _d2m_args(observed, vertices, faces, pixel_to_model, max_dist)
+    _icp_pose_args(params, B, observed.device, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, NV, name)
+    return B, H, W, NV, F, p2m, max_dist
+
+
+def _icp_pose_args(params, B, dev, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, NV, name="parameters"):
     for t, what in ((params, name), (offset, "offset"), (offset_inv, "offset_inv")):
         _check_input(t, what)
-    if tuple(params.shape) != (B, 26) or params.device != observed.device:
+    if tuple(params.shape) != (B, 26) or params.device != dev:
         raise RuntimeError("%s must be [B,26] with observed's B, on its device" % name)
     if tuple(offset.shape) != (17, 4, 4) or tuple(offset_inv.shape) != (17, 4, 4):
         raise RuntimeError("offset and offset_inv must be [17,4,4]")
     if _skin_tables(skin_vertex_start, skin_bone, skin_wv, None) != NV:
         raise RuntimeError("the skin table must have the vertices' NV rows")
-    return B, H, W, NV, F, p2m, max_dist
 
 
 def pose_icp_normal(observed, vertices, faces, dist, face, params, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv,
@@ -2116,6 +2120,135 @@ def pose_icp(observed, params0, faces, offset, offset_inv, skin_vertex_start, sk
                                                _ptr(offset), _ptr(offset_inv), _ptr(skin_vertex_start), _ptr(skin_bone),
                                                _ptr(skin_wv), right, B, NV, F, W, H, *p2m, fg_max, max_dist, _ptr(A), _ptr(g),
                                                _ptr(cost_data), _ptr(count), _ptr(ws_icp), stream), "shr_pose_icp_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
+                                            _ptr(cost0), stream), "shr_pose_lm_step")
+    return params, cost0, cost
+
+
+def _views_args(view, B, dev, name="view"):
+    _check_input(view, name)
+    if view.dim() != 4 or view.shape[0] != B or view.shape[1] < 1 or tuple(view.shape[2:]) != (4, 4) or view.device != dev:
+        raise RuntimeError("%s must be [B,V,4,4] with V >= 1, on the other tensors' device" % name)
+    if B * view.shape[1] > 65535:
+        raise RuntimeError("B * V must be at most 65535")
+    return view.shape[1]
+
+
+def view_vertices(vertices, view):
+    """Model-space vertices [B,NV,4] taken into every view's frame (include/spherehand_hip.h, shr_view_vertices_fwd):
+    view [B,V,4,4] rigid, x_v = R x + t -> [B,V,NV,4] fp32, the 4th float copied."""
+    _check_input(vertices, "vertices")
+    if vertices.dim() != 3 or vertices.shape[2] != 4 or vertices.shape[1] < 1:
+        raise RuntimeError("vertices must be [B,NV,4] with NV >= 1")
+    B, NV = vertices.shape[0], vertices.shape[1]
+    V = _views_args(view, B, vertices.device)
+    with _on(vertices.device):
+        out = torch.empty((B, V, NV, 4), dtype=torch.float32, device=vertices.device)
+        _lib.check(_lib.lib().shr_view_vertices_fwd(_ptr(vertices), _ptr(view), B, V, NV, _ptr(out), _stream()),
+                   "shr_view_vertices_fwd")
+    return out
+
+
+def _icp_views_args(observed, view, name="observed"):
+    _check_input(observed, name)
+    if observed.dim() != 4 or observed.shape[2] < 1 or observed.shape[3] < 1:
+        raise RuntimeError("%s must be [B,V,H,W] with H, W >= 1" % name)
+    B, V, H, W = observed.shape
+    if _views_args(view, B, observed.device) != V:
+        raise RuntimeError("view must be [B,V,4,4] with observed's B and V")
+    return B, V, H, W
+
+
+def pose_icp_normal_views(observed, view_verts, faces, dist, face, view, params, offset, offset_inv, skin_vertex_start, skin_bone,
+                          skin_wv, right_hand=True, pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf")):
+    """pose_icp_normal summed over V views of every sample (include/spherehand_hip.h, shr_pose_icp_normal_views): observed,
+    dist, face [B,V,H,W], view_verts [B,V,NV,4] = view_vertices(vertices of `params`, view), dist and face the maps of
+    mesh_data_to_model on the B V crops, view [B,V,4,4] rigid (NOT checked) -> (A [B,26,26], g [B,26], cost [B] fp64 over
+    all pixels of all views, count [B] int32)."""
+    B, V, H, W = _icp_views_args(observed, view)
+    _check_input(view_verts, "view vertices")
+    if view_verts.dim() != 4 or tuple(view_verts.shape[:2]) != (B, V) or view_verts.shape[3] != 4:
+        raise RuntimeError("view vertices must be [B,V,NV,4]")
+    _, _, _, NV, F, p2m, max_dist = _d2m_args(observed.view(B * V, H, W), view_verts.view(B * V, view_verts.shape[2], 4), faces,
+                                              pixel_to_model, max_dist)
+    _icp_pose_args(params, B, observed.device, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, NV)
+    _check_input(dist, "dist")
+    _check_input(face, "face", torch.int32)
+    for t, name in ((dist, "dist"), (face, "face")):
+        if t.shape != observed.shape or t.device != observed.device:
+            raise RuntimeError("%s must be [B,V,H,W] as observed, on its device" % name)
+    lib = _lib.lib()
+    dev = observed.device
+    with _on(dev):
+        A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+        cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(16, lib.shr_pose_icp_normal_views_workspace_bytes(B, V, W, H)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.shr_pose_icp_normal_views(_ptr(observed), _ptr(view_verts), _ptr(faces), _ptr(dist), _ptr(face), _ptr(view),
+                                                 _ptr(params), _ptr(offset), _ptr(offset_inv), _ptr(skin_vertex_start),
+                                                 _ptr(skin_bone), _ptr(skin_wv), int(bool(right_hand)), B, V, NV, F, W, H, *p2m,
+                                                 float(fg_max), max_dist, _ptr(A), _ptr(g), _ptr(cost), _ptr(count), _ptr(ws),
+                                                 _stream()), "shr_pose_icp_normal_views")
+    return A, g, cost, count
+
+
+def pose_icp_views(observed, view, params0, faces, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, right_hand=True,
+                   pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                   stiffness=None, prior=None):
+    """pose_icp on V depth views of every sample: ONE pose params0 [B,26] in the model frame fitted to observed [B,V,H,W],
+    view [B,V,4,4] rigid taking the model frame to view v's (x_v = R x + t); each iteration is one Levenberg-Marquardt step
+    on the sum of all views' costs -> (params [B,26], cost0 [B], cost [B]).  Each of the iters + 1 evaluations is
+    shr_pose_vertices_fwd (model space) -> shr_view_vertices_fwd -> shr_mesh_d2m_fwd (B V crops) ->
+    shr_pose_icp_normal_views -> shr_pose_lm_step on torch's current stream, into buffers allocated once before the loop;
+    nothing returns to the host: capturable in a graph.  iters = 0 returns params0 and cost = cost0."""
+    _check_input(faces, "faces", torch.int32)
+    B, V, H, W = _icp_views_args(observed, view)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("faces must be [F,3]")
+    dev = observed.device
+    NV, F = _skin_tables(skin_vertex_start, skin_bone, skin_wv, None), faces.shape[0]
+    verts = torch.empty((B, NV, 4), dtype=torch.float32, device=dev)
+    vverts = torch.empty((B, V, NV, 4), dtype=torch.float32, device=dev)
+    _, _, _, _, _, p2m, max_dist = _d2m_args(observed.view(B * V, H, W), vverts.view(B * V, NV, 4), faces, pixel_to_model, max_dist)
+    _icp_pose_args(params0, B, dev, offset, offset_inv, skin_vertex_start, skin_bone, skin_wv, NV, "start parameters")
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    state, trial = pose_lm_begin(params0, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        dist, face = f32(B, V, H, W), torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        params, cost0, cost = f32(B, 26), f32(B), f32(B)
+        ws_d2m = torch.empty((max(16, lib.shr_mesh_d2m_workspace_bytes(B * V, F)),), dtype=torch.uint8, device=dev)
+        ws_icp = torch.empty((max(16, lib.shr_pose_icp_normal_views_workspace_bytes(B, V, W, H)),), dtype=torch.uint8, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_vertices_fwd(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), NV, _ptr(skin_vertex_start),
+                                                 _ptr(skin_bone), _ptr(skin_wv), right, 0, 0.0, 0.0, 1.0, 1.0, None,
+                                                 _ptr(verts), None, stream), "shr_pose_vertices_fwd")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(verts), _ptr(view), B, V, NV, _ptr(vverts), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_mesh_d2m_fwd(_ptr(observed), _ptr(vverts), _ptr(faces), B * V, NV, F, W, H, *p2m, fg_max, max_dist,
+                                            _ptr(dist), _ptr(face), _ptr(ws_d2m), stream), "shr_mesh_d2m_fwd")
+            _lib.check(lib.shr_pose_icp_normal_views(_ptr(observed), _ptr(vverts), _ptr(faces), _ptr(dist), _ptr(face), _ptr(view),
+                                                     _ptr(trial), _ptr(offset), _ptr(offset_inv), _ptr(skin_vertex_start),
+                                                     _ptr(skin_bone), _ptr(skin_wv), right, B, V, NV, F, W, H, *p2m, fg_max,
+                                                     max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), _ptr(ws_icp),
+                                                     stream), "shr_pose_icp_normal_views")
             solve = int(it < iters)
             _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
                                             _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),

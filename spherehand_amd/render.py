@@ -18,6 +18,7 @@ signatures and return values), running on the hand-written HIP kernels.
     MeshVertices             bone transforms or pose -> the mesh's vertices, differentiable: the mesh terms' way to the pose
     KeypointPoseSolver       the 41 keypoints -> the pose, by Levenberg-Marquardt from a start pose: the way INTO the mesh path
     MeshPoseFitter           the pose fitted to an observed depth image: Gauss-Newton ICP on the mesh, from such a start
+    MultiViewMeshPoseFitter  the same on several depth views of every sample: one pose, one rigid transform per view
 """
 import numpy as np
 import torch
@@ -786,6 +787,56 @@ class MeshPoseFitter(nn.Module):
         return ops.pose_icp_normal(observed, verts, self.faces_i32, dist, face, params, self.fk.offset, self.fk.offset_inv,
                                    lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, self.right_hand, self.pixel_to_model,
                                    self.fg_max, self.max_dist)
+
+
+class MultiViewMeshPoseFitter(MeshPoseFitter):
+    """MeshPoseFitter on several depth views of every sample: ONE pose in the model frame fitted to V observed depth
+    images, each iteration one Levenberg-Marquardt step on the sum of all views' point-to-mesh costs (ops.pose_icp_views;
+    include/spherehand_hip.h, shr_pose_icp_normal_views).  view [B,V,4,4] is rigid and maps the model frame to view v's
+    frame, x_v = R x + t; its rotation is NOT checked to be orthonormal.  All views share width, height, pixel_to_model,
+    fg_max and max_dist; a missing camera is an all-background image and adds nothing.
+        solve(observed[B,V,H,W], view[B,V,4,4], params0[B,26], prior=None) -> (params, cost0, cost)
+        normal_equations(observed, view, params) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32)
+        views_from_cameras(camera_poses, inv_camera_poses, ref=0) -> view [B,V,4,4]
+    A REFINEMENT from a start pose, as MeshPoseFitter: the intended start is KeypointPoseSolver's pose, or the pose of the
+    previous frame.  There is NO autograd through the solve.  What further views buy -- the fingers one view hides, and the
+    bone origins a single view cannot move -- is measured in DESIGN.md 4.4o; two views can still end in a wrong basin."""
+
+    def _observed(self, observed):
+        if observed.dim() != 4 or tuple(observed.shape[2:]) != (self.height, self.width):
+            raise RuntimeError("MultiViewMeshPoseFitter takes observed [B,V,%d,%d]" % (self.height, self.width))
+        return observed.detach().contiguous().float()
+
+    @staticmethod
+    def views_from_cameras(camera_poses, inv_camera_poses, ref=0):
+        """camera_poses, inv_camera_poses [B,V,4,4] as MutualTransformation takes them -> view [B,V,4,4] =
+        inv_camera_poses[:, v] @ camera_poses[:, ref], its (ref, v) entry: the pose then lives in camera ref's frame.  Plain
+        torch, any device; a helper, not a hot path."""
+        if camera_poses.dim() != 4 or camera_poses.shape != inv_camera_poses.shape or tuple(camera_poses.shape[2:]) != (4, 4):
+            raise RuntimeError("camera_poses and inv_camera_poses must be [B,V,4,4]")
+        return torch.matmul(inv_camera_poses, camera_poses[:, ref].unsqueeze(1)).contiguous()
+
+    @torch.no_grad()
+    def solve(self, observed, view, params0, prior=None):
+        lbs = self.vertices.lbs
+        return ops.pose_icp_views(self._observed(observed), view.detach().contiguous().float(),
+                                  params0.detach().contiguous().float(), self.faces_i32, self.fk.offset, self.fk.offset_inv,
+                                  lbs.skin_vertex_start, lbs.skin_bone, lbs.skin_wv, self.right_hand, self.pixel_to_model,
+                                  self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                  None if prior is None else prior.detach().contiguous().float())
+
+    @torch.no_grad()
+    def normal_equations(self, observed, view, params):
+        lbs = self.vertices.lbs
+        observed, params = self._observed(observed), params.detach().contiguous().float()
+        view = view.detach().contiguous().float()
+        B, V, H, W = observed.shape
+        vverts = ops.view_vertices(self.vertices.pose_vertices(self.fk, params), view)
+        dist, face = ops.mesh_data_to_model(observed.view(B * V, H, W), vverts.view(B * V, vverts.shape[2], 4), self.faces_i32,
+                                            self.pixel_to_model, self.fg_max, self.max_dist)
+        return ops.pose_icp_normal_views(observed, vverts, self.faces_i32, dist.view(B, V, H, W), face.view(B, V, H, W), view,
+                                         params, self.fk.offset, self.fk.offset_inv, lbs.skin_vertex_start, lbs.skin_bone,
+                                         lbs.skin_wv, self.right_hand, self.pixel_to_model, self.fg_max, self.max_dist)
 
 
 class DepthRender(nn.Module):
