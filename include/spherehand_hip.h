@@ -1088,6 +1088,71 @@ int shr_pose_icp_normal_views(const float *observed, const float *view_vertices,
                               float bx, float ay, float by, float fg_max, float max_dist, double *A, double *g, double *cost,
                               int32_t *count, void *workspace, void *stream);
 
+/* Pose from observed depth points through the SPHERE model: Gauss-Newton / Levenberg-Marquardt ICP on the spheres -------
+ * Inverts HandTransformationMat.forward (mesh/kinematicsTransformation.py:157-177) followed by the key-point skinning of
+ * HandBallPrimitiveRender (mesh/render.py:65-88), against the observation of DataToModelLoss (mesh/render.py:93-142), whose
+ * distance min_j | |p - c_j| - r_j | this is.  The reference has no counterpart.  One evaluation of a fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_normal -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.  The search has J <= 64 candidates per point, so
+ * search, residual and row are ONE entry: there are no saved maps to hand in.
+ *   shr_sphere_icp_normal   the normal equations of 1/2 sum d^2, d = |p - c_owner| - r_owner, over the rows of all views
+ *       with respect to the 26 pose parameters.  observed[B,V,H,W] fp32, crop b V + v being view v of sample b;
+ *       view_centres[B,V,J,4]: shr_view_vertices_fwd of shr_pose_keypoints_jacobian's keypoints under view (the 4th float is
+ *       not read; they MUST be those of the pose jac belongs to, which is NOT checked); radii[J]; view[B,V,4,4] as for
+ *       shr_pose_icp_normal_views: only its top-left 3 x 3 is read, as a rotation, and it is NOT checked to be orthonormal;
+ *       jac[B,3J,26]: shr_pose_keypoints_jacobian's.  ax, bx, ay, by, fg_max, max_dist: shr_mesh_d2m_fwd's.
+ *       Data points.  shr_mesh_d2m_fwd's: pixel (row i, column j) of a view is a DATA POINT iff observed < fg_max (a NaN is
+ *       none); p = (ax (float)j + bx, ay (float)i + by, observed), one rounding per written operation.
+ *       Owner.  All fp32, one correctly rounded operation per written operator, nothing contracted.  best = +inf,
+ *       owner = -1; for j ascending with c_j = view_centres[b,v,j,0..2], r_j = radii[j]:
+ *         e = p - c_j;  n2 = (e.x e.x + e.y e.y) + e.z e.z;  n = sqrt(n2) correctly rounded;  s_j = |n - r_j|
+ *       sphere j is taken iff s_j < best: a NaN s is never taken (nor is +inf), equal distances keep the smallest j -- the
+ *       reference's min_j | |p - c_j| - r_j | with the first index on ties.  The kernel prunes nothing: every data point meets
+ *       every sphere.
+ *       -> dist[B,V,H,W] fp32 (or NULL) = fminf(s_owner, max_dist) at a data point with an owner, 0 at every other pixel;
+ *       owner[B,V,H,W] int32 (or NULL), -1 where dist has no owner.  Every element of a map that is given is written.
+ *       Row.  A data point gives a row iff it has an owner, s_owner < max_dist and, recomputed in fp64 from the fp32 p, c, r
+ *       of the owner, n = sqrt((e.x e.x + e.y e.y) + e.z e.z) is finite and > 0 (a point exactly on a centre has no
+ *       direction: no row).  Then d = n - r, signed: negative inside the sphere; u_v = e / n; the direction is taken back
+ *       to the model frame in fp64 with shr_pose_icp_normal_views' association, u_j = (R0j u_v0 + R1j u_v1) + R2j u_v2
+ *       (u = R^T u_v).  The row is d d / d params = -u^T jac[3 owner .. 3 owner + 2, :], fp64 products of the fp32 Jacobian.
+ *       A point with d = 0, exactly on the surface, still gives a row: unlike on a triangle its direction is defined.
+ *       -> moments[B,J,12] fp64 (or NULL), for the rows owned by sphere j: S = sum u u^T as (xx, xy, xz, yy, yz, zz),
+ *       h = sum d u (3), sum d^2, the number of rows (as a double), and one spare 0.
+ *       -> A[B,26,26] fp64 = sum row^T row, formed as sum_j Jc_j^T S_j Jc_j with Jc_j = jac[3j .. 3j + 2, :], all 26
+ *       columns of every sphere (no assumption about which parameters move a sphere); the lower triangle is computed and
+ *       written to both triangles: bit-symmetric.  g[B,26] fp64 = sum d row = -sum_j Jc_j^T h_j, the gradient of
+ *       1/2 sum d^2.  cost[B] fp64 = sum over ALL pixels of all views of (double)dist^2 of the fp32 distance above (a
+ *       saturated point counts max_dist^2: a truncated quadratic).  count[B] int32: the rows.  A sample without a row gets
+ *       A = 0, g = 0, count = 0.
+ *       Summation order (the contract): fixed-order fp64 chains, no atomics.  The pixels of a view in row-major order form
+ *       tiles of 1024; every moment of every sphere is one chain from 0 over its rows of the tile in ascending pixel order;
+ *       the tiles' values are added from 0, tiles ascending inside a view, views ascending.  The cost runs in the same
+ *       order over the pixels with dist != 0, then over the tiles, as a COMPENSATED chain: a pair (hi, lo) from (0, 0),
+ *       each term x added by t = hi + x, b = t - hi, lo += (hi - (t - b)) + (x - b), hi = t (a tile's lo is added to lo);
+ *       cost = hi + lo, within an ulp or two of the exact sum of the squares.
+ *       A entry (a, c), a >= c, is a chain from 0 over the spheres in ascending order
+ *       -- a sphere without a row is skipped -- of (Jc[0,a] t0 + Jc[1,a] t1) + Jc[2,a] t2, t_k = (S_k0 Jc[0,c] + S_k1 Jc[1,c])
+ *       + S_k2 Jc[2,c]; g_a is minus the chain of (Jc[0,a] h0 + Jc[1,a] h1) + Jc[2,a] h2.  Bitwise reproducible; a sample's
+ *       result does not depend on the batch it is in or on the launch shape; no host synchronisation.
+ *       workspace: 16-byte aligned, shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H) bytes (-1 on a negative size):
+ *       8 (12 J + 4) bytes per (sample, view, tile), written by the call before it is read.
+ *   Argument rules, checked before the B == 0 no-op: 1 <= H, W; 1 <= V; 1 <= J; B >= 0; max_dist >= 0, +inf allowed
+ *   (SHR_EINVAL otherwise); H, W above 2048, J above 64, B or B V above 65535: SHR_ETOOLARGE.  B == 0 is a no-op.  NULLs
+ *   other than moments, dist and owner, and misaligned pointers (4 bytes; A, g, cost, moments 8; view_centres, workspace 16):
+ *   SHR_EINVAL. */
+long long shr_sphere_icp_normal_workspace_bytes(int B, int V, int J, int W, int H);
+int shr_sphere_icp_normal(const float *observed      /* [B,V,H,W] */,
+                          const float *view_centres  /* [B,V,J,4]: shr_view_vertices_fwd of the keypoints */,
+                          const float *radii         /* [J] */,
+                          const float *view          /* [B,V,4,4] */,
+                          const float *jac           /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                          int B, int V, int J, int W, int H, float ax, float bx, float ay, float by,
+                          float fg_max, float max_dist,
+                          double *A, double *g, double *cost, int32_t *count,
+                          double *moments /* [B,J,12] or NULL */, float *dist /* [B,V,H,W] or NULL */,
+                          int32_t *owner /* [B,V,H,W] or NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

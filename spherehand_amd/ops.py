@@ -2256,6 +2256,104 @@ def pose_icp_views(observed, view, params0, faces, offset, offset_inv, skin_vert
     return params, cost0, cost
 
 
+def _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, radii, pixel_to_model, max_dist, name="parameters"):
+    B, V, H, W = _icp_views_args(observed, view)
+    Bp, J = _ik_tables(params, offset, offset_inv, bone, wv, name)
+    _check_input(radii, "radii")
+    if tuple(radii.shape) != (J,):
+        raise RuntimeError("radii must be [J], one per key-point")
+    if Bp != B or any(t.device != observed.device for t in (params, offset, offset_inv, bone, wv, radii)):
+        raise RuntimeError("%s must be [B,26] with observed's B, every tensor on observed's device" % name)
+    try:
+        p2m = tuple(float(t) for t in pixel_to_model)
+        ax, bx, ay, by = p2m
+    except (TypeError, ValueError):
+        raise RuntimeError("pixel_to_model must be four numbers (ax, bx, ay, by): x = ax j + bx, y = ay i + by")
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise RuntimeError("max_dist must be >= 0 (inf: no saturation), not %r" % (max_dist,))
+    return B, V, H, W, J, p2m, max_dist
+
+
+def sphere_icp_normal(observed, view, params, offset, offset_inv, bone, wv, radii, right_hand=True,
+                      pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), want_maps=False):
+    """The Gauss-Newton normal equations of the sphere model against observed depth (include/spherehand_hip.h,
+    shr_sphere_icp_normal): observed [B,V,H,W], view [B,V,4,4] rigid (NOT checked), params [B,26], the key-point tables of
+    pose_keypoints_jacobian and radii [J] -> (A [B,26,26], g [B,26], cost [B] fp64 over all pixels of all views, count [B]
+    int32, moments [B,J,12] fp64); with want_maps also (dist [B,V,H,W] fp32, owner [B,V,H,W] int32).  Three launches:
+    shr_pose_keypoints_jacobian -> shr_view_vertices_fwd -> shr_sphere_icp_normal; every data point meets every sphere, so
+    there is no search to run first."""
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, radii, pixel_to_model,
+                                                    max_dist)
+    lib = _lib.lib()
+    dev = observed.device
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
+        _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
+        A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+        cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
+        dist = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
+        owner = torch.empty((B, V, H, W), dtype=torch.int32, device=dev) if want_maps else None
+        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                             *p2m, float(fg_max), max_dist, _ptr(A), _ptr(g), _ptr(cost), _ptr(count),
+                                             _ptr(moments), _ptr(dist), _ptr(owner), _ptr(ws), _stream()),
+                   "shr_sphere_icp_normal")
+    return (A, g, cost, count, moments) + ((dist, owner) if want_maps else ())
+
+
+def sphere_icp(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
+               pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+               stiffness=None, prior=None):
+    """Fit the pose to V observed depth views through the SPHERE model: `iters` Levenberg-Marquardt iterations on
+    sum dist^2 + sum_i stiffness_i (p_i - prior_i)^2 from params0 [B,26], dist = min_j | |p - c_j| - r_j | saturated at
+    max_dist, over all views -> (params [B,26], cost0 [B], cost [B]).  observed [B,V,H,W], view [B,V,4,4] rigid taking the
+    model frame to view v's.  Each of the iters + 1 evaluations is shr_pose_keypoints_jacobian -> shr_view_vertices_fwd
+    (NV := J) -> shr_sphere_icp_normal -> shr_pose_lm_step on torch's current stream, into buffers allocated once before
+    the loop; nothing returns to the host: capturable in a graph.  iters = 0 returns params0 and cost = cost0."""
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
+                                                    max_dist, "start parameters")
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    dev = observed.device
+    state, trial = pose_lm_begin(params0, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        params, cost0, cost = f32(B, 26), f32(B), f32(B)
+        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
+                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
+                                            _ptr(cost0), stream), "shr_pose_lm_step")
+    return params, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

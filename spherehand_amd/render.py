@@ -839,6 +839,75 @@ class MultiViewMeshPoseFitter(MeshPoseFitter):
                                          lbs.skin_wv, self.right_hand, self.pixel_to_model, self.fg_max, self.max_dist)
 
 
+class SpherePoseFitter(nn.Module):
+    """The pose fitted to observed depth through the SPHERE model, the 41 spheres HandBallPrimitiveRender hangs on the
+    pose: `iters` Gauss-Newton / Levenberg-Marquardt iterations on sum dist^2 + sum_i stiffness_i (p_i - prior_i)^2, dist
+    being DataToModelLoss's distance min_j | |p - c_j| - r_j | of every observed point, saturated at max_dist, summed over
+    V views (ops.sphere_icp; include/spherehand_hip.h, shr_sphere_icp_normal and shr_pose_lm_step, has the equations and
+    the iteration).  A point meets 41 spheres where the mesh fit's search meets 3 382 faces: search and row are one launch.
+        solve(observed, params0, view=None, prior=None) -> (params, cost0, cost)
+        normal_equations(observed, params, view=None) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32,
+                                                          moments [B,41,12] fp64: per sphere sum u u^T, sum d u, sum d^2, rows)
+        views_from_cameras(camera_poses, inv_camera_poses, ref=0) -> view [B,V,4,4]   (MultiViewMeshPoseFitter's)
+    observed is [B,V,H,W] with view [B,V,4,4] rigid (x_v = R x + t; its rotation is NOT checked to be orthonormal), or
+    [B,H,W] with view=None: one view, the identity.  A REFINEMENT from a start pose: the intended start is
+    KeypointPoseSolver's pose from the network's keypoints, or the previous frame's pose; it can end in a wrong basin.
+    There is NO autograd through the solve.  stiffness: [26], each >= 0 (a buffer); prior: [B,26], default the start pose.
+    The observation must be one the SPHERE model explains: the shipped radii are a fat proxy of the shipped mesh, and on a
+    mesh-rendered observation this fit moves the pose away from the mesh's (DESIGN.md 4.4p has the figures).  Handing its
+    result to MeshPoseFitter on the same observation is not supported."""
+
+    def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
+                 fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0):
+        super().__init__()
+        from .hand_model import sphere_model
+        from .kinematicsTransformation import HandTransformationMat
+        bones = mesh['bones'] if isinstance(mesh, dict) else mesh
+        self.fk = HandTransformationMat([np.asarray(b['offset_matrix']).astype(np.float32) for b in bones])
+        wv, radii, bone = sphere_model(bones)
+        self.register_buffer('kp_bone', torch.from_numpy(bone.astype(np.int32)))
+        self.register_buffer('kp_wv', torch.from_numpy(np.ascontiguousarray(wv, np.float32)))
+        self.register_buffer('radii', torch.from_numpy(np.ascontiguousarray(radii, np.float32)))
+        self.register_buffer('stiffness', None if stiffness is None else
+                             torch.as_tensor(np.asarray(stiffness, np.float32)).reshape(26).clone())
+        self.width, self.height = int(width), int(height)
+        p2m = MeshDataToModelLoss.reference_grid(width, height) if pixel_to_model is None else pixel_to_model
+        self.pixel_to_model = tuple(float(t) for t in p2m)
+        self.right_hand = bool(right_hand)
+        self.iters = int(iters)
+        self.lambda0 = float(lambda0)
+        self.fg_max = float(fg_max)
+        self.max_dist = float(max_dist)
+        self.num_spheres = len(bone)
+
+    views_from_cameras = staticmethod(MultiViewMeshPoseFitter.views_from_cameras)
+
+    def _observed(self, observed, view):
+        if view is None:
+            if observed.dim() != 3:
+                raise RuntimeError("SpherePoseFitter takes observed [B,%d,%d] without a view" % (self.height, self.width))
+            observed = observed.unsqueeze(1)
+            view = torch.eye(4, dtype=torch.float32, device=observed.device).expand(observed.shape[0], 1, 4, 4)
+        if observed.dim() != 4 or tuple(observed.shape[2:]) != (self.height, self.width):
+            raise RuntimeError("SpherePoseFitter takes observed [B,V,%d,%d] with view [B,V,4,4]" % (self.height, self.width))
+        return observed.detach().contiguous().float(), view.detach().contiguous().float()
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None):
+        observed, view = self._observed(observed, view)
+        return ops.sphere_icp(observed, view, params0.detach().contiguous().float(), self.fk.offset, self.fk.offset_inv,
+                              self.kp_bone, self.kp_wv, self.radii, self.right_hand, self.pixel_to_model, self.fg_max,
+                              self.max_dist, self.iters, self.lambda0, self.stiffness,
+                              None if prior is None else prior.detach().contiguous().float())
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None):
+        observed, view = self._observed(observed, view)
+        return ops.sphere_icp_normal(observed, view, params.detach().contiguous().float(), self.fk.offset, self.fk.offset_inv,
+                                     self.kp_bone, self.kp_wv, self.radii, self.right_hand, self.pixel_to_model, self.fg_max,
+                                     self.max_dist)
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster

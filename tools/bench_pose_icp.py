@@ -32,6 +32,7 @@ def main():
     lib = _lib.lib()
     p = lambda t: t.data_ptr()  # noqa: E731
     stream = torch.cuda.Stream()
+    summary = {}                                                    # (B, S) -> the launches' medians, us
     with torch.cuda.stream(stream):
         for B, S in configs:
             stiffness = np.array([1.0] * 3 + [0.0] * 3 + [1.0] * 20, np.float32)
@@ -99,6 +100,8 @@ def main():
             print("pose icp B=%d %dx%d: vertices %.2f us, search %.2f us, normal %.2f us, step %.2f us; one iteration %.2f us, "
                   "the search %.1f %% of it" % (B, S, S, us["vertices"], us["search"], us["normal"], us["step"], total,
                                                  100.0 * us["search"] / total), flush=True)
+            summary[(B, S)] = us
+    return summary
 
 
 if __name__ == "__main__":
