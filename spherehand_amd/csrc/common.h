@@ -152,32 +152,25 @@ __device__ __forceinline__ float wave_min4_transposed(float a0, float a1, float 
 }
 
 // Correctly rounded fp32 square root for x in [0.01, 1e12] (sphere_zbuf.h documents the range and the
-// exhaustive test).  s = v_sqrt_f32(x) is within one ulp u of the root, so the result is s - u, s or s + u, and
-// which one is read off ONE residual r = fma(-s, s, x) (exact whenever it matters: |x - s^2| < 2^24 granules of
-// s^2's last place there):  sqrt(x) > s + u/2  <=>  x - s^2 > s u (+ u^2/4, below a granule)  <=>  r > t,
-// sqrt(x) < s - u/2  <=>  r <= -t,  with t = s * u formed on the bit pattern (exponent field of s added to itself).
-// Eight VALU instructions where the two-neighbour form (two increments, two residuals, two selects) takes nine;
-// the carry forms of the integer add / subtract take the comparison's result directly.
-// NOT covered by the argument above: s an exact power of two, 2^k.  The ulp BELOW s is u / 2 there, so for
-// x = prev(4^k) (23 inputs in the range) an estimate of 2^k would leave r = -4^k 2^-24 > -t and 2^k would be
-// returned where the correctly rounded root is prev(2^k).  gfx950's v_sqrt_f32 returns prev(2^k) for those inputs
-// (it never rounds the estimate UP across a binade boundary), which is what
-// tests/test_sphere_raster_gpu.py::test_sqrt_rn_exhaustive establishes on the hardware, every fp32 value of the
-// range, in the default GPU selection: the function is exact on gfx950, by measurement at those 23 points and by
-// the argument everywhere else.  Another target needs the test re-run (or t halved for the lower test when s's
-// mantissa is zero).  The s_nop counts below are gfx950's VALU-writes-vcc -> VALU-reads-vcc-as-carry wait states.
+// exhaustive test).  One Newton step on the reciprocal-root estimate, the last operation a single FMA:
+//   y = v_rsq_f32(x) (<= 1 ulp),  s = x y,  h = y / 2,  r = fma(-s, s, x),  result = fma(r, h, s).
+// s is within ~1.5 ulp of the root and r = x - s^2 is exact (it fits 24 bits at that distance), so r h = sqrt(x) - s up
+// to the relative error of h (2^-23) and the step's second-order term: the FMA rounds sqrt(x) + d ONCE, |d| <~ 2^-22 ulp.
+// That is the correctly rounded root unless sqrt(x) lies within |d| of the midpoint of two neighbours; the closest an
+// fp32 argument's root comes to one is ~2^-27 ulp (x = m (m + 1) in units of the root's ulp squared), so the bound
+// alone does not prove exactness -- tests/test_sphere_raster_gpu.py::test_sqrt_rn_exhaustive does, on the hardware, for
+// every fp32 value of the range, in the default GPU selection: the function is exact on gfx950 by measurement (its
+// v_rsq_f32 is part of the result).  Another target needs the test re-run.
+// Five VALU instructions, one of them quarter-rate, no vcc and no wait states; the form it replaces (v_sqrt_f32, one
+// residual, two compares with carry-in increments) took eight and four wait states.  The plain-arithmetic variants
+// measured on the way: s + r * h (two roundings) is exact on the range as well, one instruction more; v_sqrt_f32's
+// estimate corrected with h = v_rcp_f32(s) / 2 fails at the 23 inputs prev(4^k).
+// (An argument outside the range -- a lane that does not hit: zero, negative -- may give NaN; callers never store it.)
 __device__ __forceinline__ float sqrt_rn(float x) {
-  const float s = __builtin_amdgcn_sqrtf(x);
+  const float y = __builtin_amdgcn_rsqf(x);
+  const float s = x * y, h = 0.5f * y;
   const float r = __builtin_fmaf(-s, s, x);
-  const uint32_t sb = __float_as_uint(s);
-  const float t = __uint_as_float(sb + (sb & 0x7f800000u) - 0x4B000000u);   // s * 2^(E - 23), E = s's exponent
-  uint32_t out;
-  // (s_nop 1: a VALU write of vcc needs two wait states before a VALU reads it as a carry / mask on gfx950, and
-  // the hazard recognizer does not look inside an asm statement)
-  asm("v_cmp_gt_f32 vcc, %1, %2\n\ts_nop 1\n\tv_addc_co_u32 %0, vcc, 0, %3, vcc\n\t"
-      "v_cmp_le_f32 vcc, %1, -%2\n\ts_nop 1\n\tv_subbrev_co_u32 %0, vcc, 0, %0, vcc"
-      : "=&v"(out) : "v"(r), "v"(t), "v"(sb) : "vcc");
-  return __uint_as_float(out);
+  return __builtin_fmaf(r, h, s);
 }
 
 int d2m_set_waves(int waves);        // data_to_model.hip: launch-shape hooks behind SHR_TUNE_D2M_WAVES /

@@ -133,8 +133,23 @@ __device__ __forceinline__ uint32_t depth_key(float d) {
 __device__ __forceinline__ float key_depth(uint32_t k) {
   // (top bit set: the float was non-negative, only the sign flips back; clear: every bit does -- an arithmetic shift and one
   // three-input bit operation.  The select form, k ^ (k & 0x80000000 ? 0x80000000 : ~0), compiled to a 64-bit compare +
-  // select + xor per cell on the u64 z-buffers; same bits, and no measurable difference: round 6, tools/ab_variant.py)
-  return __uint_as_float(k ^ ((uint32_t)(~((int32_t)k >> 31)) | 0x80000000u));
+  // select + xor per cell on the u64 z-buffers; same bits, and no measurable difference: round 6, tools/ab_variant.py.
+  // The sign mask as an opaque value: the compiler otherwise rewrites this expression, too, as compare + select + xor.)
+  int32_t m = (int32_t)k >> 31;
+  asm("" : "+v"(m));
+  return __uint_as_float(k ^ ((uint32_t)~m | 0x80000000u));
+}
+// The depth key of a 64-bit cell, as an opaque 32-bit value: decoded from the 64-bit expression, key_depth() became a
+// 64-bit signed compare, a select and an xor per cell; from the high register alone it is the shift and the bit operation.
+__device__ __forceinline__ uint32_t cell_key(unsigned long long k) {
+  uint32_t h = (uint32_t)(k >> 32);
+  asm("" : "+v"(h));
+  return h;
+}
+// The low bytes of four cells' owner words (a sphere index, or 0xFFFFFFFF on a background cell) as one word, first cell
+// lowest: two byte permutes (selector 0x0c: a zero byte) and an or, where shifts and masks took nine instructions.
+__device__ __forceinline__ uint32_t pack_owner_bytes(uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) {
+  return __builtin_amdgcn_perm(o1, o0, 0x0c0c0400u) | __builtin_amdgcn_perm(o3, o2, 0x04000c0cu);
 }
 // 64-bit cells (depth key << 32 | owner): ds_min_u64 keeps the nearest hit and, among equal depths, the lowest sphere
 // index; the background cell is (key(100) << 32 | 0xFFFFFFFF).  One case needs a second look when a cell is decoded:
@@ -161,9 +176,8 @@ __device__ __forceinline__ uint32_t tie_owner(const float4 *s_sph, uint32_t j, f
 }
 
 // Correctly rounded sqrt for a normal, positive, finite fp32 argument (here
-// q > 0.01): the hardware estimate (v_sqrt_f32, <= 1 ulp) corrected by the exact
-// residuals of its two neighbours -- the same correction hipcc's sqrtf() applies,
-// without its denormal-scaling prologue.  Checked against sqrtf() on every fp32
+// q > 0.01): sqrt_rn() of common.h -- one Newton step on the hardware's reciprocal-root
+// estimate, closed by a single FMA.  Checked against sqrtf() on every fp32
 // value in [0.01, 1e12] (tests/test_sphere_raster_gpu.py::test_sqrt_rn_exhaustive).
 
 __device__ __forceinline__ bool sphere_is_tame(const float4 s) {
@@ -474,7 +488,11 @@ __device__ __forceinline__ void walk_slice_packed(const WaveList &w, int J, int 
       for (; c < c_end; c += 2, yg += 2.f * dyg, cell += 2 * dcell)
         body(j, s, cell, cell + dcell, dx, cav, yg, yg + dyg, packed, packed, c + 1 < c_end, std::false_type());
     } else {
-      const float ylim = packed ? readlane_f(yliml, j) : -3.0e38f;
+      // "row <= last row" against the sphere's own limit, a scalar; a lane outside the packing fails it from a row
+      // coordinate of +huge (its column term is -1 as well: no hit whatever the body forms from it) -- one select
+      // where a per-lane limit took a branch around the broadcast
+      const float ylim = readlane_f(yliml, j);
+      yg = packed ? yg : 3.0e38f;
       for (; c < c_end; c += 2, yg += 2.f * dyg, cell += 2 * dcell) {
         const float ygb = yg + dyg;
         body(j, s, cell, cell + dcell, dx, cav, yg, ygb, yg <= ylim, ygb <= ylim, c + 1 < c_end, std::true_type());
@@ -770,9 +788,8 @@ __device__ __forceinline__ void late_store(float4 *p, const float4 v) {
   v4u_t t = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
   asm_store16<SHR_LATE_STORE_MODE / 10>(p, t);
 }
-__device__ __forceinline__ void late_store(uchar4 *p, const uchar4 v) {
-  const uint32_t t = (uint32_t)v.x | ((uint32_t)v.y << 8) | ((uint32_t)v.z << 16) | ((uint32_t)v.w << 24);
-  asm_store4<SHR_LATE_STORE_MODE % 10>(p, t);
+__device__ __forceinline__ void late_store(uchar4 *p, const uint32_t packed) {   // (four owner bytes, first pixel lowest)
+  asm_store4<SHR_LATE_STORE_MODE % 10>(p, packed);
 }
 
 template <bool OWNER> struct KeyOf { using type = uint32_t; };
@@ -1171,38 +1188,48 @@ sphere_zbuf_fwd_kernel(const float4 *__restrict__ spheres, int N, int J_, int H_
     const Key *zrow = zbuf - (p0 - r0) * pitch - cu0;   // cell of region pixel (v, x) = zrow[v * pitch + x]
     const unsigned box_h = pe > p0 ? (unsigned)(pe - p0) : 0u;
     if (VEC4) {
-      for (int cb = out_lo + (wave_s << 6); cb < out_hi; cb += nwaves << 6) {   // (a scalar loop: wave-wide stores of whole units)
-        const int c = cb + lane;
-        if (c >= out_hi) continue;
-        int v, x;
-        if (POW2 || w4_shift >= 0) { v = c >> w4_shift; x = (c & (w4 - 1)) << 2; }
-        else { v = c / w4; x = (c - v * w4) << 2; }
-        float4 o = bgd;
-        uchar4 a = bga;
-        if (!BOX || ((unsigned)(v + r0 - p0) < box_h && (unsigned)(x - cu0) < (unsigned)bw)) {
-          const Key *cell = zrow + v * pitch + x;
-          if (OWNER) {
-            const ulonglong2 k01 = reinterpret_cast<const ulonglong2 *>(cell)[0];
-            const ulonglong2 k23 = reinterpret_cast<const ulonglong2 *>(cell)[1];
-            o = make_float4(key_depth((uint32_t)(k01.x >> 32)), key_depth((uint32_t)(k01.y >> 32)),
-                            key_depth((uint32_t)(k23.x >> 32)), key_depth((uint32_t)(k23.y >> 32)));
-            a = make_uchar4((uint8_t)k01.x, (uint8_t)k01.y, (uint8_t)k23.x, (uint8_t)k23.y);
-            if (may_tie && (is_background_tie(k01.x) || is_background_tie(k01.y) || is_background_tie(k23.x) ||
-                            is_background_tie(k23.y))) {   // (practically never)
-              const float yg = axis_coord_t<POW2>(ay, v + r0);
-              if (is_background_tie(k01.x)) a.x = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg);
-              if (is_background_tie(k01.y)) a.y = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg);
-              if (is_background_tie(k23.x)) a.z = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg);
-              if (is_background_tie(k23.y)) a.w = (uint8_t)tie_owner(hdr.s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg);
+      // TIE: a crop with a sphere centred behind the background looks at every cell for a hit at exactly 100.0; any
+      // other crop -- a wave-uniform branch around the loop -- runs a body that does not contain the test at all.
+      auto stream_units = [&](auto tie_tag) {
+        constexpr bool TIE = decltype(tie_tag)::value;
+        for (int cb = out_lo + (wave_s << 6); cb < out_hi; cb += nwaves << 6) {   // (a scalar loop: wave-wide stores of whole units)
+          const int c = cb + lane;
+          if (c >= out_hi) continue;
+          int v, x;
+          if (POW2 || w4_shift >= 0) { v = c >> w4_shift; x = (c & (w4 - 1)) << 2; }
+          else { v = c / w4; x = (c - v * w4) << 2; }
+          float4 o = bgd;
+          uint32_t a = 0xFFFFFFFFu;
+          static_assert(SHR_ARGMIN_NONE == 255, "background owner bytes");
+          if (!BOX || ((unsigned)(v + r0 - p0) < box_h && (unsigned)(x - cu0) < (unsigned)bw)) {
+            // (whole region at the image's own pitch, W + kRowPad: v * pitch + x is 4 c plus the rows' padding)
+            const Key *cell = BOX ? zrow + v * pitch + x : zbuf + ((c << 2) + v * kRowPad);
+            if (OWNER) {
+              const ulonglong2 k01 = reinterpret_cast<const ulonglong2 *>(cell)[0];
+              const ulonglong2 k23 = reinterpret_cast<const ulonglong2 *>(cell)[1];
+              o = make_float4(key_depth(cell_key(k01.x)), key_depth(cell_key(k01.y)), key_depth(cell_key(k23.x)),
+                              key_depth(cell_key(k23.y)));
+              a = pack_owner_bytes((uint32_t)k01.x, (uint32_t)k01.y, (uint32_t)k23.x, (uint32_t)k23.y);
+              if (TIE && (is_background_tie(k01.x) || is_background_tie(k01.y) || is_background_tie(k23.x) ||
+                          is_background_tie(k23.y))) {   // (practically never)
+                const float yg = axis_coord_t<POW2>(ay, v + r0);
+                if (is_background_tie(k01.x)) a = (a & ~0xffu) | (tie_owner(hdr.s_sph, (uint32_t)k01.x, axis_coord_t<POW2>(ax, x), yg) & 0xffu);
+                if (is_background_tie(k01.y)) a = (a & ~0xff00u) | ((tie_owner(hdr.s_sph, (uint32_t)k01.y, axis_coord_t<POW2>(ax, x + 1), yg) & 0xffu) << 8);
+                if (is_background_tie(k23.x)) a = (a & ~0xff0000u) | ((tie_owner(hdr.s_sph, (uint32_t)k23.x, axis_coord_t<POW2>(ax, x + 2), yg) & 0xffu) << 16);
+                if (is_background_tie(k23.y)) a = (a & ~0xff000000u) | ((tie_owner(hdr.s_sph, (uint32_t)k23.y, axis_coord_t<POW2>(ax, x + 3), yg) & 0xffu) << 24);
+              }
+            } else {
+              const uint4 k = *reinterpret_cast<const uint4 *>(cell);
+              o = make_float4(key_depth(k.x), key_depth(k.y), key_depth(k.z), key_depth(k.w));
             }
-          } else {
-            const uint4 k = *reinterpret_cast<const uint4 *>(cell);
-            o = make_float4(key_depth(k.x), key_depth(k.y), key_depth(k.z), key_depth(k.w));
           }
+          // (c >= 0: an unsigned index spares the sign extension of the 64-bit address)
+          if (OWNER) late_store(aout4 + (unsigned)c, a);
+          late_store(out4 + (unsigned)c, o);
         }
-        if (OWNER) late_store(aout4 + c, a);
-        late_store(out4 + c, o);
-      }
+      };
+      if (OWNER && may_tie) stream_units(std::true_type());
+      else stream_units(std::false_type());
     } else {
       for (int p = out_lo + tid; p < out_hi; p += nthr) {
         const int v = p / W, u = p - v * W;
@@ -1373,12 +1400,12 @@ sphere_zbuf_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     const int rh = r1 - r0;
     auto put_unit = [&](int u, const v4f g, uint32_t o) {
       const int c = (u << 6) + lane;
-      int v, x;
-      if (POW2 || w4_shift >= 0) { v = c >> w4_shift; x = (c & (w4 - 1)) << 2; }
-      else { v = c / w4; x = (c - v * w4) << 2; }
+      const int v = (POW2 || w4_shift >= 0) ? c >> w4_shift : c / w4;
       if (c < nchunk && (unsigned)(v - r0) < (unsigned)rh) {   // (a unit may straddle the pass's first or last row)
-        *reinterpret_cast<v4f *>(gbuf + (v - r0) * LW + x) = g;
-        *reinterpret_cast<uint32_t *>(obuf + (v - r0) * LW + x) = o;
+        // (v - r0) * LW + x with W = 4 w4 and x = 4 (c - v w4): four times the chunk plus the rows' padding
+        const int cell = (c << 2) + v * kRowPad - r0 * LW;
+        *reinterpret_cast<v4f *>(gbuf + cell) = g;
+        *reinterpret_cast<uint32_t *>(obuf + cell) = o;
       }
     };
     if (VEC4) {
@@ -1799,10 +1826,11 @@ sphere_zbuf_mse_body(const float4 *__restrict__ spheres, int N, int J_, int H_, 
           return;
         }
       }
-      ulonglong2 *cell = reinterpret_cast<ulonglong2 *>(zb + (v + r0) * pitch + x);
+      // (whole region at the image's own pitch: v * pitch + x is 4 c plus the rows' padding, see the forward's stream-out)
+      ulonglong2 *cell = reinterpret_cast<ulonglong2 *>(BOX ? zb + (v + r0) * pitch + x : zbuf + ((c << 2) + v * kRowPad));
       ulonglong2 k01 = cell[0], k23 = cell[1];
-      const float4 d = make_float4(key_depth((uint32_t)(k01.x >> 32)), key_depth((uint32_t)(k01.y >> 32)),
-                                   key_depth((uint32_t)(k23.x >> 32)), key_depth((uint32_t)(k23.y >> 32)));
+      const float4 d = make_float4(key_depth(cell_key(k01.x)), key_depth(cell_key(k01.y)), key_depth(cell_key(k23.x)),
+                                   key_depth(cell_key(k23.y)));
       if (out) stream_store(out4 + c, d);
       if (may_tie && (is_background_tie(k01.x) || is_background_tie(k01.y) || is_background_tie(k23.x) ||
                       is_background_tie(k23.y))) {   // a hit at exactly 100.0 (practically never): who owns it (tie_owner)
