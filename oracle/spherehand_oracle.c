@@ -181,7 +181,9 @@ int oracle_sphere_raster_bwd(const float *spheres, const float *grad_depth, int 
         const float g = gd[(size_t)v * W + u];
         const float dx = xg[u] - sp[4 * bj], dy = yg - sp[4 * bj + 1], r = sp[4 * bj + 3];
         const float g_sq = -g;
-        const float g_q = g_sq / (2.0f * bsq);
+        /* torch.clamp(min) passes no gradient for a NaN argument (its mask q >= min is false): g_q = 0, and the
+         * chain below then gives 0 * finite = 0 and 0 * NaN = NaN, as autograd does (tests/golden/g_edges_sphere.npz) */
+        const float g_q = (bsq == bsq) ? g_sq / (2.0f * bsq) : 0.0f;
         const float g_xd = -g_q;
         const float g_dx = g_xd * (2.0f * dx);
         const float g_dy = g_xd * (2.0f * dy);

@@ -115,7 +115,8 @@ __device__ __forceinline__ void tile_min(unsigned long long mask, int J, const f
       if (hit) {
         const float sq = sqrtf(q);
         const float d = sz - sq;
-        const bool take = (d < best[k]) || (d != d);  // torch.min: NaN wins, ties keep first
+        // torch.min: a NaN wins over any number, ties keep the first index -- and so does the first of two NaNs
+        const bool take = !(d >= best[k]) && (best[k] == best[k]);
         if (take) {
           best[k] = d;
           owner[k] = j;
@@ -236,6 +237,8 @@ sphere_tile_bwd_kernel(const float4 *__restrict__ spheres, const float *__restri
     for (int k = 0; k < 4; k++) {
       const bool in = row_ok && (g.u0 + k < W) && owner[k] != SHR_ARGMIN_NONE;
       if (!in) owner[k] = SHR_ARGMIN_NONE;
+      // (a record with a NaN in x, y or r: w = NaN where autograd's clamp(min) passes 0 -- the same in the z-buffer
+      // kernels, which tests/test_multiview_gpu.py holds this kernel equal to; DESIGN.md section 3, recorded deviation)
       const float w = in ? gk[k] / bsq[k] : 0.f;
       pz[k] = in ? gk[k] : 0.f;
       pw[k] = -w;

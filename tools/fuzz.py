@@ -47,7 +47,7 @@ def sphere_case():
         if not ok:
             fails += 1
             print("SPHERE (non-finite) MISMATCH", dict(N=N, J=J, H=H, W=W, mode=mode, zb=zb))
-        return
+        return   # (gradients of non-finite records: tests/golden/g_edges_sphere.npz, tests/test_edges_gpu.py)
     ok = np.array_equal(bits(d.cpu().numpy()), bits(od)) and np.array_equal(a.cpu().numpy(), oa)
     why = [] if ok else ['fwd depth %d px, owner %d px' % (int((bits(d.cpu().numpy()) != bits(od)).sum()), int((a.cpu().numpy() != oa).sum()))]
     gd = rs.standard_normal((N, H, W)).astype(np.float32)
@@ -115,7 +115,7 @@ def d2m_case():
             D = np.abs(np.linalg.norm(P[:, None, :] - cen[n][None].astype(np.float64), axis=-1) - rad[None].astype(np.float64))
             m = D.min(1)
             if (np.abs(m - 50.0) < 2e-4).any() or (m < 2e-4).any():
-                return
+                return   # (on the clamp, on a surface: pinned by tests/golden/g_edges_d2m.npz, term_exactly_50 / point_on_surface)
             # a point equidistant from two DIFFERENT spheres to within a few fp32 ulps: which of them owns it (and gets
             # its unit vector) is decided by the last bit of the root -- v_sqrt_f32 here, sqrtf in the oracle, whatever
             # the reference's platform computes -- while the loss is the same: not a comparable case either (the long
@@ -127,7 +127,7 @@ def d2m_case():
                     order = np.argsort(D[close], axis=1)[:, :2]
                     same_record = np.all(cen[n][order[:, 0]] == cen[n][order[:, 1]], axis=1) & (rad[order[:, 0]] == rad[order[:, 1]])
                     if (~same_record).any():     # (duplicated spheres tie EXACTLY: the first index must win, that is checked)
-                        return
+                        return   # (exact ties are pinned by tests/golden/g_edges_d2m.npz, identical_spheres)
     loss, grad = ops.data_to_model(dev(depth), dev(cen), dev(rad), want_grad=True)
     # any launch shape gives the same bits (the sums are integers)
     ops.set_tuning(ops.TUNE_D2M_WAVES, int(rs.choice([4, 8, 16]))); ops.set_tuning(ops.TUNE_D2M_BAND_UNITS, int(rs.choice([1, 2, 3, 8])))
