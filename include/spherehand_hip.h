@@ -1153,6 +1153,81 @@ int shr_sphere_icp_normal(const float *observed      /* [B,V,H,W] */,
                           double *moments /* [B,J,12] or NULL */, float *dist /* [B,V,H,W] or NULL */,
                           int32_t *owner /* [B,V,H,W] or NULL */, void *workspace, void *stream);
 
+/* The model-to-data term of the sphere fit: Gauss-Newton rows of the RENDERED spheres against observed depth ---------------
+ * The reference fits the sphere model with MSELoss(render, observed) + 500 DataToModelLoss (mesh/multiview_utility.py:96-129);
+ * shr_sphere_icp_normal above is the second term, this entry is the first: the spheres are rendered as BallRender.forward
+ * and the min over the sphere axis render them (mesh/render.py:26-53, :87-89), the render is compared with the
+ * observation, and every model pixel gives a row.  A sphere that lies over observed background, or in front of the
+ * observed surface, gives no row to shr_sphere_icp_normal and many to this entry.  The reference has no counterpart of
+ * the normal equations.  One evaluation of the combined fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_normal
+ *     -> shr_sphere_render_normal(accumulate = 1) -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_sphere_render_normal   the normal equations of weight / 2 sum e^2, e = D - O', over the model pixels of all views
+ *       with respect to the 26 pose parameters.  observed, view_centres, radii, view, jac, ax, bx, ay, by, fg_max:
+ *       shr_sphere_icp_normal's.
+ *       Render.  All fp32, one correctly rounded operation per written operator, nothing contracted.  Pixel (row i, column
+ *       j) has xg = ax (float)j + bx, yg = ay (float)i + by.  D = background, owner = -1, behind = true; for k ascending
+ *       with (x, y, z) = view_centres[b,v,k,0..2], r = radii[k]: dx = xg - x, dy = yg - y, q = (r r - dx dx) - dy dy
+ *       (shr_sphere_raster_fwd's sequence); the sphere HITS iff q > 0.01f, and then d = z - sqrt(q), the root correctly
+ *       rounded (no root is taken otherwise).  A hit with d < D is taken: D = d, owner = k (a NaN is never taken, equal
+ *       depths keep the smallest index).  A hit with d == D while owner == -1 and behind, that is exactly AT the
+ *       background with every lower sphere hitting strictly behind it, is taken too: torch.min's first index over maps
+ *       that hold the background where a sphere misses.  After a hit behind = behind && d > background; after a miss
+ *       behind = false.  For a power-of-two W == H == S, (ax, bx, ay, by) = (300 / S, -150, 300 / S, -150) and
+ *       background = 100 the grid is shr_sphere_raster_fwd's bit for bit: depth equals its depth in every bit and owner
+ *       its argmin with 255 as -1.
+ *       -> depth[B,V,H,W] fp32 (or NULL) = D; owner[B,V,H,W] int32 (or NULL).  Every element of a map that is given is
+ *       written, whatever the observation holds.
+ *       Residual.  A pixel whose observed depth is a NaN gives no term and no row.  Otherwise O' = observed < fg_max ?
+ *       observed : background and e = (double)D - (double)O'.  The pixel's cost term is min(|e|, (double)max_resid)^2: a
+ *       truncated quadratic; a pixel without an owner over an observed point has D = background and pays its term, but
+ *       has no row.
+ *       Row.  A pixel gives a row iff it has an owner, |e| < max_resid and, recomputed in fp64 from the fp32 xg, yg, x, y, r
+ *       of the owner, s = sqrt((r r - dx dx) - dy dy) with dx = xg - x, dy = yg - y is finite and > 0.  Then the gradient
+ *       of D with respect to the owner's centre in the view's frame is (-dx / s, -dy / s, 1), taken back to the model
+ *       frame in fp64 with shr_pose_icp_normal_views' association and negated: u_j = -((R0j v0 + R1j v1) + R2j v2)
+ *       (u = -R^T grad).  The row is d e / d params = -u^T jac[3 owner .. 3 owner + 2, :]: shr_sphere_icp_normal's
+ *       convention, so that the two entries' A and g add.  A pixel with e = 0 still gives a row.
+ *       -> moments[B,J,12] fp64 (or NULL), for the rows owned by sphere j: S = sum u u^T as (xx, xy, xz, yy, yz, zz),
+ *       h = sum e u (3), sum e^2 over the rows, the number of rows (as a double), and one spare 0: this term's own,
+ *       unweighted.  count[B] int32: the rows, likewise.
+ *       weight and accumulate.  With A_r = sum_j Jc_j^T S_j Jc_j, g_r = -sum_j Jc_j^T h_j (Jc_j = jac[3j .. 3j + 2, :], all
+ *       26 columns of every sphere) and cost_r = the sum of the cost terms over ALL pixels of all views:
+ *         accumulate == 0:  A = w A_r, g = w g_r, cost = w cost_r                  (w = (double)weight)
+ *         accumulate == 1:  A += w A_r, g += w g_r, cost += w cost_r: one product and one sum per entry, on top of what
+ *                           the buffers hold -- the output of a preceding shr_sphere_icp_normal.  The LOWER triangle of A
+ *                           is read and the sum written to both triangles.  With weight == 0 the three are not touched.
+ *       Summation order (the contract), shr_sphere_icp_normal's word for word: fixed-order fp64 chains, no atomics.  The
+ *       pixels of a view in row-major order form tiles of 1024; every moment of every sphere is one chain from 0 over its
+ *       rows of the tile in ascending pixel order; the tiles' values are added from 0, tiles ascending inside a view,
+ *       views ascending.  The cost runs in the same order over the pixels with a term != 0, then over the tiles, as a
+ *       COMPENSATED chain: a pair (hi, lo) from (0, 0), each term x added by t = hi + x, b = t - hi,
+ *       lo += (hi - (t - b)) + (x - b), hi = t (a tile's lo is added to lo); cost_r = hi + lo.  A_r entry (a, c), a >= c, is
+ *       a chain from 0 over the spheres in ascending order -- a sphere without a row is skipped -- of
+ *       (Jc[0,a] t0 + Jc[1,a] t1) + Jc[2,a] t2, t_k = (S_k0 Jc[0,c] + S_k1 Jc[1,c]) + S_k2 Jc[2,c], written to both
+ *       triangles: bit-symmetric; g_r,a is minus the chain of (Jc[0,a] h0 + Jc[1,a] h1) + Jc[2,a] h2.  Bitwise
+ *       reproducible; a sample's result does not depend on the batch it is in or on the launch shape; no host
+ *       synchronisation.  Every pixel meets every sphere: nothing is pruned.
+ *       workspace: 16-byte aligned, shr_sphere_render_normal_workspace_bytes(B, V, J, W, H) bytes (-1 on a negative size):
+ *       8 (12 J + 4) bytes per (sample, view, tile), written by the call before it is read.
+ *   Argument rules, checked before the B == 0 no-op: 1 <= H, W; 1 <= V; 1 <= J; B >= 0; max_resid >= 0, +inf allowed;
+ *   weight finite and >= 0; background finite; accumulate 0 or 1 (SHR_EINVAL otherwise); H, W above 2048, J above 64, B or
+ *   B V above 65535: SHR_ETOOLARGE.  B == 0 is a no-op.  NULLs other than moments, depth and owner, and misaligned pointers
+ *   (4 bytes; A, g, cost, moments 8; view_centres, workspace 16): SHR_EINVAL.  Centres and radii are taken to be finite
+ *   (NOT checked); the rotation is NOT checked to be orthonormal. */
+long long shr_sphere_render_normal_workspace_bytes(int B, int V, int J, int W, int H);
+int shr_sphere_render_normal(const float *observed      /* [B,V,H,W] */,
+                             const float *view_centres  /* [B,V,J,4]: shr_view_vertices_fwd of the keypoints */,
+                             const float *radii         /* [J] */,
+                             const float *view          /* [B,V,4,4] */,
+                             const float *jac           /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                             int B, int V, int J, int W, int H, float ax, float bx, float ay, float by,
+                             float fg_max, float background, float max_resid, float weight, int accumulate,
+                             double *A, double *g, double *cost, int32_t *count,
+                             double *moments /* [B,J,12] or NULL */, float *depth /* [B,V,H,W] or NULL */,
+                             int32_t *owner /* [B,V,H,W] or NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

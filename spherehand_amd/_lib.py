@@ -138,6 +138,8 @@ SIGNATURES = {
     "shr_pose_icp_normal_views": ([_vp] * 12 + [_i] * 7 + [_f] * 6 + [_vp] * 6, _i),
     "shr_sphere_icp_normal_workspace_bytes": ([_i, _i, _i, _i, _i], ctypes.c_longlong),
     "shr_sphere_icp_normal": ([_vp] * 5 + [_i] * 5 + [_f] * 6 + [_vp] * 9, _i),
+    "shr_sphere_render_normal_workspace_bytes": ([_i, _i, _i, _i, _i], ctypes.c_longlong),
+    "shr_sphere_render_normal": ([_vp] * 5 + [_i] * 5 + [_f] * 8 + [_i] + [_vp] * 9, _i),
     "shr_selftest_sqrt":([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_division": ([ctypes.c_uint, ctypes.c_uint, _vp, _vp], _i),
     "shr_selftest_launch_floor": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),

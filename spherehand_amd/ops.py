@@ -2354,6 +2354,116 @@ def sphere_icp(observed, view, params0, offset, offset_inv, bone, wv, radii, rig
     return params, cost0, cost
 
 
+def _sphere_render_args(max_resid, background, weight, name="weight"):
+    max_resid, background, weight = float(max_resid), float(background), float(weight)
+    if not max_resid >= 0.0:
+        raise RuntimeError("max_resid must be >= 0 (inf: no saturation), not %r" % (max_resid,))
+    if not abs(background) < float("inf"):
+        raise RuntimeError("background must be finite, not %r" % (background,))
+    if not (weight >= 0.0 and weight < float("inf")):
+        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
+    return max_resid, background, weight
+
+
+def sphere_render_normal(observed, view, params, offset, offset_inv, bone, wv, radii, right_hand=True,
+                         pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_resid=float("inf"), background=100.0,
+                         weight=1.0, accumulate_into=None, want_maps=False):
+    """The Gauss-Newton normal equations of the RENDERED sphere model against observed depth, the model-to-data term
+    (include/spherehand_hip.h, shr_sphere_render_normal): sphere_icp_normal's arguments -> (A [B,26,26], g [B,26], cost [B]
+    fp64 over all pixels of all views, count [B] int32, moments [B,J,12] fp64); with want_maps also (depth [B,V,H,W] fp32,
+    owner [B,V,H,W] int32), the render and its owners.  A, g and cost are `weight` x the term's; count and moments are the
+    term's own.  accumulate_into = (A, g, cost) of sphere_icp_normal at the same pose: weight x the term is ADDED to them in
+    place (with weight = 0 they are not touched) and they are the A, g, cost returned.  Three launches:
+    shr_pose_keypoints_jacobian -> shr_view_vertices_fwd -> shr_sphere_render_normal."""
+    B, V, H, W, J, p2m, _ = _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, radii, pixel_to_model, 0.0)
+    max_resid, background, weight = _sphere_render_args(max_resid, background, weight)
+    dev = observed.device
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+            _check_input(t, name, torch.float64)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("accumulate_into's %s must be %s fp64 on observed's device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
+        _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
+        depth = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
+        owner = torch.empty((B, V, H, W), dtype=torch.int32, device=dev) if want_maps else None
+        ws = torch.empty((max(16, lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                                *p2m, float(fg_max), background, max_resid, weight,
+                                                int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(cost), _ptr(count),
+                                                _ptr(moments), _ptr(depth), _ptr(owner), _ptr(ws), _stream()),
+                   "shr_sphere_render_normal")
+    return (A, g, cost, count, moments) + ((depth, owner) if want_maps else ())
+
+
+def sphere_icp_render(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
+                      pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                      stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0):
+    """sphere_icp with the model-to-data term: `iters` Levenberg-Marquardt iterations on
+    sum dist^2 + render_weight sum min(|D - O'|, max_resid)^2 + sum_i stiffness_i (p_i - prior_i)^2, D the sphere render of
+    the pose (background where no sphere is hit), O' the observation with its background set to `background`, over all
+    pixels of all views -> (params [B,26], cost0 [B], cost [B]).  Each of the iters + 1 evaluations is sphere_icp's with
+    shr_sphere_render_normal(accumulate = 1) after shr_sphere_icp_normal, on torch's current stream, into buffers allocated
+    once before the loop; nothing returns to the host: capturable in a graph.  render_weight = 0 issues no launch of the
+    new entry: sphere_icp bit for bit."""
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
+                                                    max_dist, "start parameters")
+    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    dev = observed.device
+    state, trial = pose_lm_begin(params0, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
+        params, cost0, cost = f32(B, 26), f32(B), f32(B)
+        # (one workspace: the two entries' formulas agree, and each writes it before it reads it)
+        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
+                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
+                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
+            if render_weight > 0.0:
+                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
+                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
+                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
+                                                        stream), "shr_sphere_render_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
+                                            _ptr(cost0), stream), "shr_pose_lm_step")
+    return params, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

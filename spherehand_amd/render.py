@@ -908,6 +908,59 @@ class SpherePoseFitter(nn.Module):
                                      self.max_dist)
 
 
+class SphereRenderPoseFitter(SpherePoseFitter):
+    """SpherePoseFitter with the reference's other term (mesh/multiview_utility.py:96-129 fits MSELoss(render, observed)
+    beside DataToModelLoss): `iters` Levenberg-Marquardt iterations on
+        sum dist^2 + render_weight sum min(|D - O'|, max_resid)^2 + sum_i stiffness_i (p_i - prior_i)^2,
+    D the sphere model's rendered depth (shr_sphere_raster_fwd's rule; `background` where no sphere is hit) and O' the
+    observation with its background set to `background`, over every pixel of every view (ops.sphere_icp_render;
+    include/spherehand_hip.h, shr_sphere_render_normal).  The data-to-model distance alone is blind to a sphere that lies
+    over observed background or in front of the observed surface: no observed point is nearest to it, so nothing but the
+    stiffness holds it.  Here every model pixel is a row.  The row's derivative holds the owner and the silhouette fixed,
+    as ops.SphereDepthRaster's backward does.
+        solve(observed, params0, view=None, prior=None) -> (params, cost0, cost)
+        normal_equations(observed, params, view=None) -> (A, g, cost, count, moments) of the SUM of the two terms' A, g and
+                                                          cost; count and moments are the render term's own
+    render_weight = 0 is SpherePoseFitter bit for bit.  The defaults are the best row of DESIGN.md 4.4q's study.  Everything
+    else, the limits included, is SpherePoseFitter's: a refinement from a start pose, NO autograd through the solve, the
+    rotation NOT checked."""
+
+    # DESIGN.md 4.4q: the study's best row
+    DEFAULT_RENDER_WEIGHT = 1.0
+    DEFAULT_MAX_RESID = 10.0
+
+    def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
+                 fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None, max_resid=None,
+                 background=100.0):
+        super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist)
+        self.render_weight = float(self.DEFAULT_RENDER_WEIGHT if render_weight is None else render_weight)
+        self.max_resid = float(self.DEFAULT_MAX_RESID if max_resid is None else max_resid)
+        self.background = float(background)
+        if not (self.render_weight >= 0.0 and self.render_weight < float("inf")) or not self.max_resid >= 0.0 or \
+                not abs(self.background) < float("inf"):
+            raise ValueError("render_weight must be finite and >= 0, max_resid >= 0 and background finite")
+
+    def _tables(self):
+        return self.fk.offset, self.fk.offset_inv, self.kp_bone, self.kp_wv, self.radii
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None):
+        observed, view = self._observed(observed, view)
+        return ops.sphere_icp_render(observed, view, params0.detach().contiguous().float(), *self._tables(), self.right_hand,
+                                     self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                     None if prior is None else prior.detach().contiguous().float(), self.render_weight,
+                                     self.max_resid, self.background)
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None):
+        observed, view = self._observed(observed, view)
+        params = params.detach().contiguous().float()
+        A, g, cost = ops.sphere_icp_normal(observed, view, params, *self._tables(), self.right_hand, self.pixel_to_model,
+                                           self.fg_max, self.max_dist)[:3]
+        return ops.sphere_render_normal(observed, view, params, *self._tables(), self.right_hand, self.pixel_to_model,
+                                        self.fg_max, self.max_resid, self.background, self.render_weight, (A, g, cost))
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster

@@ -1,0 +1,394 @@
+"""The model-to-data term of the sphere fit without a device: the entries of the C ABI with their argument rules, the new
+unit's code-object metadata, the restatement (tests/sphere_render_icp_ref.py) and what keeps it honest -- its g is the
+reverse-mode gradient of 1/2 weight sum e^2, A and g from the per-sphere moments equal the row-wise sums, a row agrees with
+central differences of the true residual with the owner held, a self-rendered observation is a minimum, the case the
+data-to-model term is blind to -- and the fp32 bars the GPU tests (tests/test_sphere_render_icp_gpu.py) hold the kernels to."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import pose_icp_ref as ref
+import sphere_icp_ref as sref
+import sphere_render_icp_ref as rref
+from conftest import ROOT
+from test_pose_ik_cpu import _metadata
+
+ENTRIES = ("shr_sphere_render_normal_workspace_bytes", "shr_sphere_render_normal")
+
+# The fp32 bars, measured as tests/test_sphere_icp_cpu.py measures its own: the restatement run with an fp32 chain against
+# the fp64 one on the GPU tests' inputs (sphere_icp_ref.cases' `right` and `left` with their three views, the odd shape and
+# the synthetic case), the largest deviation per quantity; the GPU tolerance is 4 x that.  A, g and the moments are compared
+# GIVEN THE SAME render and owner map (the fp64 run's).  test_fp32_bars measures them again and holds the constants to
+# within [1/2, 2].  They are two orders above the data-to-model term's: a pixel near a sphere's silhouette has a gradient
+# of (dx / s, dy / s) with s = sqrt(q) down to 0.1 mm against dx up to the radius, it enters A with the square of that, and
+# the fp32 rounding of a centre (1e-5 mm) moves s by dx / s^2 of that rounding: the few silhouette pixels carry the largest
+# entries AND the largest relative errors.
+FP32_A_DEVIATION = 8.8e-4         # max |A32 - A64| / max |A64| per sample, at the cases' params0
+FP32_G_DEVIATION = 1.4e-4         # max |g32 - g64| / max |g64| per sample
+FP32_M_DEVIATION = 2.3e-3         # the moments, per sample and group (uu^T | e u): max |M32 - M64| / max |M64| of the group
+FP32_COST_DEVIATION = 3.3e-7      # |cost32 - cost64| / cost64 of the two runs' own maps, the combined cost at params0
+FP32_STEP_DEVIATION = 3.3e-5      # rad | mm: the first step of the combined fit at params0
+FP32_POSE_DEVIATION = 3.4e-4      # rad | mm: the final pose of the end-to-end case, the samples whose accept sequence agrees
+A_BAR, G_BAR, M_BAR, COST_BAR, STEP_BAR, POSE_BAR = (4 * FP32_A_DEVIATION, 4 * FP32_G_DEVIATION, 4 * FP32_M_DEVIATION,
+                                                    4 * FP32_COST_DEVIATION, 4 * FP32_STEP_DEVIATION, 4 * FP32_POSE_DEVIATION)
+
+MOMENT_GROUPS = (slice(0, 6), slice(6, 9))     # (sum e^2 over the rows is a sum of the map's own values: no chain in it)
+WEIGHT, MAX_RESID = rref.DEFAULT_WEIGHT, rref.DEFAULT_MAX_RESID     # the module's defaults: DESIGN.md 4.4q's best row
+END_TO_END_ITERS = 6
+# The evaluations the GPU test of the equations runs and the bars are measured on: (case, samples, views, weight, max_resid)
+INF = float("inf")
+EVALUATIONS = (("right", 5, (0, 3), 1.0, INF), ("left", 5, (0, 3), 0.25, 10.0), ("right", 1, (2, 3), 0.25, INF),
+               ("left", 3, (1, 3), 1.0, 25.0), ("odd", 3, (0, 2), 0.5, INF))
+
+
+@pytest.fixture(scope="module")
+def mesh():
+    from spherehand_amd import hand_model
+    return hand_model.load_mesh()
+
+
+def test_header_loader_and_library_have_the_entries():
+    from spherehand_amd import _lib, build
+    text = open(os.path.join(ROOT, "include", "spherehand_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    h = ctypes.CDLL(build.build())
+    for name in ENTRIES:
+        assert re.search(r"\b%s\s*\(" % name, src), name
+        assert name in _lib.SIGNATURES and hasattr(h, name), name
+    assert text.count("through the SPHERE model") == 1
+    contract = text[text.index("The model-to-data term of the sphere fit"):text.index("long long shr_sphere_render_normal_workspace_bytes(")]
+    for cite in ("mesh/multiview_utility.py:96-129", "mesh/render.py:26-53", "no counterpart", "q > 0.01f", "smallest index",
+                 "NOT checked to be orthonormal", "tiles of 1024", "views ascending", "-R^T grad", "bit-symmetric", "COMPENSATED",
+                 "8 (12 J + 4) bytes per (sample, view, tile)", "65535", "accumulate == 1", "LOWER triangle", "weight finite",
+                 "background finite", "shr_sphere_raster_fwd's bit for bit"):
+        assert cite in contract, cite
+    assert text.index("shr_sphere_icp_normal(") < text.index("shr_sphere_render_normal(")       # after the data-to-model section
+    lib = _lib.lib()
+    assert lib.shr_abi_version() == _lib.ABI_VERSION == 23
+    ws = lib.shr_sphere_render_normal_workspace_bytes
+    assert ws(3, 2, 41, 48, 40) == 3 * 2 * 2 * 8 * (12 * 41 + 4) and ws(2, 3, 7, 32, 32) == 2 * 3 * 8 * (12 * 7 + 4)
+    assert ws(3, 2, 41, 33, 17) == 3 * 2 * 8 * (12 * 41 + 4)
+    assert ws(1, 1, 64, 2048, 2048) == 4096 * 8 * (12 * 64 + 4) and ws(0, 3, 41, 8, 8) == 0
+    for k in range(5):
+        bad = [1, 1, 41, 8, 8]
+        bad[k] = -1
+        assert ws(*bad) == -1
+    # host-side argument rules (every call below returns before a launch)
+    P = 1 << 20                                                    # a 16-byte aligned stand-in for a device address
+    normal = [P] * 5 + [2, 3, 41, 32, 32, 1.0, 0.0, 1.0, 0.0, 99.0, 100.0, 50.0, 0.5, 1] + [P] * 8 + [None]
+    bad = lambda i, val: lib.shr_sphere_render_normal(*(normal[:i] + [val] + normal[i + 1:]))   # noqa: E731
+    assert bad(5, 0) == 0                                          # B == 0: nothing to do
+    required, optional = [0, 1, 2, 3, 4, 19, 20, 21, 22, 26], [23, 24, 25]
+    for i in required:
+        assert bad(i, None) == -1, i
+    for i in required + optional:
+        assert bad(i, P + 2) == -1, i
+    for i in (1, 26, 19, 20, 21, 23):                              # view_centres, workspace: 16 bytes; A, g, cost, moments: 8
+        assert bad(i, P + 4) == -1, i
+    for i in (1, 26):
+        assert bad(i, P + 8) == -1, i
+    for i in (5, 6, 7):
+        assert bad(i, -1) == -1, i
+    assert bad(6, 0) == -1 and bad(7, 0) == -1 and bad(8, 0) == -1 and bad(9, 0) == -1       # 1 <= V, J, W, H
+    inf, nan = float("inf"), float("nan")
+    assert bad(16, -1.0) == -1 and bad(16, nan) == -1              # max_resid >= 0
+    assert bad(17, -0.5) == -1 and bad(17, inf) == -1 and bad(17, nan) == -1                  # weight finite and >= 0
+    assert bad(15, inf) == -1 and bad(15, -inf) == -1 and bad(15, nan) == -1                  # background finite
+    assert bad(18, 2) == -1 and bad(18, -1) == -1                  # accumulate 0 or 1
+    assert bad(5, 65536) == -2 and bad(8, 2049) == -2 and bad(9, 2049) == -2 and bad(7, 65) == -2
+    assert bad(6, 32768) == -2 and bad(6, 65536) == -2            # B V above 65535
+    none = list(normal)
+    none[5], none[6] = 0, 0                                        # the rules come before the no-op
+    assert lib.shr_sphere_render_normal(*none) == -1
+    none[6], none[7] = 1, 65
+    assert lib.shr_sphere_render_normal(*none) == -2
+    none[7], none[17] = 41, -1.0
+    assert lib.shr_sphere_render_normal(*none) == -1
+    none[17], none[18] = 0.0, 3
+    assert lib.shr_sphere_render_normal(*none) == -1
+    none[18], none[16] = 0, inf                                    # +inf is a max_resid, 0 a weight; B == 0 with NULLs is the no-op
+    assert lib.shr_sphere_render_normal(*([None] * 5 + none[5:19] + [None] * 9)) == 0
+
+
+def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
+    """sphere_render_icp.hip: two kernels, no scratch, no spills.  The scan kernel holds 64 (centre, radius) records, 256
+    pixel records of 13 doubles, 256 owners and four ballots in LDS (28 704 bytes, sphere_icp.hip's layout); the assembly
+    kernel 64 x 12 moments and the 192 x 26 fp32 Jacobian (26 112 bytes).  DESIGN.md 4.4q tables the figures.  The unit
+    includes common.h alone."""
+    sizes, kernels = _metadata("sphere_render_icp", tmp_path)
+    assert len(sizes) == 2 and max(sizes) == 0, sizes
+    assert len(kernels) == 2
+    lds = {"sphere_render_icp_scan_kernel": 64 * 16 + 256 * 13 * 8 + 256 * 4 + 4 * 8,
+           "sphere_render_icp_assemble_kernel": 64 * 12 * 8 + 192 * 26 * 4}
+    vgprs = {"sphere_render_icp_scan_kernel": 80, "sphere_render_icp_assemble_kernel": 48}
+    sgprs = {"sphere_render_icp_scan_kernel": 96, "sphere_render_icp_assemble_kernel": 80}
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("### 4.4q"):design.index("### 4.5 ")]
+    assert design.index("### 4.4p") < design.index("### 4.4q")
+    for name, k in kernels.items():
+        print(name, k)
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, name
+        short = [n for n in lds if n in name]
+        assert len(short) == 1, name
+        assert k["group_segment_fixed_size"] == lds[short[0]], name
+        assert k["vgpr_count"] <= vgprs[short[0]] and k["sgpr_count"] <= sgprs[short[0]], name
+        assert short[0] in section, short[0]
+    assert "28 704" in section and "26 112" in section
+    unit = open(os.path.join(ROOT, "spherehand_amd", "csrc", "sphere_render_icp.hip")).read()
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["common.h"]
+
+
+def evaluations(mesh):
+    """(case, centres32 or None): the hand cases at their starts, the odd shape and the synthetic case (its views are built
+    on the fp32 chain's centres, which both dtypes are then handed)."""
+    syn = sref.synthetic_case(mesh)
+    return [(rref.case(mesh, "right"), None), (rref.case(mesh, "left"), None), (rref.case(mesh, "odd"), None),
+            (syn, syn["centres32"])]
+
+
+def test_render_rule(mesh):
+    """The numpy render: background and -1 where nothing is hit, a hit needs q > 0.01f, the first index wins a tie (the
+    synthetic table's twin never owns a pixel), and a sphere exactly AT the background owns its pixel only while every
+    lower sphere hits behind it."""
+    case = sref.synthetic_case(mesh)
+    depth, owner = rref.render32(case["centres32"], case["model"].radii, case["p2m"], case["W"], case["H"])
+    assert (owner == sref.SYN_TWIN_OF).any() and not (owner == sref.SYN_TWIN).any() and not (owner == sref.SYN_ZERO).any()
+    assert ((owner < 0) == (depth == np.float32(100.0))).all() and (owner >= 0).sum() > 30
+    p2m = ref.grid(32, 32)
+    gx, gy = sref.grid32(p2m, 32, 32)
+    at = lambda z, r=5.0: [gx[10], gy[12], np.float32(z), 0.0]     # noqa: E731  (a sphere centred on pixel (12, 10))
+    radii = np.full(3, 5.0, np.float32)
+    for centres, want_owner, want_depth in (
+            ([at(105.0), at(300.0), at(400.0)], 0, 100.0),         # exactly at the background, the first: the owner
+            ([at(300.0), at(105.0), at(400.0)], 1, 100.0),         # the lower sphere hits behind: still the owner
+            ([[gx[20], gy[20], 50.0, 0.0], at(105.0), at(400.0)], -1, 100.0),   # a lower sphere MISSES the pixel: background
+            ([at(104.0), at(104.0), at(300.0)], 0, 99.0),          # equal depths: the first index
+            ([at(300.0), at(400.0), at(500.0)], -1, 100.0)):       # every hit behind the background
+        d, o = rref.render32(np.asarray(centres, np.float32)[None, None], radii, p2m, 32, 32)
+        assert o[0, 0, 12, 10] == want_owner and d[0, 0, 12, 10] == np.float32(want_depth), (centres, o[0, 0, 12, 10])
+    q_edge = np.asarray([[gx[10] + np.float32(4.9995), gy[12], 50.0, 0.0]], np.float32)       # q = 25 - 4.9995^2 < 0.01
+    assert rref.render32(q_edge[None, None], radii[:1], p2m, 32, 32)[1][0, 0, 12, 10] == -1
+
+
+def test_g_is_the_autograd_gradient(mesh):
+    """g of the restatement (rows from forward mode) = the reverse-mode gradient of 1/2 weight sum e^2 over the rows of all
+    views, e the chain's own residual with the owner held, through the restated chain and view transform, to 1e-12 of its
+    largest entry; A is symmetric and positive semi-definite; the per-sphere row counts add up; the cost is the sum of the
+    clipped squares."""
+    w = 0.25
+    for case, c32 in evaluations(mesh):
+        m, view, obs, p = case["model"], case["view"], case["observed"], case["params0"].float().double()
+        n = rref.normal(m, view, obs, p, case["p2m"], centres32=c32, chain_residual=True)
+        q = p.clone().requires_grad_(True)
+        e = rref.residuals(m, view, q, n["pixels"])
+        (0.5 * w * (e * e).sum()).backward()
+        err, scale = (q.grad - w * n["g"]).abs().max().item(), w * n["g"].abs().max().item()
+        print("%s: rows per sample %s; |g - autograd| %.3g of %.3g" % (case["name"], n["count"].tolist(), err, scale))
+        assert int(n["count"].min()) > 15 and err < 1e-12 * scale
+        A = n["A"]
+        assert torch.equal(A, A.transpose(1, 2)) and bool((torch.linalg.eigvalsh(A)[:, 0] > -1e-9 * scale).all())
+        assert torch.equal(n["moments"][..., 10].sum(1).long(), n["count"])
+        contract = rref.normal(m, view, obs, p, case["p2m"], centres32=c32)
+        dev = ((contract["g"] - n["g"]).abs().amax(1) / n["g"].abs().amax(1)).max().item()
+        print("    the contract's e (the fp32 render) against the chain's: g differs by %.3g" % dev)
+        assert dev < 1e-5
+        near = rref.normal(m, view, obs, p, case["p2m"], centres32=c32, max_resid=10.0)
+        e_map = rref.residual_map(obs, near["depth"])
+        sat = np.abs(e_map) >= 10.0
+        assert torch.equal(near["count"], torch.as_tensor(((near["owner"] >= 0) & ~sat).sum((1, 2, 3))))
+        assert torch.allclose(near["cost"], torch.as_tensor(np.where(sat, 100.0, e_map ** 2).sum((1, 2, 3))), rtol=1e-13)
+
+
+def test_moments_give_A_and_g(mesh):
+    """A = sum_j Jc_j^T S_j Jc_j and g = -sum_j Jc_j^T h_j from the moments (directions by autograd with respect to the
+    model-frame centres, the Jacobian by reverse mode) equal the row-wise sums (rows by forward mode) to rounding: the sign
+    convention is shr_sphere_icp_normal's."""
+    for case, c32 in evaluations(mesh):
+        m, p = case["model"], case["params0"].float().double()
+        n = rref.normal(m, case["view"], case["observed"], p, case["p2m"], centres32=c32)
+        A, g = sref.from_moments(m, p, n["moments"])
+        ea = ((A - n["A"]).abs().amax((1, 2)) / n["A"].abs().amax((1, 2))).max().item()
+        eg = ((g - n["g"]).abs().amax(1) / n["g"].abs().amax(1)).max().item()
+        print("%s: A from the moments %.3g, g %.3g (relative to the largest entry)" % (case["name"], ea, eg))
+        assert ea < 1e-12 and eg < 1e-12
+
+
+def test_rows_against_central_differences(mesh):
+    """e(p + h t) - e(p - h t) over 2 h against J t under the GENERAL rotation, e the TRUE residual of the pixel with its
+    owner held, in fp64.  The pixels within 1 mm of their sphere's silhouette (s < 1: the root's curvature is unbounded
+    there) are left out; on the rest the discrepancy is the differences' own second-order term: it falls by 4 from
+    h = 2^-16 to h / 2."""
+    base = rref.case(mesh, "right")
+    m, p, p2m = base["model"], base["params0"].float().double(), base["p2m"]
+    view, obs = base["view"][:, 2:3], base["observed"][:, 2:3]
+    R = view[0, 0, :3, :3].numpy()
+    assert np.abs(R - R.T).max() > 0.3 and np.abs(np.abs(R) - np.eye(3)).max() > 0.1
+    n = rref.normal(m, view, obs, p, p2m)
+    pts = n["pixels"]
+    _, J = rref.rows(m, view, p, pts)
+    c = m.view_centres(p, view)[torch.as_tensor(pts[0]), torch.as_tensor(pts[1]), torch.as_tensor(pts[3])]
+    r = torch.as_tensor(m.radii.astype(np.float64))[torch.as_tensor(pts[3])]
+    xy = torch.as_tensor(pts[2])
+    inner = (r * r - (xy[:, 0] - c[:, 0]) ** 2 - (xy[:, 1] - c[:, 1]) ** 2).sqrt() > 1.0
+    gen = torch.Generator().manual_seed(5)
+    directions = [torch.randn(p.shape, generator=gen, dtype=torch.float64) for _ in range(3)]
+    errs = []
+    for h in (2.0 ** -16, 2.0 ** -17):
+        worst = 0.0
+        for t in directions:
+            t = t / t.norm(dim=1, keepdim=True)
+            fd = (rref.residuals(m, view, p + h * t, pts) - rref.residuals(m, view, p - h * t, pts)) / (2 * h)
+            jt = (J * t[torch.as_tensor(pts[0])]).sum(-1)
+            worst = max(worst, (fd - jt)[inner].abs().max().item())
+        errs.append(worst)
+    print("|fd - J t| %.3g at h = 2^-16, %.3g at h / 2: ratio %.2f over %d of %d pixels; largest |J| %.3g"
+          % (errs[0], errs[1], errs[0] / errs[1], int(inner.sum()), len(inner), J[inner].abs().max().item()))
+    assert int(inner.sum()) > 200 and 3.5 < errs[0] / errs[1] < 4.5 and errs[1] < 1e-3 * J[inner].abs().max().item()
+
+
+def test_self_rendered_observation_is_a_minimum(mesh):
+    """At p* the observation the model rendered itself under the rasterizer's hit rule (render64: fp64 inside, rounded
+    once) has every residual at the fp32 rounding of the depth: the fp32 render rounds five times on the way to a depth
+    below 128 mm (3.8e-6 mm per rounding at the depth, 1.5e-5 at r^2 <= 600 and a root's derivative 1 / (2 s) <= 5 on a hit)
+    -- every |e| is below 1e-3 mm, most far below.  So cost(p*) <= pixels 1e-6 and |g(p*)| <= 1e-3 sum |row|, against costs
+    of 1e5 and more at the starts.  The few pixels at which a sphere's q is within 1e-3 of the hit threshold (the fp32 q may
+    decide the hit the other way and show the sphere behind), and those whose surface lies between fg_max and the background
+    (the observation calls it background), are taken out of the observation: a NaN has no term."""
+    for name in ("right", "left"):
+        case = rref.case(mesh, name)
+        m, view, p = case["model"], case["view"], case["p_star"]
+        obs = rref.render64(m, view, p, case["W"], case["H"], case["p2m"])
+        undecided = rref.undecided_hits(m, view, p, case["W"], case["H"], case["p2m"])
+        undecided |= (obs >= np.float32(ref.FG_MAX)) & (obs < np.float32(rref.BACKGROUND))   # a surface the observation calls background
+        assert undecided.sum() <= 1e-3 * undecided.size
+        obs = np.where(undecided, np.float32("nan"), obs)
+        n = rref.normal(m, view, obs, p, case["p2m"])
+        e = rref.residual_map(obs, n["depth"])
+        _, J = rref.rows(m, view, p, n["pixels"])
+        bound = torch.zeros_like(n["g"]).index_add_(0, torch.as_tensor(n["pixels"][0]), J.abs()) * 1e-3
+        n0 = rref.normal(m, view, obs, case["params0"].float().double(), case["p2m"])
+        print("%s: cost(p*) %s, |g(p*)| %.3g, largest |e| %.3g over %s rows; cost(p0) %s" %
+              (name, n["cost"].tolist(), n["g"].abs().max().item(), np.nanmax(np.abs(e)), n["count"].tolist(), n0["cost"].tolist()))
+        assert np.nanmax(np.abs(e)) < 1e-3 and int(n["count"].min()) > 100
+        assert bool((n["cost"] <= n["count"].double() * 1e-6).all()) and bool((n["g"].abs() <= bound).all())
+        assert bool((n0["cost"] > 1e6 * n["cost"]).all())
+
+
+def test_blind_case(mesh):
+    """The case the data-to-model term cannot see (sphere_render_icp_ref.blind_case): no observed point is sphere BLIND's, so
+    its private parameters get a gradient of exactly 0 from the data-to-model term; its pixels lie over observed background
+    or in front of the observed surface, so the render term's gradient on them is not 0."""
+    case = rref.blind_case(mesh)
+    m, view, obs, p = case["model"], case["view"], case["observed"], case["params0"]
+    d = sref.normal(m, view, obs, p, case["p2m"], centres32=case["centres32"])
+    r = rref.normal(m, view, obs, p, case["p2m"], centres32=case["centres32"])
+    private = case["private"]
+    print("private parameters %s; data-to-model rows of the sphere %s, render rows %s; render g there %s"
+          % (private.tolist(), d["moments"][:, rref.BLIND, 10].tolist(), r["moments"][:, rref.BLIND, 10].tolist(),
+             r["g"][:, private].tolist()))
+    assert len(private) >= 2 and int(d["count"].min()) > 10
+    assert not bool(d["moments"][:, rref.BLIND].any()) and not bool(d["g"][:, private].any())
+    assert bool((r["moments"][:, rref.BLIND, 10] >= 1).all()) and bool((r["g"][:, private].abs().amax(1) > 1.0).all())
+
+
+def test_ops_refuse_what_the_kernels_do_not_take(mesh):
+    """No device here: the ops refuse CPU tensors and bad scalars with a RuntimeError; the module's tables and defaults."""
+    from spherehand_amd import ops
+    from spherehand_amd.render import SpherePoseFitter, SphereRenderPoseFitter
+    fit = SphereRenderPoseFitter(mesh, 48, 40, stiffness=ref.STIFFNESS)
+    base = SpherePoseFitter(mesh, 48, 40, stiffness=ref.STIFFNESS)
+    assert isinstance(fit, SpherePoseFitter) and fit.iters == base.iters and fit.max_dist == base.max_dist
+    assert fit.pixel_to_model == base.pixel_to_model and torch.equal(fit.radii, base.radii) and fit.background == 100.0
+    assert fit.render_weight == SphereRenderPoseFitter.DEFAULT_RENDER_WEIGHT == WEIGHT
+    assert fit.max_resid == SphereRenderPoseFitter.DEFAULT_MAX_RESID == MAX_RESID
+    assert SphereRenderPoseFitter(mesh, 48, 40, render_weight=0.0, max_resid=float("inf")).render_weight == 0.0
+    for word in ("SpherePoseFitter", "blind", "NO autograd", "NOT checked", "render_weight = 0", "4.4q", "silhouette fixed"):
+        assert word in SphereRenderPoseFitter.__doc__, word
+    for bad in (dict(render_weight=-1.0), dict(render_weight=float("inf")), dict(max_resid=-1.0), dict(background=float("nan"))):
+        with pytest.raises(ValueError):
+            SphereRenderPoseFitter(mesh, 48, 40, **bad)
+    obs, view, p0 = torch.full((2, 3, 40, 48), 100.0), torch.eye(4).expand(2, 3, 4, 4).contiguous(), torch.zeros(2, 26)
+    tables = (fit.fk.offset, fit.fk.offset_inv, fit.kp_bone, fit.kp_wv, fit.radii)
+    for call in (lambda: fit.solve(obs, p0, view), lambda: fit.solve(obs[:, 0], p0), lambda: fit.normal_equations(obs, p0, view),
+                 lambda: fit.solve(obs, p0), lambda: fit.solve(obs[:, :, :8], p0, view),
+                 lambda: ops.sphere_render_normal(obs, view, p0, *tables),
+                 lambda: ops.sphere_icp_render(obs, view, p0, *tables, iters=-1),
+                 lambda: ops.sphere_icp_render(obs, view, p0, *tables, render_weight=-1.0),
+                 lambda: ops.sphere_render_normal(obs, view, p0, *tables, weight=float("nan")),
+                 lambda: ops.sphere_render_normal(obs, view, p0, *tables, max_resid=-2.0),
+                 lambda: ops.sphere_render_normal(obs, view, p0, *tables, background=float("inf"))):
+        with pytest.raises(RuntimeError):
+            call()
+
+
+_RUNS = {}
+
+
+def end_to_end_runs(case):
+    """dtype -> sphere_render_icp_ref.solve of the case with the module's defaults, once per process (the GPU tests run the
+    same)."""
+    if case["name"] not in _RUNS:
+        p0 = case["params0"].float().double()
+        _RUNS[case["name"]] = {dt: rref.solve(case["model"].to(dt), case["view"], case["observed"], p0, case["p2m"], WEIGHT,
+                                              MAX_RESID, END_TO_END_ITERS, stiffness=case["stiffness"])
+                               for dt in (torch.float64, torch.float32)}
+    return _RUNS[case["name"]]
+
+
+def fp32_deviations(mesh):
+    """The figures, measured: (A, g, M, cost, step, pose); `same`: the samples of the end-to-end case whose accept sequence
+    the fp32 run reproduces (`pose` is over them)."""
+    dev = dict(A=0.0, g=0.0, M=0.0, cost=0.0, step=0.0, pose=0.0)
+    syn = sref.synthetic_case(mesh)
+    runs = [(rref.case(mesh, name), None, slice(0, rows), slice(*views), max_resid) for name, rows, views, _, max_resid in EVALUATIONS]
+    for case, c32, rows, views, max_resid in runs + [(syn, syn["centres32"], slice(None), slice(None), INF)]:
+        m64, m32 = case["model"], case["model"].to(torch.float32)
+        view, obs, p, p2m = case["view"][rows, views], case["observed"][rows, views], case["params0"][rows].float().double(), case["p2m"]
+        a = rref.normal(m64, view, obs, p, p2m, centres32=c32, max_resid=max_resid)
+        held = m64.centres32(p, view) if c32 is None else c32
+        b = rref.normal(m32, view, obs, p, p2m, owner=a["owner"], depth=a["depth"], centres32=held, max_resid=max_resid)
+        assert torch.equal(a["count"], b["count"])
+        dev["A"] = max(dev["A"], ((a["A"] - b["A"]).abs().amax((1, 2)) / a["A"].abs().amax((1, 2))).max().item())
+        dev["g"] = max(dev["g"], ((a["g"] - b["g"]).abs().amax(1) / a["g"].abs().amax(1)).max().item())
+        for grp in MOMENT_GROUPS:
+            ma, mb = a["moments"][..., grp], b["moments"][..., grp]
+            dev["M"] = max(dev["M"], ((ma - mb).abs().amax((1, 2)) / ma.abs().amax((1, 2))).max().item())
+        print("%s %s: A %.3g, g %.3g, M %.3g so far" % (case["name"], max_resid, dev["A"], dev["g"], dev["M"]))
+    for name in ("right", "left", "odd"):                                        # the combined fit's first step, own maps
+        case = rref.case(mesh, name)
+        view, obs, p, p2m, mu = case["view"], case["observed"], case["params0"].float().double(), case["p2m"], case["stiffness"]
+        steps, costs = [], []
+        for m in (case["model"], case["model"].to(torch.float32)):
+            A, g, cost = rref.combined(m, view, obs, p, p2m, WEIGHT, MAX_RESID)
+            lm = ref.LM(p, 1e-3, m.dtype)
+            steps.append(lm.step(A, g, cost, p, None, mu, True) - p)
+            costs.append(cost)
+        dev["cost"] = max(dev["cost"], ((costs[0] - costs[1]).abs() / costs[0]).max().item())
+        dev["step"] = max(dev["step"], (steps[0] - steps[1]).abs().max().item())
+        print("%s: cost %.3g, step %.3g so far" % (name, dev["cost"], dev["step"]))
+    case = rref.case(mesh, "end_to_end")
+    run = end_to_end_runs(case)
+    (q64, _, _, lm64), (q32, _, _, lm32) = run[torch.float64], run[torch.float32]
+    same = (torch.stack(lm64.history) == torch.stack(lm32.history)).all(0)
+    print("%s: last fp64 step %s; the fp32 run reproduces the accept sequence: %s; |pose32 - pose64| %s"
+          % (case["name"], lm64.last_step.tolist(), same.tolist(), (q64 - q32).abs().amax(1).tolist()))
+    dev["pose"] = (q64 - q32)[same].abs().max().item() if bool(same.any()) else float("nan")
+    return dev, same
+
+
+def test_fp32_bars(mesh):
+    """The constants above, measured again.  The fp32 / fp64 CPU pair keeps at least four of the five samples of the
+    end-to-end case at END_TO_END_ITERS iterations; the combined fit's cost falls on every sample."""
+    dev, same = fp32_deviations(mesh)
+    print("fp32 against fp64: A %.3g, g %.3g, M %.3g, cost %.3g, step %.3g, pose %.3g; same %s"
+          % (dev["A"], dev["g"], dev["M"], dev["cost"], dev["step"], dev["pose"], same.tolist()))
+    assert int(same.sum()) >= 4
+    _, cost0, cost, _ = end_to_end_runs(rref.case(mesh, "end_to_end"))[torch.float64]
+    assert bool((cost <= cost0).all())
+    for name, const in (("A", FP32_A_DEVIATION), ("g", FP32_G_DEVIATION), ("M", FP32_M_DEVIATION), ("cost", FP32_COST_DEVIATION),
+                        ("step", FP32_STEP_DEVIATION), ("pose", FP32_POSE_DEVIATION)):
+        assert const / 2 <= dev[name] <= 2 * const, (name, dev[name], const)
