@@ -1228,6 +1228,79 @@ int shr_sphere_render_normal(const float *observed      /* [B,V,H,W] */,
                              double *moments /* [B,J,12] or NULL */, float *depth /* [B,V,H,W] or NULL */,
                              int32_t *owner /* [B,V,H,W] or NULL */, void *workspace, void *stream);
 
+/* The terms beside the image terms of the sphere fit: predicted keypoints as soft anchors, hinges at the joint limits ------
+ * shr_sphere_icp_normal and shr_sphere_render_normal above are the two image terms; one depth view does not determine the
+ * pose (a finger the view hides is held by shr_pose_lm_step's stiffness alone), and nothing keeps a fitted flex or abduction
+ * inside the range a hand can take.  This entry adds the two terms every sphere-model tracker carries beside its image
+ * terms: the key-points predicted per view -- they ARE the sphere centres (mesh/render.py:65-88) -- as soft anchors, and
+ * hinge penalties at the limits of the pose parameters (the support of dataset/joint_angle.py:7-236's distribution is the
+ * table joint_angle.pose_limits() gives).  The reference has no counterpart of the normal equations.  Collision rows couple
+ * two spheres, do not fit the per-sphere record and are NOT part of this entry.  One evaluation of the fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_normal
+ *     -> shr_sphere_render_normal(accumulate = 1) -> shr_sphere_prior_normal(accumulate = 1) -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_sphere_prior_normal   the normal equations of 1/2 (kp_weight sum w min(|e|, kp_max)^2 + limit_weight sum h^2) with
+ *       respect to the 26 pose parameters.  view_centres, view, jac: shr_sphere_icp_normal's; params[B,26]: the pose the
+ *       centres belong to (NOT checked).
+ *       Keypoint term.  keypoints[B,V,J,3] fp32 in view v's frame (or NULL: no keypoint term), confidence[B,V,J] fp32 >= 0
+ *       (or NULL: 1; negative values are NOT checked).  For each pair (v, j): e = k - c in fp64 from the fp32 keypoints
+ *       and view_centres, target minus model as shr_sphere_icp_normal's p - c.  The pair has NO term and no row if a
+ *       component of k is a NaN or the confidence w is 0 or a NaN.  Otherwise n2 = (e0 e0 + e1 e1) + e2 e2 and
+ *       cap2 = (double)kp_max (double)kp_max (exact; +inf for kp_max = +inf); the pair is SATURATED iff not n2 < cap2 (a
+ *       distance exactly equal to kp_max is saturated; kp_max = +inf never saturates a finite e), and its cost term is
+ *       w t, t = n2 if n2 < cap2, else cap2: w min(|e|, kp_max)^2, a truncated quadratic.  A pair that is not saturated
+ *       gives THREE rows, one per axis a of the view's frame: residual e_a, direction u = row a of view's top-left 3 x 3
+ *       AS GIVEN (the rotation is NOT checked to be orthonormal), row = d e_a / d params = -u^T jac[3j .. 3j + 2, :]:
+ *       shr_sphere_icp_normal's convention, so that the entries' A and g add.  A pair with e = 0 still gives its three
+ *       rows: the directions are the axes, there is no singular case.
+ *       -> moments[B,J,12] fp64 (or NULL), sphere j over its pairs with rows: S = sum w u u^T as (xx, xy, xz, yy, yz, zz),
+ *       h = sum w e_a u (3), sum w e_a^2, the number of PAIRS that gave rows (as a double), and one spare 0: the keypoint
+ *       term's own, NOT weighted by kp_weight.  Without keypoints every moment is 0.
+ *       Limit term.  lower[26], upper[26] fp32 (both NULL: no limit term).  For parameter i, p = params[b,i]:
+ *       h_i = p > upper_i ? (double)p - (double)upper_i : (p < lower_i ? (double)p - (double)lower_i : 0).  A comparison
+ *       with a NaN never fires and an unlimited parameter carries -inf / +inf, which never fire; a value exactly ON a
+ *       bound gives no row and cost 0.  A parameter with h_i != 0 gives one row: limit_weight on A_ii, limit_weight h_i
+ *       on g_i, limit_weight h_i^2 in the cost.
+ *       -> count[B,2] int32: the pairs that gave rows (keypoint rows / 3) and the limit rows, whatever the weights.
+ *       weights and accumulate.  The keypoint part is USED iff keypoints != NULL and kp_weight > 0, the limit part iff
+ *       lower != NULL and limit_weight > 0; a part that is not used is an exact +0 everywhere.  With
+ *         A_p[a,c] = kw A_k[a,c] + (a == c and h_a != 0 ? lw : 0),  A_k = sum_j Jc_j^T S_j Jc_j  (Jc_j = jac[3j .. 3j + 2, :])
+ *         g_p[a]   = kw (0 - G_a) + (h_a != 0 ? lw h_a : 0),        G = sum_j Jc_j^T h_j
+ *         cost_p   = kw K + lw L         (kw = (double)kp_weight, lw = (double)limit_weight)
+ *         accumulate == 0:  A = A_p, g = g_p, cost = cost_p
+ *         accumulate == 1:  A += A_p, g += g_p, cost += cost_p: one sum per entry on top of what the buffers hold -- the
+ *                           output of the image terms.  The LOWER triangle of A is read and the sum written to both
+ *                           triangles, so A stays bit-symmetric.  If neither part is used the three are not touched.
+ *       Summation order (the contract): fixed-order fp64 chains, no atomics, nothing contracted.  Every moment of sphere j
+ *       is a chain from 0 over the views in ascending order of the pair's SUBTOTAL, the subtotal a chain from 0 over the
+ *       axes a = 0, 1, 2 of one product x y: (w u_p) u_q for S_pq, (w e_a) u_p for h_p, (w e_a) e_a for sum w e_a^2 -- two
+ *       identical views give exactly twice one view's moments.  A_k entry (a, c), a >= c, is a chain from 0 over the
+ *       spheres in ascending order -- a sphere without a row is skipped -- of (Jc[0,a] t0 + Jc[1,a] t1) + Jc[2,a] t2,
+ *       t_k = (S_k0 Jc[0,c] + S_k1 Jc[1,c]) + S_k2 Jc[2,c], written to both triangles: bit-symmetric; G_a is the chain of
+ *       (Jc[0,a] h0 + Jc[1,a] h1) + Jc[2,a] h2.  K is a chain from 0 over the spheres in ascending order of the sphere's
+ *       own chain from 0 over the views in ascending order of w t; L is a chain from 0 over i ascending of h_i h_i; the
+ *       limits come after the spheres: cost_p = kw K + lw L.  Bitwise reproducible; a sample's result does not depend on
+ *       the batch it is in or on the launch shape (one workgroup per sample); no host synchronisation.
+ *       workspace: none is needed; shr_sphere_prior_normal_workspace_bytes(B, V, J) is 0 (-1 on a negative size) and
+ *       workspace may be NULL (16-byte aligned if given).
+ *   Argument rules, checked before the B == 0 no-op: 1 <= V; 1 <= J; B >= 0; kp_max >= 0, +inf allowed; kp_weight and
+ *   limit_weight finite and >= 0; accumulate 0 or 1; lower and upper both NULL or both given; confidence without keypoints
+ *   (SHR_EINVAL otherwise); J above 64, B or B V above 65535: SHR_ETOOLARGE.  B == 0 is a no-op.  NULLs other than
+ *   keypoints, confidence, lower, upper, moments and workspace, and misaligned pointers (4 bytes; A, g, cost, moments 8;
+ *   view_centres, workspace 16): SHR_EINVAL. */
+long long shr_sphere_prior_normal_workspace_bytes(int B, int V, int J);
+int shr_sphere_prior_normal(const float *view_centres  /* [B,V,J,4]: shr_view_vertices_fwd of the keypoints */,
+                            const float *view          /* [B,V,4,4] */,
+                            const float *jac           /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                            const float *params        /* [B,26]: the pose the centres belong to */,
+                            const float *keypoints     /* [B,V,J,3] in view v's frame, or NULL: no keypoint term */,
+                            const float *confidence    /* [B,V,J] >= 0, or NULL = 1 */,
+                            float kp_weight, float kp_max,
+                            const float *lower /* [26] */, const float *upper /* [26]; both NULL: no limit term */,
+                            float limit_weight, int B, int V, int J, int accumulate,
+                            double *A, double *g, double *cost, int32_t *count /* [B,2]: keypoint rows / 3, limit rows */,
+                            double *moments /* [B,J,12] or NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

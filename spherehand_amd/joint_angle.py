@@ -137,6 +137,49 @@ def sample_poses(n, seed=None):
     return torch.stack([sample_pose() for _ in range(n)])
 
 
+# --------------------------------------------------------------------------- the support of the distribution
+def pose_limits():
+    """(lower [26], upper [26]) fp32: the support of sample_pose()'s distribution on the 20 finger parameters, -inf / +inf
+    on the six palm parameters (the palm is free).  The joint-limit term of the sphere fit (render.SpherePriorPoseFitter)
+    takes this table as its default.  Derived by hand from sample_pose()'s constants, d = pi / 180:
+
+      abduction   spread = (u - 0.35) / 1.55 in [-0.35, 0.65] / 1.55, wiggle in [-5 d, 5 d], so
+                  s = spread + wiggle in [-0.35 / 1.55 - 5 d, 0.65 / 1.55 + 5 d] = [-0.31307, 0.50662];
+                  index 1.55 s, middle 0.75 s, ring -0.75 s, pinky -2.2 s (the negative factors swap the ends).
+      flexes      every finger may draw any of the five generators (mode 9, and modes 0 .. 4), so the four fingers share
+                  one range per joint, the union over the generators:
+                    straight   u scale - scale:  [-0.25, 0], [-0.4, 0], [-0.34, 0]
+                    open       u scale - 0.1:    [-0.1, 0.15], [-0.1, 0.3], [-0.1, 0.24]
+                    curls      f1 = -0.2 + c1 + 0.2 c2, f2 = -0.4 + 0.2 c1 + c2 + 0.2 c3, f3 = -0.34 + 0.7 c2 + c3 with the
+                               +-10 d jitter inside each c: half-open c1 in [-10 d, 40 d], c2, c3 in [50 d, 100 d];
+                               pinching c1 in [50 d, 100 d], c2, c3 in [-5 d, 45 d]; closed all three in [50 d, 100 d].
+                               The coefficients are positive, so each f is extreme at the ends of its c's:
+                               largest (closed)    f1 = -0.2 + 120 d, f2 = -0.4 + 140 d, f3 = -0.34 + 170 d
+                               smallest            f1 = -0.2 + (-10 + 10) d = -0.2 (half-open),
+                                                   f2 = -0.4 + (10 - 5 - 1) d (pinching), f3 = -0.34 - 8.5 d (pinching)
+                  lower = (-0.25 straight, -0.4 straight, -0.34 - 8.5 d pinching), upper = the closed curl's.
+      thumb       u - 0.5 in [-0.5, 0.5]; flex in [-0.25, 0.1] or [0.1, 0.7]; 0.25 flex; 2 u - 1.7 in [-1.7, 0.3].
+
+    Each bound is rounded OUTWARD to fp32, so that a sampled fp32 value at the end of its range is still inside."""
+    import numpy as np
+    d = pi / 180
+    s_lo, s_hi = -0.35 / 1.55 - 5 * d, 0.65 / 1.55 + 5 * d
+    flex_lo = (-0.25, -0.4, -0.34 - 8.5 * d)
+    flex_hi = (-0.2 + 120 * d, -0.4 + 140 * d, -0.34 + 170 * d)
+    lo, hi = [-float("inf")] * 6, [float("inf")] * 6
+    for factor in (1.55, 0.75, -0.75, -2.2):                               # index, middle, ring, pinky
+        ends = sorted((factor * s_lo, factor * s_hi))
+        lo += [ends[0]] + list(flex_lo)
+        hi += [ends[1]] + list(flex_hi)
+    lo += [-0.5, -0.25, -0.0625, -1.7]                                      # thumb
+    hi += [0.5, 0.7, 0.175, 0.3]
+    lo64, hi64 = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    lo32, hi32 = lo64.astype(np.float32), hi64.astype(np.float32)
+    lo32 = np.where(lo32 > lo64, np.nextafter(lo32, np.float32(-np.inf)), lo32)
+    hi32 = np.where(hi32 < hi64, np.nextafter(hi32, np.float32(np.inf)), hi32)
+    return torch.from_numpy(lo32.astype(np.float32)), torch.from_numpy(hi32.astype(np.float32))
+
+
 # --------------------------------------------------------------------------- vectorised sampler
 _DEG = pi / 180
 # generator kinds per (sample, finger): 0 straight, 1 open, 2 half-open, 3 pinching, 4 closed (= _ANY's order)

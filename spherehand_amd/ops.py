@@ -2464,6 +2464,147 @@ def sphere_icp_render(observed, view, params0, offset, offset_inv, bone, wv, rad
     return params, cost0, cost
 
 
+def _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max, limits, limit_weight):
+    kp_weight, kp_max, limit_weight = float(kp_weight), float(kp_max), float(limit_weight)
+    if not (kp_weight >= 0.0 and kp_weight < float("inf")):
+        raise RuntimeError("kp_weight must be finite and >= 0, not %r" % (kp_weight,))
+    if not (limit_weight >= 0.0 and limit_weight < float("inf")):
+        raise RuntimeError("limit_weight must be finite and >= 0, not %r" % (limit_weight,))
+    if not kp_max >= 0.0:
+        raise RuntimeError("kp_max must be >= 0 (inf: no saturation), not %r" % (kp_max,))
+    if confidence is not None and keypoints is None:
+        raise RuntimeError("confidence without keypoints")
+    if keypoints is not None:
+        _check_input(keypoints, "keypoints")
+        if tuple(keypoints.shape) != (B, V, J, 3) or keypoints.device != dev:
+            raise RuntimeError("keypoints must be [B,V,J,3], in each view's frame, on observed's device")
+    if confidence is not None:
+        _check_input(confidence, "confidence")
+        if tuple(confidence.shape) != (B, V, J) or confidence.device != dev:
+            raise RuntimeError("confidence must be [B,V,J] on observed's device")
+    lower = upper = None
+    if limits is not None:
+        try:
+            lower, upper = limits
+        except (TypeError, ValueError):
+            raise RuntimeError("limits must be (lower [26], upper [26])")
+        for t, name in ((lower, "lower"), (upper, "upper")):
+            _check_input(t, name)
+            if tuple(t.shape) != (26,) or t.device != dev:
+                raise RuntimeError("limits' %s must be [26] on observed's device" % name)
+    return kp_weight, kp_max, limit_weight, lower, upper
+
+
+def sphere_prior_normal(view, params, offset, offset_inv, bone, wv, right_hand=True, keypoints=None, confidence=None,
+                        kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0, accumulate_into=None):
+    """The normal equations of the sphere fit's keypoint and joint-limit terms (include/spherehand_hip.h,
+    shr_sphere_prior_normal): view [B,V,4,4], params [B,26], the key-point tables of pose_keypoints_jacobian, keypoints
+    [B,V,J,3] in each view's frame (None: no keypoint term), confidence [B,V,J] >= 0 (None: 1), limits = (lower [26],
+    upper [26]) (None: no limit term) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B,2] int32: pairs with rows and limit
+    rows, moments [B,J,12] fp64).  A, g and cost carry kp_weight and limit_weight; count and moments are the terms' own.
+    accumulate_into = (A, g, cost) of the image terms at the same pose: the terms are ADDED to them in place (with no
+    weighted term they are not touched) and they are the A, g, cost returned.  Three launches:
+    shr_pose_keypoints_jacobian -> shr_view_vertices_fwd -> shr_sphere_prior_normal."""
+    Bp, J = _ik_tables(params, offset, offset_inv, bone, wv, "parameters")
+    dev = params.device
+    B, V = Bp, (view.shape[1] if torch.is_tensor(view) and view.dim() == 4 else 0)
+    _views_args(view, B, dev)
+    if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
+        raise RuntimeError("every tensor must be on the parameters' device")
+    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
+                                                                       limits, limit_weight)
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+            _check_input(t, name, torch.float64)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
+        _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
+        _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(params), _ptr(keypoints),
+                                               _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper), limit_weight,
+                                               B, V, J, int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(cost),
+                                               _ptr(count), _ptr(moments), None, _stream()), "shr_sphere_prior_normal")
+    return A, g, cost, count, moments
+
+
+def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
+                      pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                      stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
+                      keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0):
+    """sphere_icp_render with the keypoint and joint-limit terms: `iters` Levenberg-Marquardt iterations on
+    sphere_icp_render's energy + kp_weight sum w min(|k - c|, kp_max)^2 + limit_weight sum_i h_i^2, k the predicted
+    keypoints [B,V,J,3] in each view's frame with confidence w [B,V,J] (None: 1), c the sphere centres in that frame, h_i the
+    distance of parameter i beyond limits = (lower [26], upper [26]) -> (params [B,26], cost0 [B], cost [B]).  Each of the
+    iters + 1 evaluations is sphere_icp_render's with shr_sphere_prior_normal(accumulate = 1) after the render entry, on
+    torch's current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a
+    graph.  With no weighted term (both weights 0, or neither keypoints nor limits) it issues no launch of the new entry:
+    sphere_icp_render bit for bit."""
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
+                                                    max_dist, "start parameters")
+    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
+    dev = observed.device
+    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
+                                                                       limits, limit_weight)
+    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    state, trial = pose_lm_begin(params0, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
+        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        params, cost0, cost = f32(B, 26), f32(B), f32(B)
+        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
+                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
+                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
+            if render_weight > 0.0:
+                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
+                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
+                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
+                                                        stream), "shr_sphere_render_normal")
+            if priors:
+                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
+                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
+                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
+                                            _ptr(cost0), stream), "shr_pose_lm_step")
+    return params, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

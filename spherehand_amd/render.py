@@ -961,6 +961,84 @@ class SphereRenderPoseFitter(SpherePoseFitter):
                                         self.fg_max, self.max_resid, self.background, self.render_weight, (A, g, cost))
 
 
+class SpherePriorPoseFitter(SphereRenderPoseFitter):
+    """SphereRenderPoseFitter with the two terms a sphere-model tracker carries beside its image terms: `iters`
+    Levenberg-Marquardt iterations on
+        SphereRenderPoseFitter's energy + kp_weight sum w min(|k - c|, kp_max)^2 + limit_weight sum_i h_i^2,
+    k the keypoints the network predicts per view (they ARE the sphere centres), w their confidence, c the sphere centres
+    in the view's frame, and h_i the distance of pose parameter i beyond `limits` (ops.sphere_icp_priors;
+    include/spherehand_hip.h, shr_sphere_prior_normal).  One depth view does not determine the pose: a finger the view
+    hides is held by the stiffness alone, and nothing else keeps a flex inside the range a hand can take.
+        solve(observed, params0, view=None, prior=None, keypoints=None, confidence=None) -> (params, cost0, cost)
+        normal_equations(observed, params, view=None, keypoints=None, confidence=None)
+            -> (A, g, cost, count [B,2], moments) of the SUM of the four terms' A, g and cost; count (pairs with rows, limit
+               rows) and moments are the new terms' own
+    keypoints is [B,V,41,3] in each view's frame -- what the network and Hand3DHeatmapRender.inv_camera give per view --
+    or [B,41,3] with view=None; confidence [B,V,41] (or [B,41]) >= 0, None: 1.  A NaN keypoint or a confidence of 0 drops
+    the pair.  limits = (lower [26], upper [26]), default joint_angle.pose_limits(): the support of the reference's pose
+    distribution on the 20 finger parameters, the palm free; limits=False: no limit term.  Without keypoints and with
+    limit_weight = 0 it is SphereRenderPoseFitter bit for bit.  The defaults are the best row of DESIGN.md 4.4r's study;
+    the same section says what the terms do NOT fix: with the keypoints themselves wrong by more than kp_max the anchor
+    is silent, and a limit is no substitute for an observation.  Collision between spheres is NOT a term here.  Everything
+    else is SphereRenderPoseFitter's: a refinement from a start pose, NO autograd through the solve, the rotation
+    NOT checked."""
+
+    # DESIGN.md 4.4r: the study's best `noise`, one-view row at sigma_k = 5 mm
+    DEFAULT_KP_WEIGHT = 0.1
+    DEFAULT_KP_MAX = float("inf")
+    DEFAULT_LIMIT_WEIGHT = 1e4
+
+    def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
+                 fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None, max_resid=None,
+                 background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None):
+        super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
+                         render_weight, max_resid, background)
+        self.kp_weight = float(self.DEFAULT_KP_WEIGHT if kp_weight is None else kp_weight)
+        self.kp_max = float(self.DEFAULT_KP_MAX if kp_max is None else kp_max)
+        self.limit_weight = float(self.DEFAULT_LIMIT_WEIGHT if limit_weight is None else limit_weight)
+        if not (self.kp_weight >= 0.0 and self.kp_weight < float("inf")) or not self.kp_max >= 0.0 or \
+                not (self.limit_weight >= 0.0 and self.limit_weight < float("inf")):
+            raise ValueError("kp_weight and limit_weight must be finite and >= 0, kp_max >= 0")
+        if limits is None:
+            from .joint_angle import pose_limits
+            limits = pose_limits()
+        if limits is False:
+            lower = upper = None
+        else:
+            lower, upper = (torch.as_tensor(np.asarray(t, np.float32)).reshape(26).clone() for t in limits)
+        self.register_buffer('lower', lower)
+        self.register_buffer('upper', upper)
+
+    def _targets(self, observed, view, keypoints, confidence):
+        single = view is None
+        observed, view = self._observed(observed, view)
+        if keypoints is not None:
+            keypoints = keypoints.detach().float()
+            keypoints = (keypoints.unsqueeze(1) if single and keypoints.dim() == 3 else keypoints).contiguous()
+        if confidence is not None:
+            confidence = confidence.detach().float()
+            confidence = (confidence.unsqueeze(1) if single and confidence.dim() == 2 else confidence).contiguous()
+        limits = None if self.lower is None else (self.lower, self.upper)
+        return observed, view, keypoints, confidence, limits
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        return ops.sphere_icp_priors(observed, view, params0.detach().contiguous().float(), *self._tables(), self.right_hand,
+                                     self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                     None if prior is None else prior.detach().contiguous().float(), self.render_weight,
+                                     self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
+                                     limits, self.limit_weight)
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        params = params.detach().contiguous().float()
+        A, g, cost = SphereRenderPoseFitter.normal_equations(self, observed, params, view)[:3]
+        return ops.sphere_prior_normal(view, params, *self._tables()[:4], self.right_hand, keypoints, confidence,
+                                       self.kp_weight, self.kp_max, limits, self.limit_weight, (A, g, cost))
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster
