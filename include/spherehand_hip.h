@@ -1301,6 +1301,64 @@ int shr_sphere_prior_normal(const float *view_centres  /* [B,V,J,4]: shr_view_ve
                             double *A, double *g, double *cost, int32_t *count /* [B,2]: keypoint rows / 3, limit rows */,
                             double *moments /* [B,J,12] or NULL */, void *workspace, void *stream);
 
+/* The term against self-penetration of the sphere fit: pairs of spheres held apart ------------------------------------------
+ * The three entries above leave nothing in the fit's energy that keeps two fingers, or a finger and the palm, from passing
+ * through each other.  The reference carries that energy as CollisionLoss (mesh/render.py:145-176): the sum over a table
+ * of 690 pairs of relu(36 - |c_a - c_b|^2), which shr_pair_losses gives as a first-order loss.  That hinge is NOT the square
+ * of a residual, so it has no Gauss-Newton rows; the fit uses h = m - |c_a - c_b| instead, whose square has the same
+ * support, with the minimum distance m a PER-PAIR table: the shipped radii are a fat proxy (at the rest pose 26 of the 690
+ * pairs are closer than r_a + r_b), so "the radius sum" cannot be the threshold, and the reference's constant 6 mm is one
+ * choice of the table among others.  The reference has no counterpart of the normal equations.  A row couples TWO
+ * spheres; it does not fit the per-sphere moments[B,J,12] of the entries above and is assembled per pair.  The term is
+ * view-independent: it reads the MODEL-frame keypoints, not view_centres, and takes no view.  One evaluation of the fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_normal
+ *     -> shr_sphere_render_normal(accumulate = 1) -> shr_sphere_prior_normal(accumulate = 1)
+ *     -> shr_sphere_collision_normal(accumulate = 1) -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_sphere_collision_normal   the normal equations of 1/2 weight sum_k h_k^2 over the ACTIVE pairs with respect to the
+ *       26 pose parameters.  centres[B,J,4]: the keypoints shr_pose_keypoints_jacobian writes beside jac, in the model
+ *       frame (component 3 is not read); jac: shr_sphere_icp_normal's.
+ *       Pairs.  Pair k is (a, b, m) = (pair_a[k], pair_b[k], pair_min[k]), m in mm.  A pair with an index outside
+ *       0 .. J - 1, with a == b, or with m not > 0 (a NaN included) is SKIPPED: no term, no row, penetration 0, and
+ *       nothing is read for it -- a bad table cannot make the entry read out of bounds.  Otherwise, in fp64 from the fp32
+ *       centres: e = c_a - c_b, n = sqrt((e0 e0 + e1 e1) + e2 e2), the root correctly rounded.  The pair is ACTIVE iff
+ *       n < (double)m: a distance exactly equal to m is not active, the reference's hinge at its kink, and a NaN never
+ *       fires.  An active pair has h = (double)m - n and the cost term h h.  It gives ONE row iff also n > 0: coincident
+ *       centres pay m^2 and have no direction, so no row.  Direction u = e / n (three correctly rounded quotients),
+ *       D_ic = (double)jac[3a + i, c] - (double)jac[3b + i, c], and
+ *         row_c = 0 - ((u0 D_0c + u1 D_1c) + u2 D_2c) = d h / d params_c:
+ *       shr_sphere_icp_normal's convention, so that the entries' A and g add.  Swapping a and b negates e, u and D
+ *       exactly and leaves every output bit for bit.
+ *       -> count[B] int32: the pairs that gave rows, whatever the weight.  penetration[B,K] fp64 (or NULL): h at an active
+ *       pair, 0 elsewhere; the term's own, NOT weighted.
+ *       weight and accumulate.  The term is USED iff pair_a != NULL, K > 0 and weight > 0; a term that is not used is an
+ *       exact +0 everywhere.  With A_c = sum rows row row^T, G = sum rows h row, C = sum active h h and w = (double)weight:
+ *         accumulate == 0:  A = w A_c, g = w G, cost = w C
+ *         accumulate == 1:  A += w A_c, g += w G, cost += w C: one product and one sum per entry on top of what the
+ *                           buffers hold -- the output of the other terms.  The LOWER triangle of A is read and the sum
+ *                           written to both triangles, so A stays bit-symmetric.  If the term is not used the three are
+ *                           not touched.
+ *       Summation order (the contract): fixed-order fp64 chains, no atomics, nothing contracted.  A_c entry (a, c), a >= c,
+ *       is a chain from 0 over the pairs with rows in ascending k of row_a row_c, written to both triangles:
+ *       bit-symmetric; G_a is the chain over the same pairs of h row_a; C is the chain from 0 over the ACTIVE pairs in
+ *       ascending k of h h.  Bitwise reproducible; a sample's result does not depend on the batch it is in or on the
+ *       launch shape (one workgroup per sample); no host synchronisation.  Every pair of the table is met: nothing is
+ *       pruned.
+ *       workspace: none is needed; shr_sphere_collision_normal_workspace_bytes(B, J, K) is 0 (-1 on a negative size) and
+ *       workspace may be NULL (16-byte aligned if given).
+ *   Argument rules, checked before the B == 0 no-op: 1 <= J; B >= 0; K >= 0; weight finite and >= 0; accumulate 0 or 1;
+ *   pair_a, pair_b and pair_min all NULL or all given; K > 0 without them (SHR_EINVAL otherwise); J above 64, K above 4096,
+ *   B above 65535: SHR_ETOOLARGE.  B == 0 is a no-op.  NULLs other than the three pair arrays, penetration and workspace,
+ *   and misaligned pointers (4 bytes; A, g, cost, penetration 8; centres, workspace 16): SHR_EINVAL.  The Jacobian and the
+ *   centres of the pairs that are met are taken to be finite apart from the NaN rule above (NOT checked). */
+long long shr_sphere_collision_normal_workspace_bytes(int B, int J, int K);
+int shr_sphere_collision_normal(const float *centres   /* [B,J,4]: shr_pose_keypoints_jacobian's keypoints, MODEL frame */,
+                                const float *jac       /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                                const int32_t *pair_a, const int32_t *pair_b /* [K] */, const float *pair_min /* [K] mm */,
+                                float weight, int B, int J, int K, int accumulate,
+                                double *A, double *g, double *cost, int32_t *count /* [B] */,
+                                double *penetration /* [B,K] or NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

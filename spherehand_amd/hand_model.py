@@ -140,3 +140,33 @@ def unique_skin(mesh):
         ustart[u + 1] = ustart[u] + (b - a)
         ubone.append(bone[a:b]); uwv.append(wv[a:b])
     return ustart, np.concatenate(ubone).astype(np.int32), np.ascontiguousarray(np.concatenate(uwv), np.float32), index
+
+
+def collision_table(mesh, min_dist=6.0, radius_scale=None):
+    """The pair table of the sphere fit's collision term (include/spherehand_hip.h, shr_sphere_collision_normal):
+    (a [K] int32, b [K] int32, m [K] float32) on the reference's 690 pairs (render._collision_pairs(); mesh/render.py:150-162).
+    m is the pair's minimum distance in mm: `min_dist` for every pair by default, the reference's constant; with
+    `radius_scale` it is m_k = min(radius_scale (r_a + r_b), the pair's distance at the rest pose), so that the rest pose
+    has no active pair -- the shipped radii are a fat proxy, and 26 pairs are closer than r_a + r_b at rest.  The table is
+    validated here, where it is built: indices in range, a != b, every m > 0."""
+    from .render import _collision_pairs
+    centres, radii, _ = sphere_model(mesh)
+    J = len(radii)
+    a, b = (np.asarray(t, np.int32) for t in _collision_pairs())
+    if radius_scale is None:
+        min_dist = float(min_dist)
+        if not (min_dist > 0.0 and min_dist < float("inf")):
+            raise ValueError("min_dist must be finite and > 0, not %r" % (min_dist,))
+        m = np.full(len(a), min_dist, np.float32)
+    else:
+        radius_scale = float(radius_scale)
+        if not (radius_scale > 0.0 and radius_scale < float("inf")):
+            raise ValueError("radius_scale must be finite and > 0, not %r" % (radius_scale,))
+        # The rest distance is taken from the table's own centres, less 2^-16 of it: the fp32 chain at p = 0 gives centres
+        # within 3e-5 mm of the table's, and a pair capped by its rest distance must not fire on that rounding.
+        c = centres[:, :3].astype(np.float64)
+        rest = np.sqrt(((c[a] - c[b]) ** 2).sum(-1)) * (1.0 - 2.0 ** -16)
+        m = np.minimum(radius_scale * (radii[a].astype(np.float64) + radii[b].astype(np.float64)), rest).astype(np.float32)
+    if len(a) == 0 or a.min() < 0 or b.min() < 0 or a.max() >= J or b.max() >= J or bool((a == b).any()) or not bool((m > 0).all()):
+        raise ValueError("the collision table needs indices in 0 .. %d, a != b and every minimum distance > 0" % (J - 1))
+    return a, b, m

@@ -2537,10 +2537,73 @@ def sphere_prior_normal(view, params, offset, offset_inv, bone, wv, right_hand=T
     return A, g, cost, count, moments
 
 
+def _sphere_collision_args(J, dev, pairs, weight, name="weight"):
+    """(pair_a, pair_b, pair_min, K, weight): pairs = (a [K] int32, b [K] int32, m [K] fp32) on `dev`, or None (K = 0).
+    hand_model.collision_table validates the table where it is built; the entry skips a bad pair."""
+    weight = float(weight)
+    if not (weight >= 0.0 and weight < float("inf")):
+        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
+    if pairs is None:
+        return None, None, None, 0, weight
+    try:
+        a, b, m = pairs
+    except (TypeError, ValueError):
+        raise RuntimeError("pairs must be (a [K] int32, b [K] int32, min_dist [K] float32)")
+    _check_input(a, "pairs' a", torch.int32)
+    _check_input(b, "pairs' b", torch.int32)
+    _check_input(m, "pairs' min_dist")
+    K = a.shape[0] if a.dim() == 1 else -1
+    if K < 0 or tuple(b.shape) != (K,) or tuple(m.shape) != (K,) or any(t.device != dev for t in (a, b, m)):
+        raise RuntimeError("pairs must be three [K] tensors on the parameters' device")
+    if K > 4096:
+        raise RuntimeError("at most 4096 pairs, not %d" % K)
+    if K == 0:
+        return None, None, None, 0, weight
+    return a, b, m, K, weight
+
+
+def sphere_collision_normal(params, offset, offset_inv, bone, wv, right_hand=True, pairs=None, weight=1.0,
+                            accumulate_into=None):
+    """The normal equations of the sphere fit's collision term (include/spherehand_hip.h, shr_sphere_collision_normal):
+    params [B,26], the key-point tables of pose_keypoints_jacobian, pairs = (a [K] int32, b [K] int32, m [K] fp32), the
+    table of hand_model.collision_table (None: no pair) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32: the pairs
+    with rows, penetration [B,K] fp64: h = m - |c_a - c_b| at an active pair, 0 elsewhere).  A, g and cost carry `weight`;
+    count and penetration are the term's own.  The term is view-independent: it reads the model-frame keypoints.
+    accumulate_into = (A, g, cost) of the other terms at the same pose: weight x the term is ADDED to them in place (with
+    weight = 0 or no pair they are not touched) and they are the A, g, cost returned.  Two launches:
+    shr_pose_keypoints_jacobian -> shr_sphere_collision_normal."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv, "parameters")
+    dev = params.device
+    if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
+        raise RuntimeError("every tensor must be on the parameters' device")
+    pa, pb, pm, K, weight = _sphere_collision_args(J, dev, pairs, weight)
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+            _check_input(t, name, torch.float64)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        penetration = torch.empty((B, K), dtype=torch.float64, device=dev)
+        _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pa), _ptr(pb), _ptr(pm), weight, B, J, K,
+                                                   int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(cost), _ptr(count),
+                                                   _ptr(penetration) if K else None, None, _stream()),
+                   "shr_sphere_collision_normal")
+    return A, g, cost, count, penetration
+
+
 def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
                       pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
                       stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
-                      keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0):
+                      keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
+                      collision=None, collision_weight=0.0):
     """sphere_icp_render with the keypoint and joint-limit terms: `iters` Levenberg-Marquardt iterations on
     sphere_icp_render's energy + kp_weight sum w min(|k - c|, kp_max)^2 + limit_weight sum_i h_i^2, k the predicted
     keypoints [B,V,J,3] in each view's frame with confidence w [B,V,J] (None: 1), c the sphere centres in that frame, h_i the
@@ -2548,7 +2611,11 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     iters + 1 evaluations is sphere_icp_render's with shr_sphere_prior_normal(accumulate = 1) after the render entry, on
     torch's current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a
     graph.  With no weighted term (both weights 0, or neither keypoints nor limits) it issues no launch of the new entry:
-    sphere_icp_render bit for bit."""
+    sphere_icp_render bit for bit.
+    collision = (a [K] int32, b [K] int32, m [K] fp32), hand_model.collision_table's pairs, with collision_weight > 0 adds
+    collision_weight sum_k max(m_k - |c_a - c_b|, 0)^2 over the model-frame centres: shr_sphere_collision_normal
+    (accumulate = 1) after the prior entry in every evaluation.  Without a weighted collision term no launch of it is
+    issued and the loop is what it is without the two arguments, bit for bit."""
     B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
                                                     max_dist, "start parameters")
     max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
@@ -2556,6 +2623,9 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
                                                                        limits, limit_weight)
     priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
+    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
+                                                                           "collision_weight")
+    collide = K > 0 and collision_weight > 0.0
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
@@ -2577,6 +2647,7 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
         A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
         model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
         prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
         params, cost0, cost = f32(B, 26), f32(B), f32(B)
         ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
                               lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
@@ -2598,6 +2669,10 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
                                                        _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
                                                        limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
                                                        _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
+            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
+                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
+                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
             solve = int(it < iters)
             _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
                                             _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),

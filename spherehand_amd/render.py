@@ -1039,6 +1039,67 @@ class SpherePriorPoseFitter(SphereRenderPoseFitter):
                                        self.kp_weight, self.kp_max, limits, self.limit_weight, (A, g, cost))
 
 
+class SphereCollisionPoseFitter(SpherePriorPoseFitter):
+    """SpherePriorPoseFitter with the term a sphere-model tracker carries against self-penetration: `iters`
+    Levenberg-Marquardt iterations on
+        SpherePriorPoseFitter's energy + collision_weight sum_k max(m_k - |c_a - c_b|, 0)^2
+    over the reference's 690 sphere pairs (mesh/render.py:145-176; every finger sphere against the palm's and against the
+    other fingers'), c the sphere centres in the model frame and m_k the pair's minimum distance in mm
+    (ops.sphere_icp_priors with `collision`; include/spherehand_hip.h, shr_sphere_collision_normal).  The table is
+    hand_model.collision_table(mesh, min_dist, radius_scale): m_k = min_dist, the reference's constant 6 mm, or with
+    radius_scale m_k = min(radius_scale (r_a + r_b), the pair's distance at the rest pose) -- the shipped radii are a fat
+    proxy, so the plain radius sum is already violated at rest.
+        solve(observed, params0, view=None, prior=None, keypoints=None, confidence=None) -> (params, cost0, cost)
+        normal_equations(observed, params, view=None, keypoints=None, confidence=None)
+            -> (A, g, cost, count [B], penetration [B,690]) of the SUM of the five terms' A, g and cost; count (pairs with
+               rows) and penetration (h at an active pair, 0 elsewhere) are the new term's own
+    collision_weight = 0 is SpherePriorPoseFitter bit for bit.  The defaults come from DESIGN.md 4.4s's study, which also
+    says what the term does NOT fix: it keeps centres apart, not surfaces, it pushes along the line between two centres
+    whatever the image says, and poses the sampler itself produces have pairs under 6 mm.  Everything else is
+    SpherePriorPoseFitter's: a refinement from a start pose, NO autograd through the solve, the rotation NOT checked."""
+
+    # DESIGN.md 4.4s: the study's row
+    DEFAULT_COLLISION_WEIGHT = 1.0
+    DEFAULT_MIN_DIST = 6.0
+    DEFAULT_RADIUS_SCALE = None
+
+    def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
+                 fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None, max_resid=None,
+                 background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None, collision_weight=None,
+                 min_dist=None, radius_scale=None):
+        super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
+                         render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits)
+        from .hand_model import collision_table
+        self.collision_weight = float(self.DEFAULT_COLLISION_WEIGHT if collision_weight is None else collision_weight)
+        if not (self.collision_weight >= 0.0 and self.collision_weight < float("inf")):
+            raise ValueError("collision_weight must be finite and >= 0")
+        self.min_dist = float(self.DEFAULT_MIN_DIST if min_dist is None else min_dist)
+        self.radius_scale = self.DEFAULT_RADIUS_SCALE if radius_scale is None else float(radius_scale)
+        a, b, m = collision_table(mesh, self.min_dist, self.radius_scale)
+        self.register_buffer('pair_a', torch.from_numpy(a))
+        self.register_buffer('pair_b', torch.from_numpy(b))
+        self.register_buffer('pair_min', torch.from_numpy(m))
+
+    def _pairs(self):
+        return self.pair_a, self.pair_b, self.pair_min
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        return ops.sphere_icp_priors(observed, view, params0.detach().contiguous().float(), *self._tables(), self.right_hand,
+                                     self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                     None if prior is None else prior.detach().contiguous().float(), self.render_weight,
+                                     self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
+                                     limits, self.limit_weight, collision=self._pairs(), collision_weight=self.collision_weight)
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None):
+        params = params.detach().contiguous().float()
+        A, g, cost = SpherePriorPoseFitter.normal_equations(self, observed, params, view, keypoints, confidence)[:3]
+        return ops.sphere_collision_normal(params, *self._tables()[:4], self.right_hand, self._pairs(), self.collision_weight,
+                                           (A, g, cost))
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster

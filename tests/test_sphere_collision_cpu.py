@@ -1,0 +1,427 @@
+"""The collision term of the sphere fit without a device: the entries of the C ABI with their argument rules, the new unit's
+code-object metadata, the pair table against the reference's, the restatement (tests/sphere_collision_ref.py) and what keeps
+it honest -- its g is the reverse-mode gradient of 1/2 cost, A and g of the header's chains equal the row-wise sums, the
+hinge at its kink -- the fp32 bars the GPU tests (tests/test_sphere_collision_gpu.py) hold the kernel to, and the study's
+claim on the crossed family."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import pose_icp_ref as ref
+import sphere_collision_ref as cref
+import sphere_icp_ref as sref
+import sphere_prior_ref as pref
+from conftest import ROOT
+from test_pose_ik_cpu import _metadata
+
+ENTRIES = ("shr_sphere_collision_normal_workspace_bytes", "shr_sphere_collision_normal")
+
+# The fp32 bars, by DESIGN.md 4.4p's method: the restatement run with an fp32 chain against the fp64 one on the GPU tests'
+# inputs (EVALUATIONS below), the largest deviation per quantity; the GPU tolerance is 4 x that.  A and g are compared GIVEN
+# THE SAME model-frame centres (the fp64 run's, rounded once), so that both runs hold the same pairs, the same h and the
+# same u, as the kernel and the restatement do: what differs is the Jacobian, the fp32 chain's against the fp64 chain's
+# (sphere_collision_ref.given on each).  The autograd figure is g by reverse mode through the fp32 chain against the fp64
+# run's g, each on its OWN centres: at a pair 6 mm apart a centre's 1e-5 mm turns u by 2e-6.  test_fp32_bars measures them
+# again and holds the constants to within [1/2, 2].
+FP32_A_DEVIATION = 4.69e-7        # max |A32 - A64| / max |A64| per sample with rows, at the cases' params0
+FP32_G_DEVIATION = 1.65e-6        # max |g32 - g64| / max |g64| per sample with rows
+FP32_AUTOGRAD_DEVIATION = 5.76e-6 # g by REVERSE mode through the fp32 chain (what ops.PoseSpheres' backward is) against g64
+FP32_COST_DEVIATION = 1.01e-6     # |cost32 - cost64| / cost64 of the two runs' own centres, the combined cost at params0
+FP32_STEP_DEVIATION = 1.48e-5     # rad | mm: the first step of the combined fit at params0
+FP32_POSE_DEVIATION = 3.27e-5     # rad | mm: the final pose of the end-to-end case, the samples that keep the sequence
+# Between the kernel and the numpy chain GIVEN the entry's own centres and Jacobian nothing is left but the order of at
+# most 690 fp64 terms per entry: 690 x 2^-53 = 7.7e-14 of the sum of the magnitudes, hence 1e-13 of the largest entry.
+ORDER_BAR = 1e-13
+A_BAR, G_BAR, AUTOGRAD_BAR, COST_BAR, STEP_BAR, POSE_BAR = (4 * FP32_A_DEVIATION, 4 * FP32_G_DEVIATION,
+                                                            4 * FP32_AUTOGRAD_DEVIATION, 4 * FP32_COST_DEVIATION,
+                                                            4 * FP32_STEP_DEVIATION, 4 * FP32_POSE_DEVIATION)
+WEIGHT, MIN_DIST, RADIUS_SCALE = cref.DEFAULT_COLLISION_WEIGHT, cref.DEFAULT_MIN_DIST, cref.DEFAULT_RADIUS_SCALE
+KP_WEIGHT, KP_MAX, LIMIT_WEIGHT = pref.DEFAULT_KP_WEIGHT, pref.DEFAULT_KP_MAX, pref.DEFAULT_LIMIT_WEIGHT
+# The evaluations the GPU test of the equations runs and the bars are measured on: (case, samples, table, weight); the
+# tables are sphere_collision_ref.tables(): 6 mm, 0.5 (r_a + r_b), 1.0 (r_a + r_b), and `all` (every pair active).
+EVALUATIONS = (("right", 5, "6mm", 1.0), ("left", 5, "0.5", 0.25), ("right", 3, "1.0", 2.0), ("left", 4, "1.0", 1.0),
+               ("crossed", 5, "6mm", 1.0), ("crossed", 5, "1.0", 0.5), ("right", 3, "all", 1.0))
+
+
+@pytest.fixture(scope="module")
+def mesh():
+    from spherehand_amd import hand_model
+    return hand_model.load_mesh()
+
+
+def test_header_loader_and_library_have_the_entries():
+    from spherehand_amd import _lib, build
+    text = open(os.path.join(ROOT, "include", "spherehand_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    h = ctypes.CDLL(build.build())
+    for name in ENTRIES:
+        assert re.search(r"\b%s\s*\(" % name, src), name
+        assert name in _lib.SIGNATURES and hasattr(h, name), name
+    contract = text[text.index("The term against self-penetration of the sphere fit"):
+                    text.index("long long shr_sphere_collision_normal_workspace_bytes(")]
+    for cite in ("mesh/render.py:145-176", "no counterpart", "NOT the square", "PER-PAIR", "MODEL-frame", "SKIPPED",
+                 "out of bounds", "exactly equal to m is not active", "a NaN never\n *       fires", "coincident", "ONE row",
+                 "Swapping a and b", "whatever the weight", "LOWER triangle", "bit-symmetric", "not touched", "ascending k",
+                 "no atomics", "nothing contracted", "4096", "65535", "accumulate == 1", "K > 0 without them"):
+        assert cite in contract, cite
+    assert text.index("shr_sphere_prior_normal(") < text.index("shr_sphere_collision_normal(")     # after the prior section
+    lib = _lib.lib()
+    assert lib.shr_abi_version() == _lib.ABI_VERSION == 23
+    ws = lib.shr_sphere_collision_normal_workspace_bytes
+    assert ws(3, 41, 690) == 0 and ws(0, 0, 0) == 0 and ws(65535, 64, 4096) == 0              # no workspace is needed
+    for k in range(3):
+        bad = [1, 41, 690]
+        bad[k] = -1
+        assert ws(*bad) == -1
+    # host-side argument rules (every call below returns before a launch)
+    P = 1 << 20                                                    # a 16-byte aligned stand-in for a device address
+    #          0 centres 1 jac 2 pair_a 3 pair_b 4 pair_min | 5 weight | 6 B 7 J 8 K 9 accumulate |
+    #          10 A 11 g 12 cost 13 count 14 penetration 15 workspace 16 stream
+    normal = [P] * 5 + [1.0, 2, 41, 690, 1] + [P] * 6 + [None]
+    bad = lambda i, val: lib.shr_sphere_collision_normal(*(normal[:i] + [val] + normal[i + 1:]))   # noqa: E731
+    assert bad(6, 0) == 0                                          # B == 0: nothing to do
+    required, optional = [0, 1, 10, 11, 12, 13], [14, 15]
+    for i in required:
+        assert bad(i, None) == -1, i
+    for i in required + optional + [2, 3, 4]:
+        assert bad(i, P + 2) == -1, i
+    for i in (0, 15, 10, 11, 12, 14):                              # centres, workspace: 16 bytes; A, g, cost, penetration: 8
+        assert bad(i, P + 4) == -1, i
+    for i in (0, 15):
+        assert bad(i, P + 8) == -1, i
+    for i in (6, 7, 8):
+        assert bad(i, -1) == -1, i
+    assert bad(7, 0) == -1                                         # 1 <= J
+    inf, nan = float("inf"), float("nan")
+    assert bad(5, -0.5) == -1 and bad(5, inf) == -1 and bad(5, nan) == -1      # the weight: finite and >= 0
+    assert bad(9, 2) == -1 and bad(9, -1) == -1                    # accumulate 0 or 1
+    for i in (2, 3, 4):                                            # the three pair arrays: all or none
+        assert bad(i, None) == -1, i
+    assert bad(6, 65536) == -2 and bad(7, 65) == -2 and bad(8, 4097) == -2
+    none = list(normal)
+    none[6], none[7] = 0, 0                                        # the rules come before the no-op
+    assert lib.shr_sphere_collision_normal(*none) == -1
+    none[7] = 65
+    assert lib.shr_sphere_collision_normal(*none) == -2
+    none[7], none[5] = 41, -1.0
+    assert lib.shr_sphere_collision_normal(*none) == -1
+    none[5], none[3] = 0.0, None
+    assert lib.shr_sphere_collision_normal(*none) == -1
+    none[2], none[4] = None, None                                  # K > 0 without a table
+    assert lib.shr_sphere_collision_normal(*none) == -1
+    none[8] = 0                                                    # no table and K == 0: the no-op
+    assert lib.shr_sphere_collision_normal(*none) == 0
+    assert lib.shr_sphere_collision_normal(*([None] * 5 + [0.0, 0, 1, 0, 0] + [None] * 7)) == 0
+
+
+def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
+    """sphere_collision.hip: one kernel, no scratch, no spills, no atomics.  A workgroup of 256 threads holds the 192 x 26 fp32
+    Jacobian, 64 centres, a chunk's 256 compacted pairs (32 + 4 bytes each), the 64 x 26 fp64 rows of a group of them and the
+    waves' totals in LDS: 43 552 bytes.
+    DESIGN.md 4.4s tables the figures.  The unit includes common.h alone."""
+    sizes, kernels = _metadata("sphere_collision", tmp_path)
+    assert sizes == [0] and len(kernels) == 1
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("### 4.4s"):design.index("### 4.5 ")]
+    assert design.index("### 4.4r") < design.index("### 4.4s")
+    for name, k in kernels.items():
+        print(name, k)
+        assert "sphere_collision_kernel" in name and "sphere_collision_kernel" in section
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0
+        assert k["group_segment_fixed_size"] == 256 * 32 + 64 * 26 * 8 + 192 * 26 * 4 + 64 * 16 + 256 * 4 + 2 * 4 * 4 == 43552
+        assert k["vgpr_count"] <= 64 and k["sgpr_count"] <= 106
+    assert "43 552" in section
+    unit = open(os.path.join(ROOT, "spherehand_amd", "csrc", "sphere_collision.hip")).read()
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["common.h"]
+    assert "atomic" not in unit.lower()
+
+
+def test_collision_table(mesh):
+    """hand_model.collision_table: the pairs are the reference's (tests/golden/g7_network.npz, collision_pairs); m is the
+    constant by default; with radius_scale it is capped at the rest distance, so that the rest pose -- which has 26 pairs
+    closer than r_a + r_b, the worst at 0.70 of it -- has no active pair; bad arguments are refused where it is built."""
+    from spherehand_amd import hand_model
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "g7_network.npz"))["collision_pairs"]
+    a, b, m = hand_model.collision_table(mesh)
+    assert a.dtype == b.dtype == np.int32 and m.dtype == np.float32 and len(a) == 690
+    assert np.array_equal(np.stack([a, b]), gold) and bool((m == np.float32(6.0)).all())
+    assert bool((hand_model.collision_table(mesh, 4.5)[2] == np.float32(4.5)).all())
+    model = sref.Spheres(mesh, None, True)
+    rest = torch.zeros(1, 26, dtype=torch.float64)
+    radii = model.radii.astype(np.float64)
+    full = cref.decide(model.centres(rest).float().numpy(), cref.scaled(mesh, 1.0))
+    print("rest pose: %d pairs under r_a + r_b, the worst at %.3f of it" % (full["active"].sum(), (full["n"][0] / (radii[a] + radii[b])).min()))
+    assert int(full["active"].sum()) == 26 and abs((full["n"][0] / (radii[a] + radii[b])).min() - 0.70) < 0.005
+    for dtype in (torch.float64, torch.float32):
+        for scale in (0.5, 1.0, 2.0):
+            a2, b2, m2 = hand_model.collision_table(mesh, radius_scale=scale)
+            assert np.array_equal(a2, a) and np.array_equal(b2, b) and bool((m2 > 0).all())
+            assert bool((m2 <= np.float32(scale) * (model.radii[a] + model.radii[b]) * (1 + 1e-6)).all())
+            d = cref.decide(model.to(dtype).centres(rest.to(dtype)).float().numpy(), (a2, b2, m2))
+            assert int(d["active"].sum()) == 0, (dtype, scale)
+    assert int((hand_model.collision_table(mesh, radius_scale=1.0)[2] < model.radii[a] + model.radii[b]).sum()) == 26
+    for bad in (dict(min_dist=0.0), dict(min_dist=-1.0), dict(min_dist=float("nan")), dict(radius_scale=0.0),
+                dict(radius_scale=float("inf"))):
+        with pytest.raises(ValueError):
+            hand_model.collision_table(mesh, **bad)
+
+
+def test_crossed_starts_have_active_pairs(mesh):
+    """Every one of the crossed family's 20 starts has an active pair at 6 mm that p* does not have; which parameter is
+    moved, and how far, is printed (DESIGN.md 4.4s has the table)."""
+    model = sref.Spheres(mesh, None, True)
+    p, p0 = cref.study_poses("crossed", mesh)
+    param, shift = cref.crossed_shifts(mesh)
+    six = cref.table(mesh)
+    pen0, act0 = cref.penetration(model, p0, six)
+    pen, act = cref.penetration(model, p, six)
+    print("parameter %s\nshift %s\nactive pairs at the starts %s (p*: %s), penetration %s mm"
+          % (param.tolist(), np.round(shift, 2).tolist(), act0.tolist(), act.tolist(), np.round(pen0.numpy(), 2).tolist()))
+    assert int(act0.min()) >= 1 and bool((pen0 >= pen + 0.5 - 1e-9).all())
+    assert int((param == 14).sum()) == 19 and int((param == 18).sum()) == 1 and float(np.abs(shift).max()) <= 2.0
+    moved = (p0 - p) != 0
+    assert bool((moved.sum(1) == 1).all()) and bool(moved[torch.arange(20), torch.as_tensor(param)].all())
+
+
+def evaluation_inputs(mesh, name, rows):
+    case = cref.case(mesh, name)
+    return case, case["params0"][:rows].float().double()
+
+
+def test_g_is_the_autograd_gradient(mesh):
+    """g of the restatement (rows by forward mode) = the reverse-mode gradient of 1/2 cost through pose_ik_ref.Chain, to
+    1e-12 of its largest entry; A is symmetric and positive semi-definite; the count is the rows'."""
+    tabs = cref.tables(mesh)
+    for name, rows, tab, w in EVALUATIONS:
+        case, p = evaluation_inputs(mesh, name, rows)
+        m = case["model"]
+        n = cref.normal(m, p, tabs[tab], w, chain_residual=True)
+        q = p.clone().requires_grad_(True)
+        cost = cref.energy(m, q, tabs[tab], w, held=n["decided"]["active"])
+        (0.5 * cost.sum()).backward()
+        err, scale = (q.grad - n["g"]).abs().max().item(), n["g"].abs().max().item()
+        print("%s, table %s: pairs with rows %s; |g - autograd| %.3g of %.3g; |cost - energy| %.3g"
+              % (name, tab, n["count"].tolist(), err, scale, (cost.detach() - n["cost"]).abs().max().item()))
+        if tab in ("1.0", "all"):
+            assert int(n["count"].min()) > 3
+        if name == "crossed":
+            assert int(n["count"].min()) >= 1
+        assert err <= 1e-12 * scale
+        assert torch.allclose(cost.detach(), n["cost"], rtol=1e-13, atol=0)
+        A = n["A"]
+        assert torch.allclose(A, A.transpose(1, 2), rtol=0, atol=1e-9 * max(A.abs().max().item(), 1e-300))
+        assert bool((torch.linalg.eigvalsh(0.5 * (A + A.transpose(1, 2)))[:, 0] >= -1e-9 * A.abs().max()).all())
+        contract = cref.normal(m, p, tabs[tab], w)
+        assert torch.equal(contract["count"], n["count"])
+        if scale > 0:
+            dev = (contract["g"] - n["g"]).abs().max().item() / scale
+            print("    the contract's h (on the fp32 centres) against the chain's: g differs by %.3g" % dev)
+            assert dev < 1e-5
+
+
+def test_chains_give_the_row_sums(mesh):
+    """A and g of the header's chains (sphere_collision_ref.chain: k ascending, operation for operation) equal the row-wise
+    sums formed by a matrix product (given) to 1e-13 of the largest entry, and the restatement's (rows by forward mode
+    through the fp64 chain, whose Jacobian the two are given) to 1e-6: the sign convention is d h / d params.  A is
+    bit-symmetric; swapping a and b changes no bit; the cost and the penetration are the pairs' own."""
+    tabs = cref.tables(mesh)
+    for name, rows, tab, w in EVALUATIONS:
+        case, p = evaluation_inputs(mesh, name, rows)
+        m = case["model"]
+        _, jac = m.chain.jacobian(p)
+        c32, j32 = m.centres(p).float().numpy(), jac.float().numpy()
+        A, g, cost, count, pen = cref.chain(c32, j32, tabs[tab], w)
+        A2, g2 = cref.given(c32, j32, tabs[tab], w)
+        n = cref.normal(m, p, tabs[tab], w, centres32=c32)
+        assert np.array_equal(A, A.transpose(0, 2, 1)) and np.array_equal(count, n["count"].numpy())
+        sa, sg = max(np.abs(A).max(), 1e-300), max(np.abs(g).max(), 1e-300)
+        print("%s, table %s: rows %s; chains against the row sums: A %.3g, g %.3g; against the restatement: A %.3g, g %.3g"
+              % (name, tab, count.tolist(), np.abs(A - A2.numpy()).max() / sa, np.abs(g - g2.numpy()).max() / sg,
+                 np.abs(A - n["A"].numpy()).max() / sa, np.abs(g - n["g"].numpy()).max() / sg))
+        assert np.abs(A - A2.numpy()).max() <= ORDER_BAR * sa and np.abs(g - g2.numpy()).max() <= ORDER_BAR * sg
+        assert np.abs(A - n["A"].numpy()).max() <= 1e-6 * sa and np.abs(g - n["g"].numpy()).max() <= 1e-6 * sg
+        assert np.allclose(cost, n["cost"].numpy(), rtol=1e-13, atol=0) and np.array_equal(pen, n["penetration"].numpy())
+        a, b, mm = tabs[tab]
+        for x, y in zip(cref.chain(c32, j32, (b, a, mm), w), (A, g, cost, count, pen)):
+            assert np.array_equal(x, y)
+
+
+def test_hinge_at_its_kink():
+    """Two centres (3, 4, 0) apart, exactly 5 in fp32 and fp64: inactive at m = 5 (the reference's relu at its kink) and at
+    the fp32 below, active at the next fp32 above with h = m - 5 exactly.  Coincident centres pay m^2 and give no row; a NaN
+    centre, a NaN or non-positive m, an index out of range and a == b give no term; nothing is read for a skipped pair."""
+    c = np.zeros((1, 4, 4), np.float32)
+    c[0, 0, :3], c[0, 1, :3], c[0, 3, :3] = (1.0, 2.0, 3.0), (4.0, 6.0, 3.0), (np.nan, 0.0, 0.0)
+    c[0, 2] = c[0, 0]
+    up, down = np.nextafter(np.float32(5.0), np.float32(6.0)), np.nextafter(np.float32(5.0), np.float32(4.0))
+    a = np.array([0, 0, 0, 0, 0, 1, -1, 4, 2, 0, 0], np.int32)
+    b = np.array([1, 1, 1, 2, 3, 0, 1, 1, 2, 1, 1], np.int32)
+    m = np.array([5.0, up, down, 6.0, 100.0, up, 9.0, 9.0, 9.0, np.nan, 0.0], np.float32)
+    d = cref.decide(c, (a, b, m))
+    assert d["valid"].tolist() == [True] * 6 + [False] * 5
+    assert d["active"][0].tolist() == [False, True, False, True, False, True] + [False] * 5
+    assert d["rowed"][0].tolist() == [False, True, False, False, False, True] + [False] * 5
+    assert d["n"][0, 0] == 5.0 and d["h"][0, 1] == np.float64(up) - 5.0 > 0 and d["h"][0, 3] == 6.0 and d["h"][0, 4] == 0.0
+    assert np.array_equal(d["u"][0, 1], [-0.6, -0.8, 0.0]) and np.array_equal(d["u"][0, 5], [0.6, 0.8, 0.0])
+    jac = np.random.default_rng(0).standard_normal((1, 12, 26)).astype(np.float32)
+    A, g, cost, count, pen = cref.chain(c, jac, (a, b, m), 2.0)
+    assert count.tolist() == [2] and cost[0] == 2.0 * ((d["h"][0, 1] * d["h"][0, 1] + 36.0) + d["h"][0, 5] * d["h"][0, 5])
+    only = cref.chain(c, jac, (a[[1, 5]], b[[1, 5]], m[[1, 5]]), 2.0)
+    assert np.array_equal(A, only[0]) and np.array_equal(g, only[1]) and np.any(g != 0)
+    alone = cref.chain(c, jac, (a[[3]], b[[3]], m[[3]]), 2.0)                  # coincident centres alone: the cost, no row
+    assert alone[2][0] == 72.0 and alone[3].tolist() == [0] and not alone[0].any() and not alone[1].any()
+
+
+def test_ops_refuse_what_the_kernels_do_not_take(mesh):
+    """No device here: the ops refuse CPU tensors and bad scalars with a RuntimeError; the module's table and defaults."""
+    from spherehand_amd import hand_model, ops
+    from spherehand_amd.render import SphereCollisionPoseFitter, SpherePriorPoseFitter
+    fit = SphereCollisionPoseFitter(mesh, 48, 40, stiffness=ref.STIFFNESS)
+    base = SpherePriorPoseFitter(mesh, 48, 40, stiffness=ref.STIFFNESS)
+    assert isinstance(fit, SpherePriorPoseFitter) and fit.kp_weight == base.kp_weight and fit.limit_weight == base.limit_weight
+    assert fit.collision_weight == SphereCollisionPoseFitter.DEFAULT_COLLISION_WEIGHT == WEIGHT
+    assert fit.min_dist == SphereCollisionPoseFitter.DEFAULT_MIN_DIST == MIN_DIST
+    assert fit.radius_scale == SphereCollisionPoseFitter.DEFAULT_RADIUS_SCALE == RADIUS_SCALE
+    a, b, m = hand_model.collision_table(mesh, MIN_DIST, RADIUS_SCALE)
+    assert np.array_equal(fit.pair_a.numpy(), a) and np.array_equal(fit.pair_b.numpy(), b) and np.array_equal(fit.pair_min.numpy(), m)
+    scaled = SphereCollisionPoseFitter(mesh["bones"], 48, 40, radius_scale=0.75)
+    assert np.array_equal(scaled.pair_min.numpy(), hand_model.collision_table(mesh, radius_scale=0.75)[2])
+    for word in ("SpherePriorPoseFitter", "NO autograd", "NOT checked", "4.4s", "collision_table", "mesh/render.py:145-176",
+                 "bit for bit"):
+        assert word in SphereCollisionPoseFitter.__doc__, word
+    assert "Collision" in SpherePriorPoseFitter.__doc__
+    for bad in (dict(collision_weight=-1.0), dict(collision_weight=float("inf")), dict(collision_weight=float("nan")),
+                dict(min_dist=0.0), dict(radius_scale=-1.0)):
+        with pytest.raises(ValueError):
+            SphereCollisionPoseFitter(mesh, 48, 40, **bad)
+    obs, view, p0 = torch.full((2, 1, 40, 48), 100.0), torch.eye(4).expand(2, 1, 4, 4).contiguous(), torch.zeros(2, 26)
+    tables = (fit.fk.offset, fit.fk.offset_inv, fit.kp_bone, fit.kp_wv, fit.radii)
+    pairs = (fit.pair_a, fit.pair_b, fit.pair_min)
+    for call in (lambda: fit.solve(obs, p0, view), lambda: fit.normal_equations(obs, p0, view),
+                 lambda: ops.sphere_collision_normal(p0, *tables[:4], pairs=pairs),
+                 lambda: ops.sphere_collision_normal(p0, *tables[:4], pairs=pairs, weight=-1.0),
+                 lambda: ops.sphere_icp_priors(obs, view, p0, *tables, collision=pairs, collision_weight=float("inf")),
+                 lambda: ops.sphere_icp_priors(obs, view, p0, *tables, collision=pairs, collision_weight=float("nan")),
+                 lambda: ops.sphere_icp_priors(obs, view, p0, *tables, collision=pairs[:2], collision_weight=1.0)):
+        with pytest.raises(RuntimeError):
+            call()
+
+
+_RUNS = {}
+
+
+def end_to_end_runs(case):
+    """dtype -> sphere_collision_ref.solve of the end-to-end case with the module's defaults, once per process (the GPU
+    tests run the same)."""
+    if "runs" not in _RUNS:
+        p0 = case["params0"].float().double()
+        _RUNS["runs"] = {dt: cref.solve(case["model"].to(dt), case["view"], case["observed"], p0, case["p2m"], case["table"], WEIGHT,
+                                        cref.END_TO_END_ITERS, 1e-3, case["stiffness"], keypoints=case["keypoints"],
+                                        confidence=case["confidence"], kp_weight=KP_WEIGHT, kp_max=KP_MAX, lower=case["lower"],
+                                        upper=case["upper"], limit_weight=LIMIT_WEIGHT)
+                         for dt in (torch.float64, torch.float32)}
+    return _RUNS["runs"]
+
+
+def kept(lm64, lm32):
+    """[B] bool: the samples on which the two runs keep the same accept sequence, the same active pairs and the same active
+    hinge rows in every evaluation."""
+    same = (torch.stack(lm64.history) == torch.stack(lm32.history)).all(0)
+    for a, b in zip(lm64.actives, lm32.actives):
+        same &= (a == b).all(1)
+    for a, b in zip(lm64.hinges, lm32.hinges):
+        same &= (a == b).all(1)
+    return same
+
+
+def fp32_deviations(mesh):
+    """The figures, measured: (A, g, autograd, cost, step, pose); `same`: the samples of the end-to-end case the fp32 run
+    keeps."""
+    dev = dict(A=0.0, g=0.0, autograd=0.0, cost=0.0, step=0.0, pose=0.0)
+    tabs = cref.tables(mesh)
+    for name, rows, tab, w in EVALUATIONS:
+        case, p = evaluation_inputs(mesh, name, rows)
+        m64, m32 = case["model"], case["model"].to(torch.float32)
+        held = m64.centres(p).float().numpy()
+        a = cref.normal(m64, p, tabs[tab], w, centres32=held)
+        (A64, g64r), (A32, g32r) = (cref.given(held, m.chain.jacobian(p)[1].numpy(), tabs[tab], w) for m in (m64, m32))
+        live = a["count"] > 0
+        if bool(live.any()):
+            dev["A"] = max(dev["A"], ((A64 - A32).abs().amax((1, 2))[live] / A64.abs().amax((1, 2))[live]).max().item())
+            dev["g"] = max(dev["g"], ((g64r - g32r).abs().amax(1)[live] / g64r.abs().amax(1)[live]).max().item())
+            q = p.float().clone().requires_grad_(True)                   # reverse mode through the fp32 chain
+            (0.5 * cref.energy(m32, q, tabs[tab], w, held=a["decided"]["active"]).sum()).backward()
+            g64 = cref.normal(m64, p, tabs[tab], w, chain_residual=True)["g"]
+            dev["autograd"] = max(dev["autograd"], ((q.grad.double() - g64).abs().amax(1)[live] / g64.abs().amax(1)[live]).max().item())
+        print("%s table %s: rows %s; A %.3g, g %.3g, autograd %.3g so far" % (name, tab, a["count"].tolist(), dev["A"], dev["g"], dev["autograd"]))
+    for name in ("crossed", "left"):                                             # the combined fit's first step, own centres
+        case = cref.case(mesh, name)
+        view, obs, p, p2m, mu = case["view"], case["observed"], case["params0"].float().double(), case["p2m"], case["stiffness"]
+        steps, costs = [], []
+        for m in (case["model"], case["model"].to(torch.float32)):
+            A, g, cost, _ = cref.combined(m, view, obs, p, p2m, tabs["6mm"], WEIGHT, keypoints=case["keypoints"],
+                                          confidence=case["confidence"], kp_weight=KP_WEIGHT, kp_max=KP_MAX, lower=case["lower"],
+                                          upper=case["upper"], limit_weight=LIMIT_WEIGHT)
+            lm = ref.LM(p, 1e-3, m.dtype)
+            steps.append(lm.step(A, g, cost, p, None, mu, True) - p)
+            costs.append(cost)
+        dev["cost"] = max(dev["cost"], ((costs[0] - costs[1]).abs() / costs[0]).max().item())
+        dev["step"] = max(dev["step"], (steps[0] - steps[1]).abs().max().item())
+        print("%s: cost %.3g, step %.3g so far" % (name, dev["cost"], dev["step"]))
+    run = end_to_end_runs(cref.case(mesh, "crossed"))
+    (q64, _, _, lm64), (q32, _, _, lm32) = run[torch.float64], run[torch.float32]
+    same = kept(lm64, lm32)
+    print("end_to_end (seed %d): the fp32 run keeps the accept sequence, the active pairs and the hinge rows: %s; |pose32 - pose64| "
+          "%s; active pairs per evaluation %s" % (cref.END_TO_END_SEED, same.tolist(), (q64 - q32).abs().amax(1).tolist(),
+                                                  [a.sum(1).tolist() for a in lm64.actives]))
+    dev["pose"] = (q64 - q32)[same].abs().max().item() if bool(same.any()) else float("nan")
+    return dev, same
+
+
+def test_fp32_bars(mesh):
+    """The constants above, measured again.  The fp32 / fp64 CPU pair keeps at least four of the five samples of the
+    end-to-end case (seed END_TO_END_SEED of 21 .. 24, the crossed family's poses 5 (seed - 21) ...); the term is active
+    inside the loop; the fit's cost falls on every sample."""
+    dev, same = fp32_deviations(mesh)
+    print("fp32 against fp64: A %.3g, g %.3g, autograd %.3g, cost %.3g, step %.3g, pose %.3g; same %s"
+          % (dev["A"], dev["g"], dev["autograd"], dev["cost"], dev["step"], dev["pose"], same.tolist()))
+    assert int(same.sum()) >= 4
+    _, cost0, cost, lm = end_to_end_runs(cref.case(mesh, "crossed"))[torch.float64]
+    assert bool((cost <= cost0).all()) and bool((lm.actives[0].sum(1) >= 1).all())
+    for name, const in (("A", FP32_A_DEVIATION), ("g", FP32_G_DEVIATION), ("autograd", FP32_AUTOGRAD_DEVIATION),
+                        ("cost", FP32_COST_DEVIATION), ("step", FP32_STEP_DEVIATION), ("pose", FP32_POSE_DEVIATION)):
+        assert const / 2 <= dev[name] <= 2 * const, (name, dev[name], const)
+
+
+def test_term_reduces_the_penetration_on_the_crossed_family(mesh):
+    """DESIGN.md 4.4s's claim on the crossed family (one finger's abduction moved into its neighbour at the start), one view,
+    keypoints with sigma_k = 5 mm, 4.4r's defaults for the other terms and the module's defaults for this one: the 6 mm
+    penetration summed over the 20 poses after the fit is smaller with the term than with collision_weight = 0 -- the
+    parent's energy.  Both are computed here."""
+    import pose_icp_views_ref as vref
+    import sphere_render_icp_ref as rref
+    model = sref.Spheres(mesh, None, True)
+    p, p0 = cref.study_poses("crossed", mesh)
+    view = vref.views(p.shape[0], ("identity",))
+    p2m = ref.grid(48, 40)
+    obs = rref.render64(model, view, p, 48, 40, p2m)
+    lo, hi = pref.limits()
+    k = pref.targets(model, view, p, 5.0, seed=3)
+    mu = torch.as_tensor(ref.STIFFNESS)
+    tab = cref.table(mesh, MIN_DIST, RADIUS_SCALE)
+    six = cref.table(mesh, 6.0)
+    pens = {}
+    for name, w in (("with", WEIGHT), ("without", 0.0)):
+        q, _, _, _ = cref.solve(model, view, obs, p0, p2m, tab, w, 10, 1e-3, mu, keypoints=k, confidence=None, kp_weight=KP_WEIGHT,
+                                kp_max=KP_MAX, lower=lo, upper=hi, limit_weight=LIMIT_WEIGHT)
+        pen, act = cref.penetration(model, q, six)
+        pens[name] = pen.sum().item()
+        err = sref.keypoint_error(model, q, p)
+        print("%s the collision term: 6 mm penetration after the fit %.3f mm over the 20 poses (%d active pairs; at the start "
+              "%.3f mm), mean keypoint error %.3f mm" % (name, pens[name], int(act.sum()), cref.penetration(model, p0, six)[0].sum(),
+                                                         err.mean()))
+    assert WEIGHT > 0 and pens["with"] < pens["without"]
