@@ -1359,6 +1359,92 @@ int shr_sphere_collision_normal(const float *centres   /* [B,J,4]: shr_pose_keyp
                                 double *A, double *g, double *cost, int32_t *count /* [B] */,
                                 double *penetration /* [B,K] or NULL */, void *workspace, void *stream);
 
+/* A sequence of frames fitted jointly: the temporal term and the block-tridiagonal step ----------------------------------------
+ * Every sample of the entries above is an island, and the data is video.  The reference carries the term for that as
+ * TemporalSmoothnessLoss (network/util_modules.py:360-381), ClampedL2lLoss(2500) (network/util_modules.py:349-358) between
+ * the joints of consecutive samples, weight 1.0 in MultiTaskLoss (create_network_and_criterion.py:242-245).  A row of it
+ * couples frame t and frame t + 1, so the normal equations of a sequence are block-TRIDIAGONAL and the accept decision
+ * belongs to the sequence, not the frame: shr_pose_lm_step cannot take it.  The reference has no counterpart of the normal
+ * equations or of the solve.  Two departures from the reference, both deliberate: it clamps every COMPONENT of the
+ * difference at +-2500 before squaring, the term here truncates the squared NORM of a sphere's difference at ts_max^2
+ * (section 4.4r's kp_max rule; with ts_max = +inf and at hand scale, where no component reaches 2500 mm, the two energies
+ * agree up to the reference's mean over elements); and it DETACHES the previous frame, a one-sided pull of frame t + 1
+ * towards frame t, while the Gauss-Newton term is SYMMETRIC: both frames of a pair receive rows.
+ * Layout: B = S T frames, S sequences of T consecutive frames, the frames of a sequence adjacent in the batch; frame b is
+ * frame t = b mod T of sequence b / T.  One evaluation of the fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_normal
+ *     -> shr_sphere_render_normal(accumulate = 1) -> shr_sphere_prior_normal(accumulate = 1)
+ *     -> shr_sphere_collision_normal(accumulate = 1) -> shr_sphere_temporal_normal(accumulate = 1) -> shr_pose_lm_seq_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_sphere_temporal_normal   the normal equations of 1/2 w sum min(n2, ts_max^2) with respect to the 26 T parameters
+ *       of a sequence.  keypoints[B,J,4] and jac[B,3J,26]: shr_pose_keypoints_jacobian's outputs for the trial poses, in
+ *       the MODEL frame (component 3 is not read): no view enters.  frame_weight[B] or NULL (1): entry t weighs the pair
+ *       (t, t + 1); the last entry of a sequence is not read.  A pair whose weight is not > 0 (0, negative, a NaN) has no
+ *       term.  w of a pair = (double)temporal_weight (double)frame_weight.
+ *       The term.  Per pair (t, t + 1) with a weight and per sphere j, in fp64 from the fp32 values:
+ *       e = c_j(t + 1) - c_j(t), n2 = (e0 e0 + e1 e1) + e2 e2.  A NaN n2 gives NO term: no cost, no row.  Otherwise the
+ *       cost term is min(n2, cap2), cap2 = (double)ts_max (double)ts_max, and the sphere gives THREE rows iff n2 < cap2: a
+ *       difference of exactly ts_max is saturated, +inf never saturates, and e = 0 still gives rows.  The row of axis a
+ *       has +jac[3j + a, :] of frame t + 1 in frame t + 1's columns and -jac[3j + a, :] of frame t in frame t's; its
+ *       residual is e_a.
+ *       -> A[B,26,26], the DIAGONAL blocks: frame b receives w_prev P + w_next N, P and N the sums of Jc_j(b)^T Jc_j(b) over
+ *       the spheres with rows of the pair before it and of the pair after it.  g[B,26], the gradient of 1/2 the cost in
+ *       the family's convention, so that the entries' A and g add: w_prev sum Jc_j(b)^T e_j(prev) + w_next (0 - sum
+ *       Jc_j(b)^T e_j(next)).  cost[B]: the pair's cost w sum_j min(n2, cap2) belongs to its LATER frame, t + 1.
+ *       count[B] int32: the spheres with rows of the pair (t, t + 1), stored at t + 1, 0 at the first frame of a
+ *       sequence; whatever temporal_weight.
+ *       -> E[B,26,26], the OFF-DIAGONAL blocks, ALWAYS WRITTEN, NEVER accumulated: E_t couples frame t (rows) with frame
+ *       t + 1 (columns), E_t = 0 - w sum_j Jc_j(t)^T Jc_j(t + 1).  It is an exact +0 for the last frame of every sequence,
+ *       for a pair without a weight, and for every frame when temporal_weight == 0.
+ *       accumulate == 0: A, g, cost = the term's (exact +0 where a frame has no weighted pair).  accumulate == 1: the
+ *       term is ADDED, one product per pair and one sum per entry on top of what the buffers hold; the LOWER triangle of
+ *       A is read and the sum written to both triangles, so A stays bit-symmetric; a frame none of whose pairs has a
+ *       weight -- every frame when temporal_weight == 0 or T == 1 -- is not touched.
+ *       Summation order (the contract): fixed-order fp64 chains, no atomics, nothing contracted.  Every sum over the
+ *       spheres is a chain from 0 over the spheres with rows, ascending; a sphere's term is its three axes in ascending
+ *       order, ((x0 y0 + x1 y1) + x2 y2).  P and N are separate chains.  Bitwise reproducible; a sequence does not depend
+ *       on the other sequences of the batch; the launch shape is one workgroup per frame; no host synchronisation.
+ *       workspace: none is needed; shr_sphere_temporal_normal_workspace_bytes(B, T, J) is 0 (-1 on a negative size).
+ *   Argument rules, checked before the B == 0 no-op: 1 <= J, 1 <= T, B >= 0 and B % T == 0, ts_max >= 0 (+inf allowed),
+ *   temporal_weight finite and >= 0, accumulate 0 or 1 (SHR_EINVAL otherwise); J above 64, B above 65535: SHR_ETOOLARGE.
+ *   NULLs other than frame_weight and workspace, and misaligned pointers (4 bytes; A, g, E, cost 8; keypoints, workspace
+ *   16): SHR_EINVAL.
+ *   shr_pose_lm_seq_begin, shr_pose_lm_seq_step   shr_pose_lm_begin / shr_pose_lm_step with the unit of decision raised
+ *       from the crop to the sequence.  state: shr_pose_lm_seq_state_bytes(B) = 11 520 B bytes (1440 doubles per frame:
+ *       the accepted pose's A, E, g, the pose, params0, and in a sequence's first frame its total cost, lambda and
+ *       counters); workspace: shr_pose_lm_seq_workspace_bytes(B) = 11 072 B bytes (1384 doubles per frame: L_t, W_t, y_t),
+ *       needed with solve != 0; both 8-byte aligned, -1 for B < 0.
+ *       Bookkeeping per sequence: one lambda; total_s = the chain over t ascending of (cost_data_t + the stiffness term of
+ *       frame t, shr_pose_lm_step's chain); the trial of the WHOLE sequence is accepted iff total_s is finite and below the
+ *       state's; lambda x 0.3 on accept, x 10 on reject, clamped to [1e-9, 1e6], the first accepted step leaving it;
+ *       cost0[S] is written by the first step after begin; cost[S], params[B,26] as shr_pose_lm_step's.
+ *       The solve (solve != 0), on the accepted equations: M_t = A_t + diag(mu); the block-tridiagonal system with
+ *       diagonal blocks M_t + lambda diag(M_t), off-diagonal blocks E_t and right-hand side -(g_t + mu (p_t - prior_t)),
+ *       by block Cholesky forward over t: D_t = (M_t + lambda diag(M_t)) - W_{t-1} W_{t-1}^T (the previous factor's
+ *       outer product subtracted entry by entry, k ascending, then the column recurrence of shr_pose_lm_step), L_t L_t^T
+ *       = D_t, W_t = E_t^T L_t^-T by 26 triangular solves, then block forward and back substitution; all fp64, every sum
+ *       in index order.  One workgroup per sequence.  A pivot that is not positive and finite ANYWHERE in the sequence
+ *       writes trial_out = p for the whole sequence.  trial_out[B,26] fp32 = p + delta (may be trial).
+ *       With T == 1 every output and the state's pose are shr_pose_lm_step's BIT FOR BIT (E is then not read and may be
+ *       NULL).
+ *   Argument rules: state given and 8-byte aligned, B >= 0, 1 <= T, B % T == 0 (SHR_EINVAL otherwise), B above 2^24:
+ *   SHR_ETOOLARGE, checked before the B == 0 no-op; lambda0 > 0; NULLs other than prior, stiffness, E with T == 1, and
+ *   trial_out and workspace without solve; misaligned pointers (4 bytes; A, g, E, cost_data, workspace 8): SHR_EINVAL. */
+long long shr_sphere_temporal_normal_workspace_bytes(int B, int T, int J);
+int shr_sphere_temporal_normal(const float *keypoints /* [B,J,4]: shr_pose_keypoints_jacobian's, MODEL frame */,
+                               const float *jac       /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                               const float *frame_weight /* [B] or NULL */, float temporal_weight, float ts_max,
+                               int B, int T, int J, int accumulate,
+                               double *A, double *g, double *E /* [B,26,26] */, double *cost, int32_t *count /* [B] */,
+                               void *workspace, void *stream);
+long long shr_pose_lm_seq_state_bytes(int B);
+long long shr_pose_lm_seq_workspace_bytes(int B);
+int shr_pose_lm_seq_begin(const float *params0, int B, int T, float lambda0, void *state, float *trial, void *stream);
+int shr_pose_lm_seq_step(void *state, const double *A, const double *g, const double *E, const double *cost_data,
+                         const float *trial, const float *prior, const float *stiffness, int solve, int B, int T,
+                         float *trial_out, float *params, float *cost /* [S] */, float *cost0 /* [S] */, void *workspace,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2680,6 +2680,216 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     return params, cost0, cost
 
 
+def _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight):
+    try:
+        T = int(seq_len)
+    except (TypeError, ValueError):
+        raise RuntimeError("seq_len must be an integer >= 1")
+    if T < 1 or B % T != 0:
+        raise RuntimeError("seq_len must be >= 1 and divide the %d frames of the batch, not %r" % (B, seq_len))
+    temporal_weight, ts_max = float(temporal_weight), float(ts_max)
+    if not (temporal_weight >= 0.0 and temporal_weight < float("inf")):
+        raise RuntimeError("temporal_weight must be finite and >= 0, not %r" % (temporal_weight,))
+    if not ts_max >= 0.0:
+        raise RuntimeError("ts_max must be >= 0 (inf: no saturation), not %r" % (ts_max,))
+    if frame_weight is not None:
+        _check_input(frame_weight, "frame_weight")
+        if tuple(frame_weight.shape) != (B,) or frame_weight.device != dev:
+            raise RuntimeError("frame_weight must be [B] on the parameters' device")
+    return T, temporal_weight, ts_max
+
+
+def sphere_temporal_normal(params, offset, offset_inv, bone, wv, seq_len, right_hand=True, temporal_weight=1.0,
+                           ts_max=float("inf"), frame_weight=None, accumulate_into=None):
+    """The normal equations of the sphere fit's temporal term (include/spherehand_hip.h, shr_sphere_temporal_normal):
+    params [B,26], B = S seq_len frames with the frames of a sequence adjacent, the key-point tables of
+    pose_keypoints_jacobian -> (A [B,26,26] the diagonal blocks, g [B,26], E [B,26,26] the off-diagonal blocks (frame t's rows,
+    frame t + 1's columns; +0 for the last frame of a sequence), cost [B] fp64 (a pair's cost at its later frame), count [B]
+    int32: the spheres with rows of the pair ending at the frame).  The term is temporal_weight frame_weight[t]
+    sum_j min(|c_j(t + 1) - c_j(t)|, ts_max)^2 over the model-frame centres; frame_weight [B] >= 0 (None: 1) weighs the pair
+    (t, t + 1) at t.  accumulate_into = (A, g, cost) of the per-frame terms at the same poses: the term is ADDED to them in
+    place (a frame without a weighted pair is not touched) and they are the A, g, cost returned; E is always new.  Two
+    launches: shr_pose_keypoints_jacobian -> shr_sphere_temporal_normal."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv, "parameters")
+    dev = params.device
+    if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
+        raise RuntimeError("every tensor must be on the parameters' device")
+    T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+            _check_input(t, name, torch.float64)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        E = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T, J,
+                                                  int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(E), _ptr(cost),
+                                                  _ptr(count), None, _stream()), "shr_sphere_temporal_normal")
+    return A, g, E, cost, count
+
+
+def pose_lm_seq_begin(params0, seq_len, lambda0=1e-3):
+    """pose_lm_begin for sequences (shr_pose_lm_seq_begin): params0 [B,26], B = S seq_len -> (state, trial [B,26])."""
+    _check_input(params0, "start parameters")
+    if params0.dim() != 2 or params0.shape[1] != 26:
+        raise RuntimeError("start parameters must be [B,26]")
+    if not float(lambda0) > 0:
+        raise RuntimeError("lambda0 must be > 0")
+    B = params0.shape[0]
+    T = _sphere_temporal_args(B, params0.device, seq_len, 0.0, 0.0, None)[0]
+    lib = _lib.lib()
+    with _on(params0.device):
+        state = torch.empty((max(1, lib.shr_pose_lm_seq_state_bytes(B) // 8),), dtype=torch.float64, device=params0.device)
+        trial = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
+        _lib.check(lib.shr_pose_lm_seq_begin(_ptr(params0), B, T, float(lambda0), _ptr(state), _ptr(trial), _stream()),
+                   "shr_pose_lm_seq_begin")
+    return state, trial
+
+
+def pose_lm_seq_step(state, A, g, E, cost_data, trial, seq_len, prior=None, stiffness=None, solve=True, out=None, workspace=None):
+    """One step of the sequence loop (shr_pose_lm_seq_step): A [B,26,26], g [B,26], E [B,26,26] (None with seq_len 1),
+    cost_data [B] fp64 of the poses `trial` [B,26] -> (trial_out [B,26] or None without `solve`, params [B,26], cost [S],
+    cost0 [S]), S = B / seq_len: one decision, one lambda and one cost per sequence, the step from the block-tridiagonal
+    solve.  prior, stiffness, out: pose_lm_step's; workspace: shr_pose_lm_seq_workspace_bytes(B) bytes to use instead of a
+    new buffer."""
+    _check_input(trial, "trial")
+    B = trial.shape[0]
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    T = _sphere_temporal_args(B, trial.device, seq_len, 0.0, 0.0, None)[0]
+    if E is None and T > 1:
+        raise RuntimeError("E is needed with seq_len > 1")
+    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26)),
+                           (cost_data, "cost_data", (B,))):
+        if t is None:
+            continue
+        _check_input(t, name, torch.float64)
+        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    lib = _lib.lib()
+    if state.numel() * 8 < lib.shr_pose_lm_seq_state_bytes(B):
+        raise RuntimeError("state is pose_lm_seq_begin's, for the same B")
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    S = B // T
+    with _on(trial.device):
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
+            out = (new(B, 26) if solve else None, new(B, 26), new(S), new(S))
+        if workspace is None and solve:
+            workspace = torch.empty((max(1, lib.shr_pose_lm_seq_workspace_bytes(B) // 8),), dtype=torch.float64,
+                                    device=trial.device)
+        trial_out, params, cost, cost0 = out
+        _lib.check(lib.shr_pose_lm_seq_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                            _ptr(stiffness), int(bool(solve)), B, T, _ptr(trial_out) if solve else None,
+                                            _ptr(params), _ptr(cost), _ptr(cost0), _ptr(workspace) if solve else None,
+                                            _stream()), "shr_pose_lm_seq_step")
+    return (trial_out if solve else None), params, cost, cost0
+
+
+def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand=True,
+                        pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                        stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
+                        keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
+                        collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None):
+    """sphere_icp_priors over SEQUENCES: the B = S seq_len frames are S sequences of seq_len consecutive frames (adjacent in
+    the batch), fitted jointly by `iters` Levenberg-Marquardt iterations on the sum over a sequence's frames of
+    sphere_icp_priors' energy + temporal_weight sum_t frame_weight[t] sum_j min(|c_j(t + 1) - c_j(t)|, ts_max)^2, c the
+    model-frame sphere centres -> (params [B,26], cost0 [S], cost [S]): one cost, one lambda and one accept decision per
+    sequence.  Each of the iters + 1 evaluations is sphere_icp_priors' launches, then shr_sphere_temporal_normal
+    (accumulate = 1), then shr_pose_lm_seq_step (the block-tridiagonal solve) in place of shr_pose_lm_step, on torch's
+    current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a graph.
+    Without a weighted temporal term (temporal_weight = 0 or seq_len = 1) no launch of the temporal entry is issued and E
+    is zero; with seq_len = 1 the loop is sphere_icp_priors bit for bit."""
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
+                                                    max_dist, "start parameters")
+    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
+    dev = observed.device
+    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
+                                                                       limits, limit_weight)
+    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
+    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
+                                                                           "collision_weight")
+    collide = K > 0 and collision_weight > 0.0
+    T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
+    temporal = T > 1 and temporal_weight > 0.0
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    state, trial = pose_lm_seq_begin(params0, T, lambda0)
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    S = B // T
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        E = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)       # (stays zero without the temporal entry)
+        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
+        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
+        temporal_rows = torch.empty((B,), dtype=torch.int32, device=dev) if temporal else None
+        params, cost0, cost = f32(B, 26), f32(S), f32(S)
+        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
+                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        seq_ws = f64(max(1, lib.shr_pose_lm_seq_workspace_bytes(B) // 8))
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
+                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
+                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
+            if render_weight > 0.0:
+                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
+                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
+                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
+                                                        stream), "shr_sphere_render_normal")
+            if priors:
+                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
+                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
+                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
+            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
+                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
+                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
+            if temporal:
+                _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T,
+                                                          J, 1, _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(temporal_rows),
+                                                          None, stream), "shr_sphere_temporal_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_seq_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                                _ptr(stiffness), solve, B, T, _ptr(trial) if solve else None, _ptr(params),
+                                                _ptr(cost), _ptr(cost0), _ptr(seq_ws) if solve else None, stream),
+                       "shr_pose_lm_seq_step")
+    return params, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

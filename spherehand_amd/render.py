@@ -1100,6 +1100,68 @@ class SphereCollisionPoseFitter(SpherePriorPoseFitter):
                                            (A, g, cost))
 
 
+class SphereSequencePoseFitter(SphereCollisionPoseFitter):
+    """SphereCollisionPoseFitter over SEQUENCES of seq_len consecutive frames fitted jointly: the batch's B = S seq_len
+    frames are S sequences, the frames of one adjacent, and the energy of a sequence is
+        the sum over its frames of SphereCollisionPoseFitter's energy
+        + temporal_weight sum_t frame_weight[t] sum_j min(|c_j(t + 1) - c_j(t)|, ts_max)^2,
+    c the sphere centres in the model frame (ops.sphere_icp_sequence; include/spherehand_hip.h,
+    shr_sphere_temporal_normal and shr_pose_lm_seq_step).  The term is the reference's TemporalSmoothnessLoss
+    (network/util_modules.py:360-381) as Gauss-Newton rows; it couples frame t and t + 1, so the normal equations of a
+    sequence are block-tridiagonal and lambda, the cost and the accept decision belong to the sequence.  Unlike the
+    reference, which detaches the previous frame, the term pulls BOTH frames of a pair.
+        solve(observed, params0, view=None, prior=None, keypoints=None, confidence=None, frame_weight=None)
+            -> (params [B,26], cost0 [S], cost [S])
+        normal_equations(observed, params, view=None, keypoints=None, confidence=None, frame_weight=None)
+            -> (A, g, E, cost, count [B]) of the SUM of the six terms' A, g and cost; E [B,26,26] (frame t's rows, frame
+               t + 1's columns) and count (the spheres with rows of the pair ending at the frame) are the new term's own
+    frame_weight [B] >= 0 weighs the pair (t, t + 1) at t (None: 1): 0 cuts a sequence at a scene change.  With
+    seq_len = 1 it is SphereCollisionPoseFitter bit for bit.  The defaults come from DESIGN.md 4.4t's study, which also
+    says what the term does NOT fix: it penalises motion itself, so it lags a hand that really moves, and one rejected
+    frame rejects its whole sequence.  Everything else is SphereCollisionPoseFitter's: a refinement from a start pose,
+    NO autograd through the solve, the rotation NOT checked."""
+
+    # DESIGN.md 4.4t: the study's row
+    DEFAULT_TEMPORAL_WEIGHT = 0.1
+    DEFAULT_TS_MAX = float("inf")
+
+    def __init__(self, mesh, width, height, seq_len, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3,
+                 stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None,
+                 max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
+                 collision_weight=None, min_dist=None, radius_scale=None, temporal_weight=None, ts_max=None):
+        super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
+                         render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits, collision_weight,
+                         min_dist, radius_scale)
+        self.seq_len = int(seq_len)
+        self.temporal_weight = float(self.DEFAULT_TEMPORAL_WEIGHT if temporal_weight is None else temporal_weight)
+        self.ts_max = float(self.DEFAULT_TS_MAX if ts_max is None else ts_max)
+        if self.seq_len < 1 or not (self.temporal_weight >= 0.0 and self.temporal_weight < float("inf")) or \
+                not self.ts_max >= 0.0:
+            raise ValueError("seq_len must be >= 1, temporal_weight finite and >= 0, ts_max >= 0")
+
+    @staticmethod
+    def _frame_weight(frame_weight):
+        return None if frame_weight is None else frame_weight.detach().contiguous().float()
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None, frame_weight=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        return ops.sphere_icp_sequence(observed, view, params0.detach().contiguous().float(), *self._tables(), self.seq_len,
+                                       self.right_hand, self.pixel_to_model, self.fg_max, self.max_dist, self.iters,
+                                       self.lambda0, self.stiffness,
+                                       None if prior is None else prior.detach().contiguous().float(), self.render_weight,
+                                       self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
+                                       limits, self.limit_weight, self._pairs(), self.collision_weight, self.temporal_weight,
+                                       self.ts_max, self._frame_weight(frame_weight))
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, frame_weight=None):
+        params = params.detach().contiguous().float()
+        A, g, cost = SphereCollisionPoseFitter.normal_equations(self, observed, params, view, keypoints, confidence)[:3]
+        return ops.sphere_temporal_normal(params, *self._tables()[:4], self.seq_len, self.right_hand, self.temporal_weight,
+                                          self.ts_max, self._frame_weight(frame_weight), (A, g, cost))
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster

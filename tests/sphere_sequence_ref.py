@@ -1,0 +1,513 @@
+"""A restatement of the sequence fit of the sphere model (spherehand_amd/csrc/sphere_temporal.hip and lm_seq.hip;
+include/spherehand_hip.h, the section of shr_sphere_temporal_normal and shr_pose_lm_seq_step), on top of
+tests/sphere_collision_ref.py, tests/sphere_prior_ref.py, tests/sphere_icp_ref.py and tests/pose_icp_ref.py's LM, none of which
+it changes (test helper; not a conftest):
+
+    decide         per (pair, sphere): e, n2, valid, the cost term and whether it has rows -- the header's rules in numpy fp64
+                   on fp32 centres; arrays are indexed by the pair's EARLIER frame
+    energy         the torch expression of the cost per frame (a pair's cost at its later frame), differentiable in p
+    normal         A, g, E, cost, count by AUTOGRAD: the Jacobian of a sequence's stacked residuals with respect to all of
+                   its 26 T parameters, H = J^T W J cut into blocks; nothing about +-Jc is stated
+    chain          A, g, E, cost, count in the header's summation order, operation for operation, GIVEN the entry's own fp32
+                   centres and Jacobian: what the entry gives
+    block_solve    shr_pose_lm_seq_step's block Cholesky, forward and back substitution word for word, numpy fp64
+    dense_solve    the 26 T x 26 T system assembled densely and solved by numpy.linalg.solve: the independent check
+    SeqLM          shr_pose_lm_seq_begin / _step: one lambda, one cost and one decision per sequence
+    combined/solve the loop of ops.sphere_icp_sequence on sphere_collision_ref.combined
+    sequence_case  the inputs of the GPU tests, on which the fp32 bars are measured
+    study          DESIGN.md 4.4t's table
+
+dtype is the chain's, as in sphere_icp_ref."""
+import numpy as np
+import torch
+
+import pose_icp_ref as ref
+import pose_icp_views_ref as vref
+import sphere_collision_ref as cref
+import sphere_icp_ref as sref
+import sphere_prior_ref as pref
+import sphere_render_icp_ref as rref
+
+INF = float("inf")
+# render.SphereSequencePoseFitter's defaults
+DEFAULT_TEMPORAL_WEIGHT, DEFAULT_TS_MAX = 0.1, INF
+
+
+def _weights(B, T, frame_weight):
+    """[B] fp64: the weight of the pair (b, b + 1), 0 where frame b is the last of its sequence or the weight is not > 0."""
+    fw = np.ones(B, np.float32) if frame_weight is None else np.asarray(frame_weight, np.float32)
+    with np.errstate(invalid="ignore"):
+        live = (np.arange(B) % T < T - 1) & (fw > 0)
+    return np.where(live, fw.astype(np.float64), 0.0), live
+
+
+def decide(centres32, T, ts_max=INF, frame_weight=None):
+    """dict over [B,J] indexed by the pair's EARLIER frame: e [B,J,3] = c(b + 1) - c(b), n2, valid (the pair has a weight and
+    n2 is no NaN), act (rows: n2 < cap2), term (min(n2, cap2), 0 where not valid); fw [B], live [B]."""
+    c = np.asarray(centres32, np.float32)[..., :3].astype(np.float64)
+    B = c.shape[0]
+    fw, live = _weights(B, T, frame_weight)
+    e = np.roll(c, -1, axis=0) - c
+    with np.errstate(invalid="ignore", over="ignore"):
+        n2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+        cap2 = np.float64(np.float32(ts_max)) * np.float64(np.float32(ts_max))
+        valid = live[:, None] & ~np.isnan(n2)
+        act = valid & (n2 < cap2)
+        term = np.where(valid, np.where(act, n2, cap2), 0.0)
+    return dict(e=e, n2=n2, valid=valid, act=act, term=term, fw=fw, live=live, cap2=cap2)
+
+
+def energy(model, p, T, temporal_weight=1.0, ts_max=INF, frame_weight=None, held=None):
+    """cost [B] as a torch expression of p: the pair (b - 1, b)'s cost at frame b, w sum_j min(n2, cap2), the set with rows
+    decided at p itself or held (decide()'s dict)."""
+    c = model.centres(p).double()
+    B = c.shape[0]
+    d = decide(c.detach().numpy(), T, ts_max, frame_weight) if held is None else held
+    e = torch.roll(c, -1, 0) - c
+    n2 = (e * e).sum(-1)
+    cap = torch.full_like(n2, float(min(d["cap2"], 1.7e308)))
+    t = torch.where(torch.as_tensor(d["act"]), n2, torch.where(torch.as_tensor(d["valid"]), cap, torch.zeros_like(n2)))
+    w = float(np.float32(temporal_weight)) * torch.as_tensor(d["fw"])
+    pair = w * t.sum(1)                                        # at the earlier frame
+    return torch.roll(pair, 1, 0) * torch.as_tensor((np.arange(B) % T > 0).astype(np.float64))
+
+
+def normal(model, p, T, temporal_weight=1.0, ts_max=INF, frame_weight=None, centres32=None, chain_residual=False):
+    """dict of A [B,26,26], g [B,26], E [B,26,26], cost [B], count [B] by autograd through the chain: per sequence the
+    Jacobian of the stacked residuals e of the spheres with rows with respect to the sequence's [T,26] parameters.
+    centres32: the centres the rows are decided on (the kernel's own), default the model's rounded once.  chain_residual:
+    the chain's own e in g (whose gradient g then is) instead of the contract's."""
+    B = p.shape[0]
+    tw = float(np.float32(temporal_weight))
+    c32 = model.centres(p.to(model.dtype)).detach().float().numpy() if centres32 is None else np.asarray(centres32, np.float32)
+    d = decide(c32, T, ts_max, frame_weight)
+    A, g, E = (torch.zeros(B, 26, 26, dtype=torch.float64), torch.zeros(B, 26, dtype=torch.float64),
+               torch.zeros(B, 26, 26, dtype=torch.float64))
+    for s in range(B // T if tw > 0 else 0):
+        rows_ = slice(s * T, s * T + T)
+        act = torch.as_tensor(d["act"][rows_])
+        if not bool(act.any()):
+            continue
+        w = (tw * torch.as_tensor(d["fw"][rows_]))[:, None, None].expand(T, act.shape[1], 3)[act]
+
+        def resid(P):
+            c = model.centres(P).double()
+            return (torch.roll(c, -1, 0) - c)[act]             # [N,3] of the (pair, sphere) with rows
+
+        P = p[rows_].detach().to(model.dtype)
+        Jr = torch.autograd.functional.jacobian(resid, P).double().reshape(-1, T * 26)
+        r = torch.as_tensor(d["e"][rows_])[act].reshape(-1)    # the contract's e: fp64 on the fp32 centres
+        if chain_residual:
+            r = resid(P).detach().double().reshape(-1)
+        H = (Jr * w.reshape(-1, 1)).t() @ Jr
+        G = Jr.t() @ (w.reshape(-1) * r)
+        for t in range(T):
+            A[s * T + t] = H[26 * t:26 * t + 26, 26 * t:26 * t + 26]
+            g[s * T + t] = G[26 * t:26 * t + 26]
+            if t < T - 1:
+                E[s * T + t] = H[26 * t:26 * t + 26, 26 * t + 26:26 * t + 52]
+    pair = tw * d["fw"] * d["term"].sum(1)
+    later = (np.arange(B) % T > 0)
+    cost = torch.as_tensor(np.where(later, np.roll(pair, 1), 0.0))
+    count = torch.as_tensor(np.where(later, np.roll(d["act"].sum(1), 1), 0))
+    return dict(A=A, g=g, E=E, cost=cost, count=count, decided=d)
+
+
+def chain(centres32, jac32, T, temporal_weight=1.0, ts_max=INF, frame_weight=None, into=None):
+    """(A, g, E, cost, count) numpy fp64 in the header's order, operation for operation.  A sphere's term is its three axes
+    ascending, ((x0 y0 + x1 y1) + x2 y2); the sums run over the spheres with rows, ascending, from 0; P (the pair before
+    the frame) and N (the pair after it) are separate chains: A = w_prev P + w_next N, g = w_prev P + w_next (0 - N),
+    E = 0 - w_next X.  into = (A, g, cost): the term is added (accumulate = 1), frames without a weighted pair untouched."""
+    d = decide(centres32, T, ts_max, frame_weight)
+    q = np.asarray(jac32).astype(np.float64)
+    B, J = d["act"].shape
+    q = q.reshape(B, J, 3, 26)
+    tw = np.float64(np.float32(temporal_weight))
+    used = tw > 0
+    A, g, cost = (np.zeros((B, 26, 26)), np.zeros((B, 26)), np.zeros(B)) if into is None else (np.array(t, np.float64) for t in into)
+    E = np.zeros((B, 26, 26))
+    count = np.zeros(B, np.int64)
+    for b in range(B):
+        use_p = used and b % T > 0 and bool(d["live"][b - 1])
+        use_n = used and bool(d["live"][b])
+        if b % T > 0:
+            count[b] = d["act"][b - 1].sum()
+        wp = tw * d["fw"][b - 1] if use_p else 0.0
+        wn = tw * d["fw"][b] if use_n else 0.0
+        P, N, X = np.zeros((26, 26)), np.zeros((26, 26)), np.zeros((26, 26))
+        GP, GN, C = np.zeros(26), np.zeros(26), np.float64(0.0)
+        for j in range(J):
+            own = q[b, j]
+            sq = (own[0][:, None] * own[0][None] + own[1][:, None] * own[1][None]) + own[2][:, None] * own[2][None]
+            if use_p and d["act"][b - 1, j]:
+                e = d["e"][b - 1, j]
+                P = P + sq
+                GP = GP + ((own[0] * e[0] + own[1] * e[1]) + own[2] * e[2])
+            if use_n and d["act"][b, j]:
+                e, nxt = d["e"][b, j], q[b + 1, j]
+                N = N + sq
+                GN = GN + ((own[0] * e[0] + own[1] * e[1]) + own[2] * e[2])
+                X = X + ((own[0][:, None] * nxt[0][None] + own[1][:, None] * nxt[1][None]) + own[2][:, None] * nxt[2][None])
+            if use_p:
+                C = C + d["term"][b - 1, j]
+        if use_n:
+            E[b] = 0.0 - wn * X
+        if into is not None and not (use_p or use_n):
+            continue
+        mine_A, mine_g = wp * P + wn * N, wp * GP + wn * (0.0 - GN)
+        if into is None:
+            A[b], g[b], cost[b] = mine_A, mine_g, wp * C
+        else:
+            A[b], g[b] = A[b] + mine_A, g[b] + mine_g
+            if use_p:
+                cost[b] = cost[b] + wp * C
+    return A, g, E, cost, count
+
+
+# ---- the solve ----------------------------------------------------------------------------------------------------------
+def _cholesky(M, lam, Wt):
+    """lm_seq.hip's sq_cholesky: column by column, the diagonal damped first, the previous factor's outer product subtracted
+    entry by entry (k ascending), then the columns' own.  (L, ok)."""
+    n = M.shape[0]
+    L = np.zeros((n, n))
+    for k in range(n):
+        v = M[k:, k].copy()
+        v[0] = v[0] + lam * v[0]
+        if Wt is not None:
+            for m in range(n):
+                v = v - Wt[m, k:] * Wt[m, k]
+        for m in range(k):
+            v = v - L[k:, m] * L[k, m]
+        d = v[0]
+        if not (d > 0 and d < np.inf):
+            return L, False
+        root = np.sqrt(d)
+        L[k:, k] = v / root
+        L[k, k] = root
+    return L, True
+
+
+def block_solve(A, g, E, lam, mu, p, prior, T):
+    """delta [T,26] (None where a pivot is not positive and finite) of ONE sequence: the header's block Cholesky, forward over t,
+    then block forward and back substitution, every sum in index order.  A, E [T,26,26], g, p, prior [T,26] fp64."""
+    A, g, E, p, prior, mu = (np.asarray(t, np.float64) for t in (A, g, E, p, prior, mu))
+    n = 26
+    Ls, Wts, ys = [], [], []
+    Wt, y_prev = None, None
+    for t in range(T):
+        M = A[t].copy()
+        M[np.arange(n), np.arange(n)] += mu
+        with np.errstate(all="ignore"):
+            L, ok = _cholesky(M, lam, Wt)
+        if not ok:
+            return None
+        rhs = -(g[t] + mu * (p[t] - prior[t]))
+        if t > 0:
+            c = np.zeros(n)
+            for k in range(n):
+                c = c + Wt[k] * y_prev[k]
+            rhs = rhs - c
+        y, acc = np.zeros(n), np.zeros(n)
+        for k in range(n):
+            y[k] = (rhs[k] - acc[k]) / L[k, k]
+            acc[k + 1:] = acc[k + 1:] + L[k + 1:, k] * y[k]
+        Ls.append(L)
+        ys.append(y)
+        y_prev = y
+        if t < T - 1:
+            Wt = E[t].copy()                                   # Wt[k, i] = W[i, k]: column i solves L z = E[:, i]
+            for k in range(n):
+                v = Wt[k].copy()
+                for m in range(k):
+                    v = v - L[k, m] * Wt[m]
+                Wt[k] = v / L[k, k]
+            Wts.append(Wt)
+    x = np.zeros((T, n))
+    for t in range(T - 1, -1, -1):
+        z = ys[t].copy()
+        if t < T - 1:
+            c = np.zeros(n)
+            for i in range(n):
+                c = c + Wts[t][:, i] * x[t + 1, i]
+            z = z - c
+        acc = np.zeros(n)
+        L = Ls[t]
+        for k in range(n - 1, -1, -1):
+            x[t, k] = (z[k] - acc[k]) / L[k, k]
+            acc[:k] = acc[:k] + L[k, :k] * x[t, k]
+    return x
+
+
+def dense_system(A, g, E, lam, mu, p, prior, T):
+    """(H [26T,26T], rhs [26T]): diagonal blocks M_t + lam diag(M_t), M_t = A_t + diag(mu); blocks (t, t + 1) = E_t and
+    (t + 1, t) = E_t^T; rhs -(g_t + mu (p_t - prior_t))."""
+    A, g, E, p, prior, mu = (np.asarray(t, np.float64) for t in (A, g, E, p, prior, mu))
+    H, rhs = np.zeros((26 * T, 26 * T)), np.zeros(26 * T)
+    for t in range(T):
+        M = A[t] + np.diag(mu)
+        H[26 * t:26 * t + 26, 26 * t:26 * t + 26] = M + lam * np.diag(np.diag(M))
+        rhs[26 * t:26 * t + 26] = -(g[t] + mu * (p[t] - prior[t]))
+        if t < T - 1:
+            H[26 * t:26 * t + 26, 26 * t + 26:26 * t + 52] = E[t]
+            H[26 * t + 26:26 * t + 52, 26 * t:26 * t + 26] = E[t].T
+    return H, rhs
+
+
+def dense_solve(A, g, E, lam, mu, p, prior, T):
+    H, rhs = dense_system(A, g, E, lam, mu, p, prior, T)
+    return np.linalg.solve(H, rhs).reshape(T, 26)
+
+
+class SeqLM:
+    """shr_pose_lm_seq_begin / shr_pose_lm_seq_step: pose_icp_ref.LM with one lambda, one cost and one decision per sequence of
+    T frames.  The step is the block algorithm on torch's LAPACK calls, as pose_icp_ref.LM's is (with T = 1 the very same
+    calls); block_solve is the kernel's recurrences word for word, held against it by the tests."""
+
+    def __init__(self, params0, T, lambda0=1e-3, dtype=torch.float64):
+        B = params0.shape[0]
+        assert B % T == 0
+        S = B // T
+        self.T, self.S, self.dtype = T, S, dtype
+        self.p0 = params0.double().clone()
+        self.p = self.p0.clone()
+        self.cost = torch.full((S,), INF, dtype=torch.float64)
+        self.lam = torch.full((S,), float(np.float32(lambda0)), dtype=torch.float64)
+        self.A, self.E = torch.zeros(B, 26, 26, dtype=torch.float64), torch.zeros(B, 26, 26, dtype=torch.float64)
+        self.g = torch.zeros(B, 26, dtype=torch.float64)
+        self.fresh, self.moved = True, torch.zeros(S, dtype=torch.bool)
+        self.accepts, self.rejects = torch.zeros(S, dtype=torch.int64), torch.zeros(S, dtype=torch.int64)
+        self.cost0 = None
+        self.trial = self.p0.clone()
+        self.history = []
+
+    def step(self, A, g, E, cost_data, trial, prior=None, stiffness=None, solve=True):
+        B, T, S = trial.shape[0], self.T, self.S
+        trial = trial.double()
+        prior = self.p0 if prior is None else prior.double()
+        mu = torch.zeros(26, dtype=torch.float64) if stiffness is None else torch.as_tensor(stiffness).double()
+        frame = cost_data.double().clone()
+        for i in range(26):
+            diff = trial[:, i] - prior[:, i]
+            frame = frame + mu[i] * (diff * diff)
+        frame = frame.view(S, T)
+        total = frame[:, 0].clone()
+        for t in range(1, T):
+            total = total + frame[:, t]
+        accept = torch.isfinite(total) & (total < self.cost)
+        af = accept.repeat_interleave(T)
+        self.p = torch.where(af[:, None], trial, self.p)
+        self.A = torch.where(af[:, None, None], A.double(), self.A)
+        self.E = torch.where(af[:, None, None], E.double(), self.E)
+        self.g = torch.where(af[:, None], g.double(), self.g)
+        self.cost = torch.where(accept, total, self.cost)
+        factor = torch.where(accept, torch.where(self.moved, torch.tensor(ref.LAMBDA_DOWN, dtype=torch.float64),
+                                                 torch.tensor(1.0, dtype=torch.float64)),
+                             torch.tensor(ref.LAMBDA_UP, dtype=torch.float64))
+        self.lam = (self.lam * factor).clamp(ref.LAMBDA_MIN, ref.LAMBDA_MAX)
+        self.moved = self.moved | accept
+        self.accepts, self.rejects = self.accepts + accept.long(), self.rejects + (~accept).long()
+        self.history.append(accept.clone())
+        if self.fresh:
+            self.cost0, self.fresh = total.clone(), False
+        if not solve:
+            return None
+        M = self.A + torch.diag_embed(mu.expand(B, 26))
+        Md = (M + torch.diag_embed(self.lam.repeat_interleave(T)[:, None] * torch.diagonal(M, dim1=1, dim2=2))).view(S, T, 26, 26)
+        rhs = (-(self.g + mu * (self.p - prior))).view(S, T, 26)
+        Ev = self.E.view(S, T, 26, 26)
+        ok = torch.ones(S, dtype=torch.bool)
+        eye = torch.eye(26, dtype=torch.float64).expand(S, 26, 26)
+        Ls, Ws, ys = [], [], []
+        W = y = None
+        for t in range(T):
+            D = Md[:, t] if t == 0 else Md[:, t] - W @ W.transpose(1, 2)
+            L, info = torch.linalg.cholesky_ex(D)
+            diag = torch.diagonal(L, dim1=1, dim2=2)
+            ok = ok & (info == 0) & torch.isfinite(L).all(-1).all(-1) & (diag > 0).all(-1)
+            L = torch.where(ok.view(S, 1, 1), L, eye)
+            r = rhs[:, t] if t == 0 else rhs[:, t] - (W @ y.unsqueeze(-1)).squeeze(-1)
+            Ls.append(L)
+            if T == 1:
+                break
+            y = torch.linalg.solve_triangular(L, r.unsqueeze(-1), upper=False).squeeze(-1)
+            ys.append(y)
+            if t < T - 1:                                      # W L^T = E^T
+                W = torch.linalg.solve_triangular(L, Ev[:, t], upper=False).transpose(1, 2)
+                Ws.append(W)
+        if T == 1:
+            delta = torch.cholesky_solve(rhs[:, 0].unsqueeze(-1), Ls[0]).squeeze(-1).view(S, 1, 26)
+        else:
+            xs = [None] * T
+            for t in range(T - 1, -1, -1):
+                z = ys[t] if t == T - 1 else ys[t] - (Ws[t].transpose(1, 2) @ xs[t + 1].unsqueeze(-1)).squeeze(-1)
+                xs[t] = torch.linalg.solve_triangular(Ls[t].transpose(1, 2), z.unsqueeze(-1), upper=True).squeeze(-1)
+            delta = torch.stack(xs, 1)
+        delta = torch.where(ok.view(S, 1, 1), delta, torch.zeros_like(delta)).reshape(B, 26)
+        self.ok = ok
+        self.trial = (self.p + delta).float().double()        # the trial is fp32 by contract, whatever the chain
+        return self.trial
+
+
+def combined(model, view, observed, p, p2m, T, tab=None, collision_weight=0.0, temporal_weight=0.0, ts_max=INF,
+             frame_weight=None, **prior):
+    """(A, g, E, cost, temporal) at poses p: sphere_collision_ref.combined per frame plus the temporal term; `temporal` is
+    normal()'s dict or None where the loop issues no launch of the entry (E is then zero)."""
+    A, g, cost, _ = cref.combined(model, view, observed, p, p2m, tab, collision_weight, **prior)
+    if T == 1 or not temporal_weight > 0:
+        return A, g, torch.zeros_like(A), cost, None
+    n = normal(model, p, T, temporal_weight, ts_max, frame_weight)
+    return A + n["A"], g + n["g"], n["E"], cost + n["cost"], n
+
+
+def solve(model, view, observed, params0, p2m, T, tab=None, collision_weight=0.0, temporal_weight=0.0, ts_max=INF,
+          frame_weight=None, iters=10, lambda0=1e-3, stiffness=None, prior=None, **terms):
+    """The loop of ops.sphere_icp_sequence in model.dtype -> (params [B,26], cost0 [S], cost [S], lm); lm.rowed: per
+    evaluation the [B,J] bool of the spheres with temporal rows (None without the term)."""
+    start = params0.float().double() if model.dtype == torch.float32 else params0.double()
+    lm = SeqLM(start, T, lambda0, model.dtype)
+    lm.rowed = []
+    trial = lm.trial
+    for it in range(iters + 1):
+        A, g, E, cost, n = combined(model, view, observed, trial, p2m, T, tab, collision_weight, temporal_weight, ts_max,
+                                    frame_weight, **terms)
+        lm.rowed.append(None if n is None else torch.as_tensor(n["decided"]["act"]))
+        out = lm.step(A, g, E, cost, trial, prior, stiffness, solve=it < iters)
+        trial = out if out is not None else trial
+    return lm.p, lm.cost0, lm.cost, lm
+
+
+# ---- sequences ----------------------------------------------------------------------------------------------------------
+def sequence_poses(S, T, seed=31, sigma_start=None):
+    """(p* [S T,26], p0 [S T,26]): sequence s runs from pose 2 s to pose 2 s + 1 of pose_icp_ref.poses(2 S, seed), linearly
+    interpolated in the 26 parameters (T = 1: pose 2 s); the starts are p* + N(0, 0.1 rad) on the 23 angles and N(0, 2 mm)
+    on the translation, drawn independently per frame."""
+    p, _ = ref.poses(2 * S, seed)
+    lam = torch.linspace(0, 1, T, dtype=torch.float64) if T > 1 else torch.zeros(1, dtype=torch.float64)
+    star = (p[0::2, None] * (1 - lam)[None, :, None] + p[1::2, None] * lam[None, :, None]).reshape(S * T, 26)
+    gen = torch.Generator().manual_seed(seed + 1000)
+    p0 = star + ref.SIGMA_ANGLE * torch.randn(S * T, 26, generator=gen, dtype=torch.float64)
+    p0[:, 3:6] = star[:, 3:6] + ref.SIGMA_MM * torch.randn(S * T, 3, generator=gen, dtype=torch.float64)
+    return star, p0
+
+
+def jitter(model, p, p_star, T):
+    """mean over t and j of |(c_j(t + 1) - c_j(t)) - the truth's| per sequence, mm (fp64)"""
+    m = model.to(torch.float64)
+    c, cs = m.centres(p.double()), m.centres(p_star.double())
+    B, J = c.shape[:2]
+    d = (c.view(B // T, T, J, 3)[:, 1:] - c.view(B // T, T, J, 3)[:, :-1]) - \
+        (cs.view(B // T, T, J, 3)[:, 1:] - cs.view(B // T, T, J, 3)[:, :-1])
+    return d.norm(dim=-1).mean((1, 2))
+
+
+END_TO_END_ITERS = 4
+_CACHE = {}
+
+
+def sequence_case(mesh, S, T, table="hand", seed=31, sigma_k=2.0):
+    """The GPU tests' inputs: S sequences of T frames at 32 x 32, one identity view, the right hand's 41 spheres (`hand`) or
+    sphere_icp_ref.synthetic_table's 7 points (`synthetic`: the twin pair, a radius of 0), sphere-rendered, STIFFNESS,
+    keypoints with sigma_k mm of noise drawn per frame, pose_limits(), and the collision table where the table is the
+    hand's (`table` None otherwise).  Once per process; nothing modifies a case."""
+    key = (S, T, table, seed, sigma_k)
+    if key not in _CACHE:
+        model = sref.Spheres(mesh, None if table == "hand" else sref.synthetic_table(), True)
+        B = S * T
+        p, p0 = sequence_poses(max(S, 1), T, seed)
+        p, p0 = p[:B], p0[:B]
+        view = vref.views(B, ("identity",)) if B else np.zeros((0, 1, 4, 4))
+        W = H = 32
+        base = dict(name="sequence", model=model, W=W, H=H, p2m=ref.grid(W, H), p_star=p, params0=p0, view=view,
+                    kinds=("identity",), observed=sref.render(model, view, p, W, H) if B else np.zeros((0, 1, H, W), np.float32),
+                    stiffness=torch.as_tensor(ref.STIFFNESS), iters=END_TO_END_ITERS, S=S, T=T)
+        if B:
+            base = pref.with_targets(base, sigma=sigma_k, seed=13, drop=False)
+        base["table"] = cref.table(mesh) if table == "hand" else None
+        _CACHE[key] = base
+    return _CACHE[key]
+
+
+def terms_of(case, kp_weight=pref.DEFAULT_KP_WEIGHT, kp_max=pref.DEFAULT_KP_MAX, limit_weight=pref.DEFAULT_LIMIT_WEIGHT):
+    """The keyword arguments of combined / solve for a case's keypoint and limit terms."""
+    return dict(keypoints=case["keypoints"], confidence=case["confidence"], kp_weight=kp_weight, kp_max=kp_max,
+                lower=case["lower"], upper=case["upper"], limit_weight=limit_weight if case["lower"] is not None else 0.0)
+
+
+# ---- the study ----------------------------------------------------------------------------------------------------------
+BLIND_FRAMES = (3, 4)     # the middle frames of T = 8 in which the `blind` family hides the index finger
+
+
+def study_sequences(family, S=3, T=8):
+    """(p*, p0, hidden [S T] bool).  `noise`: sequence_poses(S, T, 41).  `blind`: 4.4q's blind finger in the MIDDLE frames
+    only -- the truth keeps the index finger curled in every frame (so it is smooth); in frames BLIND_FRAMES the start has
+    that finger extended and `hidden` marks the frame: the study drops the finger's keypoints there, so that in those
+    frames nothing but the stiffness -- and the temporal term -- holds it."""
+    p, p0 = sequence_poses(S, T, 41)
+    hidden = torch.zeros(S * T, dtype=torch.bool)
+    if family == "blind":
+        F = rref.FINGER
+        noise = p0 - p
+        p = p.clone()
+        p[:, F + 1:F + 4] = torch.tensor(rref.CURLED, dtype=torch.float64)
+        p0 = p + noise
+        for t in BLIND_FRAMES:
+            hidden[t::T] = True
+        p0[hidden, F + 1:F + 4] = torch.tensor(rref.EXTENDED, dtype=torch.float64)
+    return p, p0, hidden
+
+
+def study(mesh, W=48, H=40, S=3, T=8, iters=10, sigma=5.0,
+          rows=((0.01, INF), (0.1, INF), (1.0, INF), (10.0, INF), (0.1, 20.0), (1.0, 20.0)), families=("noise", "blind"), out=print):
+    """The table of DESIGN.md 4.4t: per family, temporal_weight and ts_max, over S sequences of T frames, one view, 4.4s's
+    defaults for the other terms and keypoints with sigma mm of noise drawn per frame: the mean keypoint error and the
+    frame-to-frame jitter before and after, and the median and worst cost0 / cost per sequence.  The first row of a family
+    (`frames`) is the frame-by-frame fit, SphereCollisionPoseFitter at its defaults on the same frames (T = 1)."""
+    model = sref.Spheres(mesh, None, True)
+    p2m = ref.grid(W, H)
+    mu = torch.as_tensor(ref.STIFFNESS)
+    lo, hi = pref.limits()
+    tab = cref.table(mesh)
+    B = S * T
+    view = vref.views(B, ("identity",))
+    finger = None                                              # the spheres the index finger's flexes move (`blind`)
+    rows_out = []
+    for family in families:
+        p, p0, hidden = study_sequences(family, S, T)
+        obs = rref.render64(model, view, p, W, H, p2m)
+        k = pref.targets(model, view, p, sigma, seed=3)
+        if family == "blind":
+            c0 = model.centres(p).detach()
+            q = p.clone()
+            q[:, rref.FINGER + 1:rref.FINGER + 4] += 0.5
+            finger = np.nonzero((model.centres(q).detach() - c0).norm(dim=-1).max(0).values.numpy() > 1e-9)[0]
+            k[np.ix_(np.nonzero(hidden.numpy())[0], [0], finger)] = np.nan
+        terms = dict(keypoints=k, confidence=None, kp_weight=pref.DEFAULT_KP_WEIGHT, kp_max=pref.DEFAULT_KP_MAX, lower=lo,
+                     upper=hi, limit_weight=pref.DEFAULT_LIMIT_WEIGHT)
+        start, jit0 = sref.keypoint_error(model, p0, p), jitter(model, p0, p, T)
+        out("%s: start keypoint error %.2f mm, jitter %.2f mm; the truth moves %.2f mm per frame and sphere"
+            % (family, start.mean(), jit0.mean(), jitter(model, p, p[:1].expand_as(p), T).mean()))
+        for name, tw, cap, TT in (("frames", 0.0, INF, 1),) + tuple(("seq", w, c, T) for w, c in rows):
+            q, c0, c, _ = solve(model, view, obs, p0, p2m, TT, tab, cref.DEFAULT_COLLISION_WEIGHT, tw, cap, None, iters, 1e-3, mu,
+                                **terms)
+            err, jit = sref.keypoint_error(model, q, p), jitter(model, q, p, T)
+            ratio = c0 / c.clamp(min=1e-300)
+            row = dict(family=family, name=name, weight=tw, ts_max=cap, start=start.mean().item(), mean=err.mean().item(),
+                       median=err.median().item(), jitter0=jit0.mean().item(), jitter=jit.mean().item(),
+                       ratio_median=ratio.median().item(), ratio_worst=ratio.min().item())
+            if family == "blind":
+                fe = (model.centres(q) - model.centres(p)).detach().norm(dim=-1)[:, finger].mean(1)
+                row["hidden"] = fe[hidden].mean().item()
+            rows_out.append(row)
+            out("  %-6s w %-5g ts_max %-4g: error %.2f -> %.2f (%.2f) mm, jitter %.2f -> %.2f mm, cost0/cost %.3g (worst %.3g)%s"
+                % (name, tw, cap, row["start"], row["mean"], row["median"], row["jitter0"], row["jitter"], row["ratio_median"],
+                   row["ratio_worst"], "" if "hidden" not in row else "; the hidden finger in its frames %.2f mm" % row["hidden"]))
+    return rows_out
+
+
+if __name__ == "__main__":
+    import sys
+    from spherehand_amd import hand_model
+    kw = {}
+    if len(sys.argv) > 1:
+        kw["families"] = (sys.argv[1],)
+    study(hand_model.load_mesh(), **kw)
