@@ -1445,6 +1445,97 @@ int shr_pose_lm_seq_step(void *state, const double *A, const double *g, const do
                          float *trial_out, float *params, float *cost /* [S] */, float *cost0 /* [S] */, void *workspace,
                          void *stream);
 
+/* The constant-velocity term of the sequence fit and the block-pentadiagonal step ----------------------------------------------
+ * shr_sphere_temporal_normal penalises the first difference c_j(t + 1) - c_j(t): motion itself, so it lags a hand that
+ * really moves.  What a tracker carries instead is a constant-velocity prior, the SECOND difference
+ * a = (c_j(k - 1) + c_j(k + 1)) - 2 c_j(k): zero on a hand that moves steadily, and a frame without data is interpolated
+ * from both neighbours.  The energy is of the family of network/util_modules.py:349-381 (ClampedL2lLoss,
+ * TemporalSmoothnessLoss), one difference further; the reference has no counterpart of this term, of its normal
+ * equations or of the solve.  A row couples THREE frames, so the normal equations of a sequence gain a second
+ * off-diagonal block F and are block-PENTADIAGONAL: shr_pose_lm_seq_step cannot take them.
+ * Layout: shr_sphere_temporal_normal's, B = S T, the frames of a sequence adjacent.  One evaluation of the fit is
+ *   ... -> shr_sphere_temporal_normal(accumulate = 1) -> shr_sphere_accel_normal(accumulate = 1, accumulate_E = 1 iff the
+ *   first-difference entry was launched) -> shr_pose_lm_seq2_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_sphere_accel_normal   the normal equations of 1/2 w sum min(n2, acc_max^2) with respect to the 26 T parameters of
+ *       a sequence.  keypoints[B,J,4] and jac[B,3J,26]: shr_pose_keypoints_jacobian's outputs for the trial poses, in the
+ *       MODEL frame (component 3 is not read).  A triple is centred at frame k of its sequence, 1 <= k <= T - 2;
+ *       triple_weight[B] or NULL (1): entry k weighs the triple centred at k; the first and last entry of a sequence are
+ *       not read.  A triple whose weight is not > 0 (0, negative, a NaN) has no term.  w_k = (double)accel_weight
+ *       (double)triple_weight[k].
+ *       The term.  Per triple with a weight and per sphere j, in fp64 from the fp32 values:
+ *       a = (c_j(k - 1) + c_j(k + 1)) - 2 c_j(k), n2 = (a0 a0 + a1 a1) + a2 a2.  A NaN n2 gives NO term: no cost, no row.
+ *       Otherwise the cost term is min(n2, cap2), cap2 = (double)acc_max (double)acc_max, and the sphere gives THREE rows
+ *       iff n2 < cap2: exactly acc_max is saturated, +inf never saturates, and a = 0 still gives rows.  The row of axis x
+ *       has +jac(k - 1)[3j + x, :] in frame k - 1's columns, -2 jac(k)[3j + x, :] in frame k's and +jac(k + 1)[3j + x, :]
+ *       in frame k + 1's; its residual is a_x.
+ *       Outputs.  With G_j(x, y) = Jc_j(x)^T Jc_j(y), S_k the spheres with rows of triple k and w_k = 0 outside
+ *       1 ... T - 2, frame b receives
+ *         A[b] = (w_{b-1} sum_{S_{b-1}} G_j(b, b) + (4 w_b) sum_{S_b} G_j(b, b)) + w_{b+1} sum_{S_{b+1}} G_j(b, b), three
+ *                separate chains;
+ *         g[b] = (w_{b-1} sum Jc_j(b)^T a_j(b - 1) - (2 w_b) sum Jc_j(b)^T a_j(b)) + w_{b+1} sum Jc_j(b)^T a_j(b + 1), the
+ *                gradient of 1/2 the cost in the family's convention, so that the entries' A and g add;
+ *         E[b] = (0 - (2 w_b) sum_{S_b} G_j(b, b + 1)) - (2 w_{b+1}) sum_{S_{b+1}} G_j(b, b + 1): frame b's rows, frame
+ *                b + 1's columns;
+ *         F[b] = w_{b+1} sum_{S_{b+1}} G_j(b, b + 2): frame b's rows, frame b + 2's columns.
+ *       cost[B]: a triple's cost w sum_j min(n2, cap2) belongs to its LAST frame, k + 1.  count[B] int32: the spheres with
+ *       rows of the triple centred at b - 1, 0 at the first two frames of a sequence; whatever accel_weight.
+ *       accumulate governs A, g and cost as in shr_sphere_temporal_normal: 0 writes the term's (exact +0 where a frame has
+ *       no weighted triple); 1 ADDS it, the LOWER triangle of A is read and the sum written to both triangles, so A stays
+ *       bit-symmetric, and a frame none of whose triples has a weight -- every frame when accel_weight == 0 or T <= 2 -- is
+ *       not touched.  accumulate_E == 0 writes E, an exact +0 where the frame has no term; accumulate_E == 1 adds the
+ *       term to what E holds (shr_sphere_temporal_normal's E), a frame without a term left alone.  F is ALWAYS WRITTEN,
+ *       NEVER accumulated: an exact +0 for the last two frames of a sequence, for a triple without a weight and when
+ *       accel_weight == 0.
+ *       Summation order (the contract): fixed-order fp64 chains, no atomics, nothing contracted.  Every sum over the
+ *       spheres is a chain from 0 over the spheres with rows, ascending; a sphere's term is its three axes in ascending
+ *       order, ((x0 y0 + x1 y1) + x2 y2).  Bitwise reproducible; a sequence does not depend on the other sequences of the
+ *       batch; the launch shape is one workgroup per frame; no host synchronisation.
+ *       workspace: none is needed; shr_sphere_accel_normal_workspace_bytes(B, T, J) is 0 (-1 on a negative size).
+ *   Argument rules, checked before the B == 0 no-op: shr_sphere_temporal_normal's -- 1 <= J, 1 <= T, B >= 0 and
+ *   B % T == 0, acc_max >= 0 (+inf allowed), accel_weight finite and >= 0, accumulate and accumulate_E 0 or 1 (SHR_EINVAL
+ *   otherwise); J above 64, B above 65535: SHR_ETOOLARGE.  NULLs other than triple_weight and workspace, and misaligned
+ *   pointers (4 bytes; A, g, E, F, cost 8; keypoints, workspace 16): SHR_EINVAL.
+ *   shr_pose_lm_seq2_begin, shr_pose_lm_seq2_step   shr_pose_lm_seq_begin / shr_pose_lm_seq_step's contract word for word
+ *       with one more argument F [B,26,26] after E: the bookkeeping per sequence, the cost chain, the accept rule, lambda,
+ *       cost0 and trial_out = p for the whole sequence on a pivot that is not positive and finite ANYWHERE in it are
+ *       unchanged.  state: shr_pose_lm_seq2_state_bytes(B) = 16 960 B bytes (2120 doubles per frame: shr_pose_lm_seq_step's
+ *       state of the B frames, 1440 doubles each -- the accepted pose's A, E, g, the pose, params0, and in a sequence's
+ *       first frame its total cost, lambda and counters -- FOLLOWED by the accepted F of the B frames, 680 doubles each);
+ *       workspace: shr_pose_lm_seq2_workspace_bytes(B) = 16 512 B bytes (2064 doubles per frame: shr_pose_lm_seq_step's
+ *       workspace of the B frames, 1384 doubles each -- L_t, W_t, y_t -- followed by V_t of the B frames, 680 doubles
+ *       each), needed with solve != 0; both 8-byte aligned, every part a multiple of 8 doubles per frame, -1 for B < 0.
+ *       A state belongs to the B it began with.  F and V_t stand behind, not inside, the frames' records so that a step
+ *       without F can be handed to shr_pose_lm_seq_step as it is.
+ *       The solve, on the accepted equations: diagonal blocks M_t + lambda diag(M_t), M_t = A_t + diag(mu), blocks E_t at
+ *       (t, t + 1) and F_t at (t, t + 2), right-hand side r_t = -(g_t + mu (p_t - prior_t)), by block Cholesky with
+ *       bandwidth two, forward over t:
+ *         D_t = (M_t + lambda diag M_t) - W_{t-1} W_{t-1}^T - V_{t-2} V_{t-2}^T, per entry the W product subtracted first
+ *               and then the V product, each m ascending, then the column recurrence of shr_pose_lm_step; L_t L_t^T = D_t;
+ *         L_t y_t = r_t - W_{t-1} y_{t-1} - V_{t-2} y_{t-2};
+ *         W_t = (E_t^T - V_{t-1} W_{t-1}^T) L_t^-T (t <= T - 2), V_t = F_t^T L_t^-T (t <= T - 3), 26 triangular solves each;
+ *       backward: L_t^T x_t = y_t - W_t^T x_{t+1} - V_t^T x_{t+2}.  All fp64, every sum in index order, the W term before
+ *       the V term.  F of the last two frames and E of the last frame of a sequence are not read.  One workgroup per
+ *       sequence.
+ *       F == NULL is allowed at any T: the call IS shr_pose_lm_seq_step's, so every output and the state's pose are
+ *       shr_pose_lm_seq_step's BIT FOR BIT -- with T == 1 shr_pose_lm_step's (E may then be NULL too).  Give F in every
+ *       step of a loop or in none: a step without F solves the accepted equations without their F.
+ *   Argument rules: shr_pose_lm_seq_begin / _step's; F 8-byte aligned. */
+long long shr_sphere_accel_normal_workspace_bytes(int B, int T, int J);
+int shr_sphere_accel_normal(const float *keypoints /* [B,J,4]: shr_pose_keypoints_jacobian's, MODEL frame */,
+                            const float *jac       /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                            const float *triple_weight /* [B] or NULL */, float accel_weight, float acc_max,
+                            int B, int T, int J, int accumulate, int accumulate_E,
+                            double *A, double *g, double *E, double *F /* [B,26,26] */, double *cost, int32_t *count /* [B] */,
+                            void *workspace, void *stream);
+long long shr_pose_lm_seq2_state_bytes(int B);
+long long shr_pose_lm_seq2_workspace_bytes(int B);
+int shr_pose_lm_seq2_begin(const float *params0, int B, int T, float lambda0, void *state, float *trial, void *stream);
+int shr_pose_lm_seq2_step(void *state, const double *A, const double *g, const double *E, const double *F /* or NULL */,
+                          const double *cost_data, const float *trial, const float *prior, const float *stiffness, int solve,
+                          int B, int T, float *trial_out, float *params, float *cost /* [S] */, float *cost0 /* [S] */,
+                          void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2815,6 +2815,142 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
     current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a graph.
     Without a weighted temporal term (temporal_weight = 0 or seq_len = 1) no launch of the temporal entry is issued and E
     is zero; with seq_len = 1 the loop is sphere_icp_priors bit for bit."""
+    return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
+                                 fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
+                                 keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
+                                 temporal_weight, ts_max, frame_weight, 0.0, float("inf"), None)
+
+
+def _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight):
+    accel_weight, acc_max = float(accel_weight), float(acc_max)
+    if not (accel_weight >= 0.0 and accel_weight < float("inf")):
+        raise RuntimeError("accel_weight must be finite and >= 0, not %r" % (accel_weight,))
+    if not acc_max >= 0.0:
+        raise RuntimeError("acc_max must be >= 0 (inf: no saturation), not %r" % (acc_max,))
+    if triple_weight is not None:
+        _check_input(triple_weight, "triple_weight")
+        if tuple(triple_weight.shape) != (B,) or triple_weight.device != dev:
+            raise RuntimeError("triple_weight must be [B] on the parameters' device")
+    return accel_weight, acc_max
+
+
+def sphere_accel_normal(params, offset, offset_inv, bone, wv, seq_len, right_hand=True, accel_weight=1.0, acc_max=float("inf"),
+                        triple_weight=None, accumulate_into=None, accumulate_E_into=None):
+    """The normal equations of the sphere fit's constant-velocity term (include/spherehand_hip.h, shr_sphere_accel_normal):
+    params [B,26], B = S seq_len frames with the frames of a sequence adjacent, the key-point tables of
+    pose_keypoints_jacobian -> (A [B,26,26] the diagonal blocks, g [B,26], E [B,26,26] (frame t's rows, frame t + 1's
+    columns), F [B,26,26] (frame t's rows, frame t + 2's columns; +0 for the last two frames of a sequence), cost [B] fp64 (a
+    triple's cost at its last frame), count [B] int32: the spheres with rows of the triple ending at the frame).  The term is
+    accel_weight triple_weight[k] sum_j min(|c_j(k - 1) - 2 c_j(k) + c_j(k + 1)|, acc_max)^2 over the model-frame centres;
+    triple_weight [B] >= 0 (None: 1) weighs the triple centred at k.  accumulate_into = (A, g, cost) of the other terms at
+    the same poses: the term is ADDED to them in place (a frame without a weighted triple is not touched) and they are the
+    A, g, cost returned.  accumulate_E_into = E of shr_sphere_temporal_normal at the same poses: the term's E is added to
+    it in place.  F is always new.  Two launches: shr_pose_keypoints_jacobian -> shr_sphere_accel_normal."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv, "parameters")
+    dev = params.device
+    if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
+        raise RuntimeError("every tensor must be on the parameters' device")
+    T = _sphere_temporal_args(B, dev, seq_len, 0.0, 0.0, None)[0]
+    accel_weight, acc_max = _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight)
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+    E = accumulate_E_into
+    for t, name, shape in (() if accumulate_into is None else ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,)))) + \
+            (() if E is None else ((E, "E", (B, 26, 26)),)):
+        _check_input(t, name, torch.float64)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("the %s to accumulate into must be %s fp64 on the parameters' device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        if E is None:
+            E = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        F = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        _lib.check(lib.shr_sphere_accel_normal(_ptr(kp), _ptr(jac), _ptr(triple_weight), accel_weight, acc_max, B, T, J,
+                                               int(accumulate_into is not None), int(accumulate_E_into is not None), _ptr(A),
+                                               _ptr(g), _ptr(E), _ptr(F), _ptr(cost), _ptr(count), None, _stream()),
+                   "shr_sphere_accel_normal")
+    return A, g, E, F, cost, count
+
+
+def pose_lm_seq2_begin(params0, seq_len, lambda0=1e-3):
+    """pose_lm_seq_begin for the block-pentadiagonal step (shr_pose_lm_seq2_begin): params0 [B,26], B = S seq_len ->
+    (state, trial [B,26])."""
+    _check_input(params0, "start parameters")
+    if params0.dim() != 2 or params0.shape[1] != 26:
+        raise RuntimeError("start parameters must be [B,26]")
+    if not float(lambda0) > 0:
+        raise RuntimeError("lambda0 must be > 0")
+    B = params0.shape[0]
+    T = _sphere_temporal_args(B, params0.device, seq_len, 0.0, 0.0, None)[0]
+    lib = _lib.lib()
+    with _on(params0.device):
+        state = torch.empty((max(1, lib.shr_pose_lm_seq2_state_bytes(B) // 8),), dtype=torch.float64, device=params0.device)
+        trial = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
+        _lib.check(lib.shr_pose_lm_seq2_begin(_ptr(params0), B, T, float(lambda0), _ptr(state), _ptr(trial), _stream()),
+                   "shr_pose_lm_seq2_begin")
+    return state, trial
+
+
+def pose_lm_seq2_step(state, A, g, E, F, cost_data, trial, seq_len, prior=None, stiffness=None, solve=True, out=None,
+                      workspace=None):
+    """pose_lm_seq_step with the second off-diagonal blocks F [B,26,26] (frame t's rows, frame t + 2's columns) after E
+    (shr_pose_lm_seq2_step): the step is from the block-PENTAdiagonal solve.  F None: no second band, and every output is
+    pose_lm_seq_step's bit for bit.  state: pose_lm_seq2_begin's; workspace: shr_pose_lm_seq2_workspace_bytes(B) bytes to use
+    instead of a new buffer."""
+    _check_input(trial, "trial")
+    B = trial.shape[0]
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    T = _sphere_temporal_args(B, trial.device, seq_len, 0.0, 0.0, None)[0]
+    if E is None and T > 1:
+        raise RuntimeError("E is needed with seq_len > 1")
+    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26)),
+                           (F, "F", (B, 26, 26)), (cost_data, "cost_data", (B,))):
+        if t is None:
+            continue
+        _check_input(t, name, torch.float64)
+        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    lib = _lib.lib()
+    if state.numel() * 8 < lib.shr_pose_lm_seq2_state_bytes(B):
+        raise RuntimeError("state is pose_lm_seq2_begin's, for the same B")
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+    S = B // T
+    with _on(trial.device):
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
+            out = (new(B, 26) if solve else None, new(B, 26), new(S), new(S))
+        if workspace is None and solve:
+            workspace = torch.empty((max(1, lib.shr_pose_lm_seq2_workspace_bytes(B) // 8),), dtype=torch.float64,
+                                    device=trial.device)
+        trial_out, params, cost, cost0 = out
+        _lib.check(lib.shr_pose_lm_seq2_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(F), _ptr(cost_data), _ptr(trial),
+                                             _ptr(prior), _ptr(stiffness), int(bool(solve)), B, T,
+                                             _ptr(trial_out) if solve else None, _ptr(params), _ptr(cost), _ptr(cost0),
+                                             _ptr(workspace) if solve else None, _stream()), "shr_pose_lm_seq2_step")
+    return (trial_out if solve else None), params, cost, cost0
+
+
+def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model, fg_max,
+                          max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background, keypoints, confidence,
+                          kp_weight, kp_max, limits, limit_weight, collision, collision_weight, temporal_weight, ts_max,
+                          frame_weight, accel_weight, acc_max, triple_weight):
+    """The loop of sphere_icp_sequence and sphere_icp_trajectory.  Without a weighted acceleration term (accel_weight = 0 or
+    seq_len < 3) it is sphere_icp_sequence's: shr_pose_lm_seq_begin / _step, no F; with one, shr_sphere_accel_normal follows
+    the first-difference entry and the step is shr_pose_lm_seq2_begin / _step's."""
     B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
                                                     max_dist, "start parameters")
     max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
@@ -2827,10 +2963,12 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
     collide = K > 0 and collision_weight > 0.0
     T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
     temporal = T > 1 and temporal_weight > 0.0
+    accel_weight, acc_max = _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight)
+    accel = T > 2 and accel_weight > 0.0
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
-    state, trial = pose_lm_seq_begin(params0, T, lambda0)
+    state, trial = (pose_lm_seq2_begin if accel else pose_lm_seq_begin)(params0, T, lambda0)
     if prior is not None:
         _check_input(prior, "prior")
         if tuple(prior.shape) != (B, 26):
@@ -2847,15 +2985,17 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
         kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
         A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
-        E = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)       # (stays zero without the temporal entry)
+        E = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)       # (stays zero without a term between frames)
+        F = f64(B, 26, 26) if accel else None
         model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
         prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
         pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
         temporal_rows = torch.empty((B,), dtype=torch.int32, device=dev) if temporal else None
+        accel_rows = torch.empty((B,), dtype=torch.int32, device=dev) if accel else None
         params, cost0, cost = f32(B, 26), f32(S), f32(S)
         ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
                               lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
-        seq_ws = f64(max(1, lib.shr_pose_lm_seq_workspace_bytes(B) // 8))
+        seq_ws = f64(max(1, (lib.shr_pose_lm_seq2_workspace_bytes if accel else lib.shr_pose_lm_seq_workspace_bytes)(B) // 8))
         stream = _stream()
         for it in range(iters + 1):
             _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
@@ -2882,12 +3022,38 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
                 _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T,
                                                           J, 1, _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(temporal_rows),
                                                           None, stream), "shr_sphere_temporal_normal")
+            if accel:                                          # (without the first-difference entry E is this entry's alone)
+                _lib.check(lib.shr_sphere_accel_normal(_ptr(kp), _ptr(jac), _ptr(triple_weight), accel_weight, acc_max, B, T, J,
+                                                       1, int(temporal), _ptr(A), _ptr(g), _ptr(E), _ptr(F), _ptr(cost_data),
+                                                       _ptr(accel_rows), None, stream), "shr_sphere_accel_normal")
             solve = int(it < iters)
-            _lib.check(lib.shr_pose_lm_seq_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(trial), _ptr(prior),
-                                                _ptr(stiffness), solve, B, T, _ptr(trial) if solve else None, _ptr(params),
-                                                _ptr(cost), _ptr(cost0), _ptr(seq_ws) if solve else None, stream),
-                       "shr_pose_lm_seq_step")
+            tail = (_ptr(cost_data), _ptr(trial), _ptr(prior), _ptr(stiffness), solve, B, T, _ptr(trial) if solve else None,
+                    _ptr(params), _ptr(cost), _ptr(cost0), _ptr(seq_ws) if solve else None, stream)
+            if accel:
+                _lib.check(lib.shr_pose_lm_seq2_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(F), *tail), "shr_pose_lm_seq2_step")
+            else:
+                _lib.check(lib.shr_pose_lm_seq_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), *tail), "shr_pose_lm_seq_step")
     return params, cost0, cost
+
+
+def sphere_icp_trajectory(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand=True,
+                          pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                          stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
+                          keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
+                          collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None,
+                          accel_weight=1.0, acc_max=float("inf"), triple_weight=None):
+    """sphere_icp_sequence with the constant-velocity term: the energy of a sequence gains
+    accel_weight sum_k triple_weight[k] sum_j min(|c_j(k - 1) - 2 c_j(k) + c_j(k + 1)|, acc_max)^2 over its triples of
+    consecutive frames -> (params [B,26], cost0 [S], cost [S]).  Each of the iters + 1 evaluations is sphere_icp_sequence's
+    launches up to shr_sphere_temporal_normal, then shr_sphere_accel_normal (accumulate = 1; accumulate_E = 1 iff the
+    first-difference entry was launched in this evaluation), then shr_pose_lm_seq2_step (the block-pentadiagonal solve), on
+    torch's current stream, into buffers allocated once before the loop; nothing returns to the host: capturable in a
+    graph.  Without a weighted acceleration term (accel_weight = 0 or seq_len < 3) no launch of the entry is issued and F is
+    not formed: the loop is then sphere_icp_sequence's own, launch for launch."""
+    return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
+                                 fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
+                                 keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
+                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight)
 
 
 def _depth_normals_args(depth, scale, max_step):

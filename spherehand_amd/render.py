@@ -1162,6 +1162,74 @@ class SphereSequencePoseFitter(SphereCollisionPoseFitter):
                                           self.ts_max, self._frame_weight(frame_weight), (A, g, cost))
 
 
+class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
+    """SphereSequencePoseFitter with a constant-velocity term: the energy of a sequence gains
+        accel_weight sum_k triple_weight[k] sum_j min(|c_j(k - 1) - 2 c_j(k) + c_j(k + 1)|, acc_max)^2
+    over its triples of consecutive frames (ops.sphere_icp_trajectory; include/spherehand_hip.h, shr_sphere_accel_normal
+    and shr_pose_lm_seq2_step).  The second difference is zero on a hand that moves steadily, where the first difference
+    of SphereSequencePoseFitter penalises motion itself; the energy is of the family of network/util_modules.py:349-381, the
+    reference has no counterpart of the term.  A row couples three frames, so the normal equations of a sequence are
+    block-pentadiagonal.
+        solve(observed, params0, view=None, prior=None, keypoints=None, confidence=None, frame_weight=None,
+              triple_weight=None) -> (params [B,26], cost0 [S], cost [S])
+        normal_equations(observed, params, view=None, keypoints=None, confidence=None, frame_weight=None,
+                         triple_weight=None)
+            -> (A, g, E, F, cost, count [B]) of the SUM of the seven terms' A, g, cost and E; F [B,26,26] (frame t's rows,
+               frame t + 2's columns) and count (the spheres with rows of the triple ending at the frame) are the new
+               term's own
+    triple_weight [B] >= 0 weighs the triple centred at k (None: 1): 0 at the two frames around a scene change cuts the
+    sequence there.  With accel_weight = 0 (or seq_len < 3) it is SphereSequencePoseFitter bit for bit.  The defaults
+    (accel_weight 0.1, acc_max 20 mm, temporal_weight 0: the first-difference term is OFF) come from DESIGN.md 4.4u's
+    study on three sequences of eight frames: that row is the only one at or below the frame-by-frame fit's keypoint error
+    on steady motion (0.40 against 0.44 mm, jitter 0.49 against 0.73 mm) and stays beside it where the motion turns (0.45
+    against 0.41 mm), where SphereSequencePoseFitter's default gives 1.64 mm.  What the term does NOT fix: a finger hidden
+    for two frames stays 37 mm off (acc_max cuts the term exactly there; acc_max = inf brings it to 26 mm, no better than
+    the first difference, and costs 2.2 mm where the motion turns); weights of 1 and above wreck the fit; a real
+    acceleration is penalised; one rejected frame rejects its whole sequence.  Everything else is SphereSequencePoseFitter's:
+    a refinement from a start pose, one accept decision per sequence, NO autograd through the solve, the rotation
+    NOT checked."""
+
+    # DESIGN.md 4.4u: the study's row
+    DEFAULT_TEMPORAL_WEIGHT = 0.0
+    DEFAULT_ACCEL_WEIGHT = 0.1
+    DEFAULT_ACC_MAX = 20.0
+
+    def __init__(self, mesh, width, height, seq_len, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3,
+                 stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None,
+                 max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
+                 collision_weight=None, min_dist=None, radius_scale=None, temporal_weight=None, ts_max=None,
+                 accel_weight=None, acc_max=None):
+        super().__init__(mesh, width, height, seq_len, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
+                         render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits, collision_weight,
+                         min_dist, radius_scale, temporal_weight, ts_max)
+        self.accel_weight = float(self.DEFAULT_ACCEL_WEIGHT if accel_weight is None else accel_weight)
+        self.acc_max = float(self.DEFAULT_ACC_MAX if acc_max is None else acc_max)
+        if not (self.accel_weight >= 0.0 and self.accel_weight < float("inf")) or not self.acc_max >= 0.0:
+            raise ValueError("accel_weight must be finite and >= 0, acc_max >= 0")
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None, frame_weight=None,
+              triple_weight=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        return ops.sphere_icp_trajectory(observed, view, params0.detach().contiguous().float(), *self._tables(), self.seq_len,
+                                         self.right_hand, self.pixel_to_model, self.fg_max, self.max_dist, self.iters,
+                                         self.lambda0, self.stiffness,
+                                         None if prior is None else prior.detach().contiguous().float(), self.render_weight,
+                                         self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
+                                         limits, self.limit_weight, self._pairs(), self.collision_weight, self.temporal_weight,
+                                         self.ts_max, self._frame_weight(frame_weight), self.accel_weight, self.acc_max,
+                                         self._frame_weight(triple_weight))
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, frame_weight=None,
+                         triple_weight=None):
+        params = params.detach().contiguous().float()
+        A, g, E, cost, _ = SphereSequencePoseFitter.normal_equations(self, observed, params, view, keypoints, confidence,
+                                                                     frame_weight)
+        return ops.sphere_accel_normal(params, *self._tables()[:4], self.seq_len, self.right_hand, self.accel_weight,
+                                       self.acc_max, self._frame_weight(triple_weight), (A, g, cost), E)
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster

@@ -1,0 +1,542 @@
+"""The constant-velocity term of the sequence fit and the block-pentadiagonal step without a device: the entries of the C ABI
+with their argument rules, the new units' code-object metadata, the restatement (tests/sphere_trajectory_ref.py) and what
+keeps it honest -- its g is the reverse-mode gradient of 1/2 cost, the header's chains equal the blocks autograd gives, the
+block solve equals a dense solve, without F it is sphere_sequence_ref's step and loop exactly -- and the fp32 bars the GPU
+tests (tests/test_sphere_trajectory_gpu.py) hold the kernels to."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import pose_icp_ref as ref
+import sphere_collision_ref as cref
+import sphere_sequence_ref as qref
+import sphere_trajectory_ref as tref
+from conftest import ROOT
+from test_pose_ik_cpu import _metadata
+
+ENTRIES = ("shr_sphere_accel_normal_workspace_bytes", "shr_sphere_accel_normal", "shr_pose_lm_seq2_state_bytes",
+           "shr_pose_lm_seq2_workspace_bytes", "shr_pose_lm_seq2_begin", "shr_pose_lm_seq2_step")
+INF = float("inf")
+
+# The fp32 bars, by DESIGN.md 4.4p's method: the restatement run with an fp32 chain against the fp64 one on the GPU tests'
+# inputs (EVALUATIONS below), the largest deviation per quantity; the GPU tolerance is 4 x that.  A, g, E and F are compared
+# GIVEN THE SAME model-frame centres (the fp64 run's, rounded once), so that both runs hold the same spheres with rows and
+# the same a, as the kernel and the restatement do: what differs is the Jacobian (sphere_trajectory_ref.chain on each).
+# test_fp32_bars measures them again and holds the constants to within [1/2, 2].
+FP32_A_DEVIATION = 3.62e-7        # max |A32 - A64| / max |A64| per frame with rows
+FP32_G_DEVIATION = 5.06e-7        # max |g32 - g64| / max |g64| per frame with rows
+FP32_E_DEVIATION = 2.55e-7        # max |E32 - E64| / max |E64| per frame with a term
+FP32_F_DEVIATION = 2.50e-7        # max |F32 - F64| / max |F64| per frame that is the first of a weighted triple
+FP32_COST_DEVIATION = 1.36e-7     # |cost32 - cost64| / cost64 per sequence of the two runs' own centres, the combined cost
+FP32_STEP_DEVIATION = 7.25e-5     # rad | mm: the first step of the combined trajectory fit at params0
+FP32_POSE_DEVIATION = 4.25e-5     # rad | mm: the final pose of the end-to-end case, every sequence
+# The chains against autograd's blocks given the fp64 chain's Jacobian, of the largest entry: measured 1.3e-15
+# (test_chains_give_the_autograd_blocks prints it), asserted at 4 x.  4.4t's two-frame term measured 3e-16; this one sums three
+# chains per entry and the centre's block carries the factor 4, so its rounding is that much larger.
+CHAIN_DEVIATION = 1.3e-15
+ORDER_BAR = 4 * CHAIN_DEVIATION
+# The block solve against numpy.linalg.solve of the dense 26 T x 26 T system on SOLVE_CASES, max |x_block - x_dense| /
+# max |x_dense| per sequence, measured (test_block_solve_equals_the_dense_solve prints it); asserted at 4 x.
+BLOCK_DENSE_DEVIATION = 3.6e-13
+A_BAR, G_BAR, E_BAR, F_BAR, COST_BAR, STEP_BAR, POSE_BAR = (4 * d for d in (
+    FP32_A_DEVIATION, FP32_G_DEVIATION, FP32_E_DEVIATION, FP32_F_DEVIATION, FP32_COST_DEVIATION, FP32_STEP_DEVIATION,
+    FP32_POSE_DEVIATION))
+TEMPORAL_WEIGHT, ACCEL_WEIGHT, ACC_MAX = tref.DEFAULT_TEMPORAL_WEIGHT, tref.DEFAULT_ACCEL_WEIGHT, tref.DEFAULT_ACC_MAX
+# The evaluations the GPU test of the equations runs and the bars are measured on: (S, T, table, accel_weight, acc_max,
+# triple weights or None).  T = 3 has one triple per sequence; T = 4 is the smallest T at which one E block collects from two
+# triples and F and E are both non-zero; the finite acc_max saturate some spheres of the noisy starts and keep others.
+EVALUATIONS = ((2, 1, "hand", 1.0, INF, False), (2, 2, "synthetic", 1.0, INF, False), (2, 3, "hand", 0.5, INF, False),
+               (2, 3, "synthetic", 1.0, 30.0, False), (2, 4, "hand", 2.0, 30.0, False), (2, 4, "synthetic", 1.0, INF, True),
+               (2, 8, "hand", 0.1, 30.0, True), (2, 8, "synthetic", 1.0, 40.0, False))
+SOLVE_CASES = ((2, 3, "hand"), (2, 4, "synthetic"), (2, 5, "hand"), (1, 8, "hand"))
+# The end-to-end case: two sequences of five frames of sphere_sequence_ref.sequence_case, four iterations.  Four iterations
+# do not converge, and some draws amplify rounding through the loop, so that what an fp32 chain leaves is chance (DESIGN.md
+# 4.4u has seed 31's figures).  The case is a draw without that property: a perturbation of the start by 1e-9, with either
+# sign, moves no parameter of either sequence of the fp64 restatement by more than END_TO_END_STABLE, four fp32 steps of
+# the trial (the trial is rounded to fp32 after every step, a translation of 50 mm in steps of 3.8e-6).
+# test_end_to_end_case_is_stable holds that.
+END_TO_END = (2, 5, "hand", 33)
+END_TO_END_STABLE = 4 * 2.0 ** -18
+
+
+def triple_weights(B, T, on):
+    """[B] fp32 in [0.5, 1.5) with one triple per batch at 0 (a cut) where T allows, or None."""
+    if not on:
+        return None
+    fw = (0.5 + torch.rand(B, generator=torch.Generator().manual_seed(5))).numpy().astype(np.float32)
+    if T > 3:
+        fw[2] = 0.0
+    return fw
+
+
+@pytest.fixture(scope="module")
+def mesh():
+    from spherehand_amd import hand_model
+    return hand_model.load_mesh()
+
+
+def test_header_loader_and_library_have_the_entries():
+    from spherehand_amd import _lib, build
+    text = open(os.path.join(ROOT, "include", "spherehand_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    h = ctypes.CDLL(build.build())
+    for name in ENTRIES:
+        assert re.search(r"\b%s\s*\(" % name, src), name
+        assert name in _lib.SIGNATURES and hasattr(h, name), name
+    contract = text[text.index("The constant-velocity term of the sequence fit"):
+                    text.index("long long shr_sphere_accel_normal_workspace_bytes(")]
+    for cite in ("network/util_modules.py:349-381", "no counterpart", "block-PENTADIAGONAL", "MODEL frame",
+                 "exactly acc_max is saturated", "+inf never saturates", "a = 0 still gives rows", "NO term",
+                 "ALWAYS WRITTEN,\n *       NEVER accumulated", "exact +0", "LOWER triangle", "bit-symmetric", "not touched", "no atomics",
+                 "nothing contracted", "65535", "B % T == 0", "LAST frame", "one workgroup per frame", "One workgroup per\n *       sequence",
+                 "BIT FOR BIT", "16 960", "16 512", "ANYWHERE", "F == NULL is allowed at any T", "the W term before"):
+        assert cite in contract, cite
+    assert text.index("int shr_pose_lm_seq_step(") < text.index("shr_sphere_accel_normal(")     # at the end of the header
+    lib = _lib.lib()
+    assert lib.shr_abi_version() == _lib.ABI_VERSION == 23
+    ws = lib.shr_sphere_accel_normal_workspace_bytes
+    assert ws(24, 8, 41) == 0 and ws(0, 0, 0) == 0 and ws(-1, 1, 1) == -1 and ws(1, -1, 1) == -1 and ws(1, 1, -1) == -1
+    assert lib.shr_pose_lm_seq2_state_bytes(3) == 3 * 2120 * 8 and lib.shr_pose_lm_seq2_state_bytes(-1) == -1
+    assert lib.shr_pose_lm_seq2_workspace_bytes(3) == 3 * 2064 * 8 and lib.shr_pose_lm_seq2_workspace_bytes(-1) == -1
+    assert lib.shr_pose_lm_seq2_state_bytes(0) == 0 and lib.shr_pose_lm_seq2_workspace_bytes(0) == 0
+    # the sequence step's own state and workspace, then F and V_t per frame, every part a multiple of 8 doubles
+    assert 2120 == 1440 + 680 and 2064 == 1384 + 680 and 680 >= 676 and 680 % 8 == 0
+    assert lib.shr_pose_lm_seq_state_bytes(3) == 3 * 1440 * 8 and lib.shr_pose_lm_seq_workspace_bytes(3) == 3 * 1384 * 8
+    # host-side argument rules (every call below returns before a launch)
+    P = 1 << 20                                                    # a 16-byte aligned stand-in for a device address
+    #          0 keypoints 1 jac 2 triple_weight | 3 accel_weight 4 acc_max | 5 B 6 T 7 J 8 accumulate 9 accumulate_E |
+    #          10 A 11 g 12 E 13 F 14 cost 15 count 16 workspace 17 stream
+    normal = [P] * 3 + [1.0, 20.0, 6, 3, 41, 1, 1] + [P] * 7 + [None]
+    bad = lambda i, val: lib.shr_sphere_accel_normal(*(normal[:i] + [val] + normal[i + 1:]))   # noqa: E731
+    assert bad(5, 0) == 0                                          # B == 0: nothing to do
+    required, optional = [0, 1, 10, 11, 12, 13, 14, 15], [2, 16]
+    for i in required:
+        assert bad(i, None) == -1, i
+    for i in required + optional:
+        assert bad(i, P + 2) == -1, i
+    for i in (0, 16, 10, 11, 12, 13, 14):                          # keypoints, workspace: 16 bytes; A, g, E, F, cost: 8
+        assert bad(i, P + 4) == -1, i
+    for i in (0, 16):
+        assert bad(i, P + 8) == -1, i
+    for i in (5, 6, 7):
+        assert bad(i, -1) == -1, i
+    assert bad(7, 0) == -1 and bad(6, 0) == -1                     # 1 <= J, 1 <= T
+    assert bad(6, 4) == -1 and bad(5, 7) == -1                     # B % T == 0
+    nan = float("nan")
+    assert bad(3, -0.5) == -1 and bad(3, INF) == -1 and bad(3, nan) == -1      # the weight: finite and >= 0
+    assert bad(4, -1.0) == -1 and bad(4, nan) == -1                # acc_max >= 0 ...
+    none = list(normal)
+    none[5], none[4] = 0, INF                                      # ... or +inf; the rules come before the no-op
+    assert lib.shr_sphere_accel_normal(*none) == 0
+    for i in (8, 9):                                               # both flags 0 or 1
+        assert bad(i, 2) == -1 and bad(i, -1) == -1
+        assert lib.shr_sphere_accel_normal(*(none[:i] + [2] + none[i + 1:])) == -1
+        assert lib.shr_sphere_accel_normal(*(none[:i] + [0] + none[i + 1:])) == 0
+    assert bad(5, 65536 - 65536 % 3 + 3) == -2 and bad(7, 65) == -2
+    none[7] = 65
+    assert lib.shr_sphere_accel_normal(*none) == -2
+    none[7], none[3] = 41, -1.0
+    assert lib.shr_sphere_accel_normal(*none) == -1
+    none[3], none[6] = 0.0, 0
+    assert lib.shr_sphere_accel_normal(*none) == -1
+    assert lib.shr_sphere_accel_normal(*([None] * 3 + [0.0, 0.0, 0, 1, 1, 0, 0] + [None] * 8)) == 0
+    #          0 params0 1 B 2 T 3 lambda0 4 state 5 trial 6 stream
+    begin = [P, 6, 3, 1e-3, P, P, None]
+    bad = lambda i, val: lib.shr_pose_lm_seq2_begin(*(begin[:i] + [val] + begin[i + 1:]))   # noqa: E731
+    assert bad(1, 0) == 0
+    for i in (0, 4, 5):
+        assert bad(i, None) == -1 and bad(i, P + 2) == -1, i
+    assert bad(4, P + 4) == -1                                     # the state: 8 bytes
+    assert bad(1, -3) == -1 and bad(2, 0) == -1 and bad(2, 4) == -1 and bad(3, 0.0) == -1 and bad(3, nan) == -1
+    assert bad(1, (1 << 24) + 2) == -2
+    assert lib.shr_pose_lm_seq2_begin(P, 0, 0, 1e-3, P, P, None) == -1        # the rules come before the no-op
+    #          0 state 1 A 2 g 3 E 4 F 5 cost_data 6 trial 7 prior 8 stiffness | 9 solve 10 B 11 T |
+    #          12 trial_out 13 params 14 cost 15 cost0 16 workspace 17 stream
+    step = [P] * 9 + [1, 6, 3] + [P] * 5 + [None]
+    bad = lambda i, val: lib.shr_pose_lm_seq2_step(*(step[:i] + [val] + step[i + 1:]))   # noqa: E731
+    assert bad(10, 0) == 0
+    for i in (0, 1, 2, 3, 5, 6, 12, 13, 14, 15, 16):
+        assert bad(i, None) == -1, i
+    for i in list(range(9)) + [12, 13, 14, 15, 16]:
+        assert bad(i, P + 2) == -1, i
+    for i in (0, 1, 2, 3, 4, 5, 16):                               # fp64 buffers: 8 bytes
+        assert bad(i, P + 4) == -1, i
+    assert bad(11, 4) == -1 and bad(11, 0) == -1 and bad(10, -3) == -1 and bad(10, (1 << 24) + 2) == -2
+    one = list(step)
+    one[3], one[4], one[10], one[11] = None, None, 0, 1            # E and F may be NULL with T == 1 (B = 0: no launch here)
+    assert lib.shr_pose_lm_seq2_step(*one) == 0
+    no_f = list(step)
+    no_f[4], no_f[10] = None, 0                                    # F may be NULL at any T
+    assert lib.shr_pose_lm_seq2_step(*no_f) == 0
+    nosolve = list(step)
+    nosolve[9], nosolve[12], nosolve[16], nosolve[10] = 0, None, None, 0      # without a solve: no trial_out, no workspace
+    assert lib.shr_pose_lm_seq2_step(*nosolve) == 0
+
+
+def test_units_compile_for_gfx950_without_scratch(tmp_path):
+    """sphere_accel.hip: one kernel, one workgroup of 256 threads per FRAME, no scratch, no spills, no atomics; three 192 x 26
+    fp32 Jacobians (3 x 19 968 bytes), the three triples' a [64 x 3] fp64, cost terms and flags in LDS: 66 816 bytes.
+    lm_seq2.hip: the step is one wave per SEQUENCE with A, L, W, two V blocks and the cross product [26 x 26] fp64, x, y, the
+    vector before it and the pivot in LDS: 33 080 bytes; begin uses none.  DESIGN.md 4.4u tables the figures.
+    sphere_accel.hip includes common.h alone, lm_seq2.hip lm_solve.h alone."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("### 4.4u"):design.index("### 4.5 ")]
+    assert design.index("### 4.4t") < design.index("### 4.4u")
+    sizes, kernels = _metadata("sphere_accel", tmp_path)
+    assert sizes == [0] and len(kernels) == 1
+    for name, k in kernels.items():
+        print(name, k)
+        assert "sphere_accel_kernel" in name and "sphere_accel_kernel" in section
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0
+        assert k["group_segment_fixed_size"] == 3 * 192 * 26 * 4 + 3 * 64 * 3 * 8 + 3 * 64 * 8 + 3 * 64 * 4 == 66816
+        # 38 and 58 as built; LDS already holds the kernel to two workgroups per CU, so no occupancy step is near: the
+        # ceilings only catch a change of code that costs registers
+        assert k["vgpr_count"] <= 42 and k["sgpr_count"] <= 64
+    sizes, kernels = _metadata("lm_seq2", tmp_path)
+    assert sizes == [0, 0] and len(kernels) == 2
+    for name, k in kernels.items():
+        print(name, k)
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0
+        if "step" in name:
+            assert "pose_lm_seq2_step_kernel" in name and "pose_lm_seq2_step_kernel" in section
+            assert k["group_segment_fixed_size"] == (6 * 26 * 26 + 3 * 26 + 1) * 8 == 33080
+            assert k["vgpr_count"] <= 64 and k["sgpr_count"] <= 90    # 62 and 86: lm_seq.hip's ceiling of 64 VGPRs holds
+        else:
+            assert "pose_lm_seq2_begin_kernel" in name and k["group_segment_fixed_size"] == 0 and k["vgpr_count"] <= 16
+    assert "66 816" in section and "33 080" in section
+    inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
+                                  open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
+    assert inc("sphere_accel.hip") == ["common.h"] and inc("lm_seq2.hip") == ["lm_solve.h"]
+    for unit in ("sphere_accel.hip", "lm_seq2.hip"):
+        assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
+
+
+def evaluation_inputs(mesh, S, T, table, weights_on):
+    case = qref.sequence_case(mesh, S, T, table)
+    return case, case["params0"].float().double(), triple_weights(S * T, T, weights_on)
+
+
+def test_g_is_the_autograd_gradient(mesh):
+    """g of the restatement (the Jacobian of the stacked residuals) = the reverse-mode gradient of 1/2 w sum min(n2, cap) through
+    pose_ik_ref.Chain, to 1e-12 of its largest entry; the sequence's 26 T x 26 T matrix is symmetric positive
+    semi-definite; cost and count are the triples' own, stored with the LAST frame; T <= 2 gives exact zeros."""
+    for S, T, table, w, cap, fw_on in EVALUATIONS:
+        case, p, fw = evaluation_inputs(mesh, S, T, table, fw_on)
+        m = case["model"]
+        n = tref.normal(m, p, T, w, cap, fw, chain_residual=True)
+        q = p.clone().requires_grad_(True)
+        cost = tref.energy(m, q, T, w, cap, fw, held=n["decided"])
+        (0.5 * cost.sum()).backward()
+        err, scale = (q.grad - n["g"]).abs().max().item(), n["g"].abs().max().item()
+        d = n["decided"]
+        print("S %d T %d %s acc_max %g: spheres with rows %s, saturated %d; |g - autograd| %.3g of %.3g"
+              % (S, T, table, cap, n["count"].tolist(), int((d["valid"] & ~d["act"]).sum()), err, scale))
+        assert err <= 1e-12 * max(scale, 1e-300)
+        assert torch.allclose(cost.detach(), n["cost"], rtol=1e-4, atol=0)     # (the contract's a is on the fp32 centres: a
+        # centre 100 mm out is rounded by 4e-6 mm, a second difference of a few mm by 1e-5 of itself at worst)
+        t = torch.arange(S * T) % T
+        assert not n["cost"][t < 2].any() and not n["count"][t < 2].any()
+        assert not n["E"][t == T - 1].any() and not n["F"][t >= T - 2].any()
+        if T <= 2:
+            assert not any(n[k].any() for k in ("A", "g", "E", "F", "cost", "count"))
+            continue
+        assert scale > 0 and int(n["count"].sum()) > 0
+        if cap < INF:
+            assert int((d["valid"] & ~d["act"]).sum()) > 0 and int(d["act"].sum()) > 0     # both sides of the cap are met
+        if T >= 4:
+            assert n["F"].any() and n["E"].any()
+        for s in range(S):
+            sl = slice(s * T, s * T + T)
+            H, _ = tref.dense_system(n["A"][sl], n["g"][sl], n["E"][sl], n["F"][sl], 0.0, np.zeros(26), p[sl], p[sl], T)
+            assert np.allclose(H, H.T, rtol=0, atol=1e-9 * np.abs(H).max())
+            assert np.linalg.eigvalsh(0.5 * (H + H.T))[0] >= -1e-9 * np.abs(H).max()
+
+
+def test_chains_give_the_autograd_blocks(mesh):
+    """A, g, E, F, cost and count of the header's chains (sphere_trajectory_ref.chain: +Jc, -2 Jc, +Jc, spheres ascending) equal
+    the blocks of autograd's J^T W J given the fp64 chain's Jacobian, to ORDER_BAR (4 x the measured 1.3e-15) of the largest entry.  A is bit-symmetric, F
+    of a sequence's last two frames, E of its last and both of a cut triple alone are exactly +0; accumulate = 1 adds to
+    what is there and leaves a frame without a weighted triple alone; accumulate_E = 1 adds to E; weight 0 or T <= 2
+    touches nothing."""
+    for S, T, table, w, cap, fw_on in EVALUATIONS:
+        case, p, fw = evaluation_inputs(mesh, S, T, table, fw_on)
+        m = case["model"]
+        _, jac = m.chain.jacobian(p)
+        c32 = m.centres(p).float().numpy()
+        A, g, E, F, cost, count = tref.chain(c32, jac.numpy(), T, w, cap, fw)
+        n = tref.normal(m, p, T, w, cap, fw, centres32=c32)
+        assert np.array_equal(A, A.transpose(0, 2, 1)) and np.array_equal(count, n["count"].numpy())
+        for name, x, y in (("A", A, n["A"]), ("g", g, n["g"]), ("E", E, n["E"]), ("F", F, n["F"]), ("cost", cost, n["cost"])):
+            scale = max(np.abs(x).max(), 1e-300)
+            dev = np.abs(x - y.numpy()).max() / scale
+            print("S %d T %d %s: %s chains against autograd %.3g" % (S, T, table, name, dev))
+            assert dev <= ORDER_BAR
+        t = np.arange(S * T) % T
+        for x, sel in ((E, t == T - 1), (F, t >= T - 2)):
+            assert not x[sel].any() and not np.signbit(x[sel]).any()
+        if T == 4:                                                 # frame 1's E collects from the triples centred at 1 and 2
+            both = tref.chain(c32, jac.numpy(), T, w, cap, None)[2][1]
+            first = tref.chain(c32, jac.numpy(), T, w, cap, np.array([1, 1, 0, 1] * S, np.float32))[2][1]
+            second = tref.chain(c32, jac.numpy(), T, w, cap, np.array([1, 0, 1, 1] * S, np.float32))[2][1]
+            assert first.any() and second.any() and np.allclose(both, first + second, rtol=0, atol=ORDER_BAR * np.abs(both).max())
+        if fw is not None and T > 3:                               # the triple centred at frame 2 is cut
+            assert count[3] == 0 and cost[3] == 0 and not F[1].any() and E[1].any() == bool(T > 3)
+        rng = np.random.default_rng(3)
+        base = (rng.standard_normal((S * T, 26, 26)), rng.standard_normal((S * T, 26)), rng.standard_normal(S * T))
+        base_E = rng.standard_normal((S * T, 26, 26))
+        A2, g2, E2, F2, cost2, _ = tref.chain(c32, jac.numpy(), T, w, cap, fw, into=base, into_E=base_E)
+        assert np.array_equal(F2, F) and np.array_equal(E2, base_E + E)
+        assert np.array_equal(A2, base[0] + A) and np.array_equal(g2, base[1] + g) and np.array_equal(cost2, base[2] + cost)
+        A0, g0, E0, F0, cost0, count0 = tref.chain(c32, jac.numpy(), T, 0.0, cap, fw, into=base, into_E=base_E)
+        assert np.array_equal(A0, base[0]) and np.array_equal(g0, base[1]) and np.array_equal(cost0, base[2])
+        assert np.array_equal(E0, base_E) and not F0.any() and np.array_equal(count0, count)
+        if T <= 2:
+            assert np.array_equal(A2, base[0]) and np.array_equal(g2, base[1]) and np.array_equal(cost2, base[2])
+            assert np.array_equal(E2, base_E) and not any(x.any() for x in (A, g, E, F, cost, count))
+
+
+def truncation_inputs():
+    """(centres [3,4,4], jac [3,12,26]) fp32, one triple: sphere 0 has a = (3, 4, 0), exactly 5 in fp32 and fp64; sphere 1
+    a = 0; sphere 2 a NaN centre; sphere 3 a = (0, 0.5, 0)."""
+    c = np.zeros((3, 4, 4), np.float32)
+    c[0, :, :3] = [(1.0, 2.0, 3.0), (0.5, 0.25, 0.0), (5.0, 5.0, 5.0), (7.0, 7.0, 7.0)]
+    c[1, :, :3] = [(0.0, 0.0, 0.0), (0.5, 0.25, 0.0), (5.0, 5.0, 5.0), (7.0, 7.0, 7.0)]
+    c[2, :, :3] = [(2.0, 2.0, -3.0), (0.5, 0.25, 0.0), (np.nan, 5.0, 5.0), (7.0, 7.5, 7.0)]
+    c[..., 3] = 1.0
+    return c, np.random.default_rng(0).standard_normal((3, 12, 26)).astype(np.float32)
+
+
+def test_truncation_rule():
+    """The kp_max rule of 4.4r on one triple: a second difference of (3, 4, 0), exactly 5, is saturated at acc_max = 5 and at
+    the fp32 below and has rows at the next fp32 above; a saturated sphere pays cap2 and the result is the call without it
+    plus that; a NaN centre gives no term; +inf never saturates; a = 0 still gives rows (of zero residual: A, E and F
+    without g)."""
+    c, jac = truncation_inputs()
+    up, down = np.nextafter(np.float32(5.0), np.float32(6.0)), np.nextafter(np.float32(5.0), np.float32(4.0))
+    for cap, rows, term0 in ((5.0, [False, True, False, True], 25.0), (down, [False, True, False, True], float(down) ** 2),
+                             (up, [True, True, False, True], 25.0), (INF, [True, True, False, True], 25.0)):
+        d = tref.decide(c, 3, cap)
+        assert d["act"][1].tolist() == rows and not d["act"][0].any() and not d["act"][2].any()
+        assert d["valid"][1].tolist() == [True, True, False, True] and d["n2"][1, 0] == 25.0
+        assert d["term"][1, 0] == term0 and d["term"][1, 1] == 0.0 and d["term"][1, 2] == 0.0 and d["term"][1, 3] == 0.25
+    A, g, E, F, cost, count = tref.chain(c, jac, 3, 2.0, 5.0)
+    assert count.tolist() == [0, 0, 2] and cost[0] == cost[1] == 0.0 and cost[2] == 2.0 * ((25.0 + 0.0) + 0.25)
+    pick = lambda idx: (np.ascontiguousarray(c[:, idx]),                                  # noqa: E731
+                        np.ascontiguousarray(jac.reshape(3, 4, 3, 26)[:, idx]).reshape(3, 3 * len(idx), 26))
+    without = tref.chain(*pick([1, 3]), 3, 2.0, 5.0)
+    for i in range(4):
+        assert np.array_equal((A, g, E, F)[i], without[i])
+    assert cost[2] == without[4][2] + 2.0 * 25.0
+    still = tref.chain(*pick([1]), 3, 1.0, 5.0)                                          # a = 0 alone: rows, no gradient
+    assert still[5].tolist() == [0, 0, 1] and still[0].any() and still[2][0].any() and still[3][0].any()
+    assert not still[1].any() and not still[4].any()
+
+
+def combined_at_start(case, T, model=None, accel_weight=1.0, temporal_weight=0.1):
+    p = case["params0"].float().double()
+    return (p,) + tref.combined(case["model"] if model is None else model, case["view"], case["observed"], p, case["p2m"], T,
+                                case["table"], cref.DEFAULT_COLLISION_WEIGHT if case["table"] is not None else 0.0,
+                                temporal_weight, INF, None, accel_weight, INF, None, "chain", **qref.terms_of(case))
+
+
+def test_block_solve_equals_the_dense_solve(mesh):
+    """shr_pose_lm_seq2_step's block Cholesky with bandwidth two (sphere_trajectory_ref.block_solve, word for word) against
+    numpy.linalg.solve of the dense 26 T x 26 T system, on the combined equations of SOLVE_CASES at params0 with
+    lambda = 1e-3 and STIFFNESS, both temporal terms weighted; Seq2LM's step is that rounded to fp32; without F the block
+    solve is sphere_sequence_ref.block_solve's bits; a bad pivot in one frame fails the whole sequence."""
+    worst = 0.0
+    mu = ref.STIFFNESS
+    for S, T, table in SOLVE_CASES:
+        case = qref.sequence_case(mesh, S, T, table)
+        p, A, g, E, F, cost, _ = combined_at_start(case, T)
+        assert bool(F.any()) and bool(E.any())
+        lm = tref.Seq2LM(p, T, 1e-3)
+        trial = lm.step(A, g, E, F, cost, p, None, torch.as_tensor(mu))
+        for s in range(S):
+            sl = slice(s * T, s * T + T)
+            args = (A[sl].numpy(), g[sl].numpy(), E[sl].numpy(), F[sl].numpy(), float(np.float32(1e-3)), mu, p[sl].numpy(),
+                    p[sl].numpy(), T)
+            x, y = tref.block_solve(*args), tref.dense_solve(*args)
+            dev = np.abs(x - y).max() / np.abs(y).max()
+            worst = max(worst, dev)
+            H, rhs = tref.dense_system(*args)
+            print("S %d T %d %s, sequence %d: |block - dense| %.3g of the largest step %.3g; condition %.3g; residual %.3g"
+                  % (S, T, table, s, dev, np.abs(y).max(), np.linalg.cond(H), np.abs(H @ x.reshape(-1) - rhs).max() / np.abs(rhs).max()))
+            assert dev <= 4 * BLOCK_DENSE_DEVIATION
+            without = tref.dense_solve(*(args[:3] + (None,) + args[4:]))
+            assert np.abs(without - y).max() > 1e3 * dev * np.abs(y).max()           # (F matters in these systems)
+            want = p[sl] + torch.as_tensor(x)                          # (the trial is that rounded to fp32)
+            assert torch.equal(trial[sl], want.float().double())
+            assert np.array_equal(tref.block_solve(*(args[:3] + (None,) + args[4:])), qref.block_solve(*(args[:3] + args[4:])))
+    print("block against dense: worst %.3g" % worst)
+    assert BLOCK_DENSE_DEVIATION / 4 <= worst <= 4 * BLOCK_DENSE_DEVIATION
+    A, g, E, F = (t[:T].numpy() for t in (A, g, E, F))
+    for frame, value in ((T - 1, -np.eye(26)), (1, None)):
+        bad = A.copy()
+        if value is None:
+            bad[frame, 3, 3] = np.nan
+        else:
+            bad[frame] = value
+        assert tref.block_solve(bad, g, E, F, 1e-3, mu, p[:T].numpy(), p[:T].numpy(), T) is None
+    nan_F = F.copy()
+    nan_F[0, 2, 2] = np.nan                                        # a NaN in F reaches frame 2's pivot
+    assert tref.block_solve(A, g, E, nan_F, 1e-3, mu, p[:T].numpy(), p[:T].numpy(), T) is None
+
+
+def test_without_F_it_is_the_sequence_fit_exactly(mesh):
+    """With F = None the restated step gives sphere_sequence_ref.SeqLM's trial, state and decisions exactly; with
+    accel_weight = 0 (or T < 3) the restated loop gives sphere_sequence_ref.solve's poses, costs and decisions exactly."""
+    case = qref.sequence_case(mesh, 2, 3)
+    p, A, g, E, F, cost, _ = combined_at_start(case, 3)
+    a, b = qref.SeqLM(p, 3, 1e-3), tref.Seq2LM(p, 3, 1e-3)
+    for _ in range(2):
+        x, y = a.step(A, g, E, cost, p, None, case["stiffness"]), b.step(A, g, E, None, cost, p, None, case["stiffness"])
+        assert torch.equal(x, y) and torch.equal(a.p, b.p) and torch.equal(a.lam, b.lam) and torch.equal(a.cost, b.cost)
+    terms = qref.terms_of(case)
+    args = (case["model"], case["view"], case["observed"], case["params0"], case["p2m"])
+    for T, aw in ((3, 0.0), (2, 1.0)):
+        case = qref.sequence_case(mesh, 6 // T, T)
+        terms = qref.terms_of(case)
+        args = (case["model"], case["view"], case["observed"], case["params0"], case["p2m"])
+        want = qref.solve(*args, T, case["table"], 1.0, 0.5, 20.0, None, 3, 1e-3, case["stiffness"], **terms)
+        got = tref.solve(*args, T, case["table"], 1.0, 0.5, 20.0, None, aw, 30.0, None, 3, 1e-3, case["stiffness"], **terms)
+        assert torch.equal(want[0], got[0]) and torch.equal(want[1], got[1]) and torch.equal(want[2], got[2])
+        assert all(torch.equal(x, y) for x, y in zip(want[3].history, got[3].history)) and torch.equal(want[3].lam, got[3].lam)
+        assert all(r is None for r in got[3].rowed)
+
+
+def test_ops_refuse_what_the_kernels_do_not_take(mesh):
+    """No device here: the ops refuse CPU tensors and bad scalars with a RuntimeError; the module's defaults."""
+    from spherehand_amd import ops
+    from spherehand_amd.render import SphereSequencePoseFitter, SphereTrajectoryPoseFitter
+    fit = SphereTrajectoryPoseFitter(mesh, 32, 32, 3, stiffness=ref.STIFFNESS)
+    assert isinstance(fit, SphereSequencePoseFitter) and fit.seq_len == 3
+    assert fit.temporal_weight == SphereTrajectoryPoseFitter.DEFAULT_TEMPORAL_WEIGHT == TEMPORAL_WEIGHT
+    assert fit.accel_weight == SphereTrajectoryPoseFitter.DEFAULT_ACCEL_WEIGHT == ACCEL_WEIGHT
+    assert fit.acc_max == SphereTrajectoryPoseFitter.DEFAULT_ACC_MAX == ACC_MAX
+    assert SphereSequencePoseFitter(mesh, 32, 32, 3).temporal_weight == qref.DEFAULT_TEMPORAL_WEIGHT     # the parent's stay
+    for word in ("SphereSequencePoseFitter", "NO autograd", "NOT checked", "4.4u", "network/util_modules.py:349-381",
+                 "bit for bit", "block-pentadiagonal", "does NOT fix"):
+        assert word in SphereTrajectoryPoseFitter.__doc__, word
+    for bad in (dict(accel_weight=-1.0), dict(accel_weight=INF), dict(accel_weight=float("nan")), dict(acc_max=-1.0),
+                dict(acc_max=float("nan")), dict(temporal_weight=-1.0)):
+        with pytest.raises(ValueError):
+            SphereTrajectoryPoseFitter(mesh, 32, 32, 3, **bad)
+    obs, view, p0 = torch.full((6, 1, 32, 32), 100.0), torch.eye(4).expand(6, 1, 4, 4).contiguous(), torch.zeros(6, 26)
+    tables = (fit.fk.offset, fit.fk.offset_inv, fit.kp_bone, fit.kp_wv, fit.radii)
+    f64 = lambda *s: torch.zeros(s, dtype=torch.float64)           # noqa: E731
+    for call in (lambda: fit.solve(obs, p0, view), lambda: fit.normal_equations(obs, p0, view),
+                 lambda: ops.sphere_accel_normal(p0, *tables[:4], 3),
+                 lambda: ops.sphere_accel_normal(p0, *tables[:4], 4),
+                 lambda: ops.sphere_accel_normal(p0, *tables[:4], 3, accel_weight=-1.0),
+                 lambda: ops.sphere_icp_trajectory(obs, view, p0, *tables, 4),
+                 lambda: ops.sphere_icp_trajectory(obs, view, p0, *tables, 3, accel_weight=INF),
+                 lambda: ops.sphere_icp_trajectory(obs, view, p0, *tables, 3, acc_max=float("nan")),
+                 lambda: ops.pose_lm_seq2_begin(p0, 3),
+                 lambda: ops.pose_lm_seq2_step(f64(6 * 2120), f64(6, 26, 26), f64(6, 26), None, None, f64(6), p0, 3)):
+        with pytest.raises(RuntimeError):
+            call()
+
+
+_RUNS = {}
+
+
+def end_to_end_run(mesh, dtype=torch.float64):
+    """sphere_trajectory_ref.solve of the end-to-end case (END_TO_END: two sequences of five frames, four iterations) with the
+    module's defaults in `dtype`, once per process (the GPU tests run the same)."""
+    if dtype not in _RUNS:
+        S, T = END_TO_END[:2]
+        case = qref.sequence_case(mesh, *END_TO_END)
+        p0 = case["params0"].float().double()
+        _RUNS[dtype] = tref.solve(case["model"].to(dtype), case["view"], case["observed"], p0, case["p2m"], T, case["table"],
+                                  cref.DEFAULT_COLLISION_WEIGHT, TEMPORAL_WEIGHT, qref.DEFAULT_TS_MAX, None, ACCEL_WEIGHT,
+                                  ACC_MAX, None, qref.END_TO_END_ITERS, 1e-3, case["stiffness"], **qref.terms_of(case))
+    return _RUNS[dtype]
+
+
+def test_end_to_end_case_is_stable(mesh):
+    """The end-to-end case does not amplify rounding: the fp64 restatement's final pose moves by at most END_TO_END_STABLE
+    under a perturbation of the start by +-1e-9 (the prior held), in both sequences; seed 31's figure is printed beside it."""
+    S, T = END_TO_END[:2]
+    noise = torch.randn(S * T, 26, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+
+    def moved(seed):
+        case = qref.sequence_case(mesh, S, T, END_TO_END[2], seed)
+        start = case["params0"].float().double()
+        q = [tref.solve(case["model"], case["view"], case["observed"], start + eps * noise, case["p2m"], T, case["table"],
+                        cref.DEFAULT_COLLISION_WEIGHT, TEMPORAL_WEIGHT, qref.DEFAULT_TS_MAX, None, ACCEL_WEIGHT, ACC_MAX, None,
+                        qref.END_TO_END_ITERS, 1e-3, case["stiffness"], start, "chain", **qref.terms_of(case))[0]
+             for eps in (0.0, 1e-9, -1e-9)]
+        return max((x - q[0]).abs().max().item() for x in q[1:])
+
+    here, first = moved(END_TO_END[3]), moved(31)
+    print("a 1e-9 perturbation of the start moves the final pose by %.3g (seed %d) and %.3g (seed 31); bar %.3g"
+          % (here, END_TO_END[3], first, END_TO_END_STABLE))
+    assert here <= END_TO_END_STABLE
+
+
+def kept(lm64, lm32):
+    """[S] bool: the sequences on which the two runs keep the same accept sequence and the same spheres with rows."""
+    same = (torch.stack(lm64.history) == torch.stack(lm32.history)).all(0)
+    for a, b in zip(lm64.rowed, lm32.rowed):
+        assert (a is None) == (b is None)
+        if a is not None:
+            same &= (a == b).view(lm64.S, -1).all(1)
+    return same
+
+
+def fp32_deviations(mesh):
+    dev = dict(A=0.0, g=0.0, E=0.0, F=0.0, cost=0.0, step=0.0, pose=0.0)
+    for S, T, table, w, cap, fw_on in EVALUATIONS:
+        if T <= 2:
+            continue
+        case, p, fw = evaluation_inputs(mesh, S, T, table, fw_on)
+        m64, m32 = case["model"], case["model"].to(torch.float32)
+        held = m64.centres(p).float().numpy()
+        out64, out32 = (tref.chain(held, m.chain.jacobian(p)[1].numpy(), T, w, cap, fw) for m in (m64, m32))
+        for i, name in enumerate("AgEF"):
+            x, y = out64[i], out32[i]
+            big = np.abs(x).reshape(S * T, -1).max(1)
+            live = big > 0
+            dev[name] = max(dev[name], (np.abs(x - y).reshape(S * T, -1).max(1)[live] / big[live]).max())
+        print("S %d T %d %s: A %.3g, g %.3g, E %.3g, F %.3g so far" % (S, T, table, dev["A"], dev["g"], dev["E"], dev["F"]))
+    for S, T, table in SOLVE_CASES:                                              # the combined fit's first step, own centres
+        case = qref.sequence_case(mesh, S, T, table)
+        mu = case["stiffness"]
+        steps, costs = [], []
+        for m in (case["model"], case["model"].to(torch.float32)):
+            p, A, g, E, F, cost, _ = combined_at_start(case, T, m)
+            lm = tref.Seq2LM(p, T, 1e-3, m.dtype)
+            steps.append(lm.step(A, g, E, F, cost, p, None, mu, True) - p)
+            costs.append(cost.view(S, T).sum(1))
+        dev["cost"] = max(dev["cost"], ((costs[0] - costs[1]).abs() / costs[0]).max().item())
+        dev["step"] = max(dev["step"], (steps[0] - steps[1]).abs().max().item())
+        print("S %d T %d %s: cost %.3g, step %.3g so far" % (S, T, table, dev["cost"], dev["step"]))
+    (q64, _, _, lm64), (q32, _, _, lm32) = (end_to_end_run(mesh, dt) for dt in (torch.float64, torch.float32))
+    same = kept(lm64, lm32)
+    T = END_TO_END[1]
+    diff = (q64 - q32).abs().view(-1, T * 26).amax(1)
+    print("end_to_end: the fp32 run keeps the decisions and the rows: %s; |pose32 - pose64| %s; decisions %s"
+          % (same.tolist(), diff.tolist(), [h.tolist() for h in lm64.history]))
+    dev["pose"] = diff.max().item()
+    return dev, same
+
+
+def test_fp32_bars(mesh):
+    """The constants above, measured again.  The fp32 / fp64 CPU pair keeps EVERY accept decision and the same rows in both
+    sequences of the end-to-end case; the fit's cost falls on every sequence and the acceleration term has rows inside
+    the loop."""
+    dev, same = fp32_deviations(mesh)
+    print("fp32 against fp64: A %.3g, g %.3g, E %.3g, F %.3g, cost %.3g, step %.3g, pose %.3g; same %s"
+          % (dev["A"], dev["g"], dev["E"], dev["F"], dev["cost"], dev["step"], dev["pose"], same.tolist()))
+    assert bool(same.all())
+    _, cost0, cost, lm = end_to_end_run(mesh, torch.float64)
+    print("end_to_end: cost0 %s, cost %s" % (cost0.tolist(), cost.tolist()))
+    assert bool((cost < cost0).all()) and int(lm.rowed[0].sum()) > 0 and bool(torch.stack(lm.history).any())
+    for name, const in (("A", FP32_A_DEVIATION), ("g", FP32_G_DEVIATION), ("E", FP32_E_DEVIATION), ("F", FP32_F_DEVIATION),
+                        ("cost", FP32_COST_DEVIATION), ("step", FP32_STEP_DEVIATION), ("pose", FP32_POSE_DEVIATION)):
+        assert const / 2 <= dev[name] <= 2 * const, (name, dev[name], const)
