@@ -1536,6 +1536,103 @@ int shr_pose_lm_seq2_step(void *state, const double *A, const double *g, const d
                           int B, int T, float *trial_out, float *params, float *cost /* [S] */, float *cost0 /* [S] */,
                           void *workspace, void *stream);
 
+/* Parameters that the frames of a group SHARE: the arrowhead step --------------------------------------------------------------
+ * Every fit above treats the model's constants -- the sphere radii first of all -- as given, and DESIGN.md 4.4p and 4.4s name
+ * them as the weakest thing left.  A constant of the hand belongs to the person, not the frame: it is one vector sigma [K]
+ * for the N frames of a group while every frame keeps its own pose.  The observation is DataToModelLoss's
+ * (mesh/render.py:93-142) with sigma among the unknowns; the reference has no counterpart of the shared solve.  A shared
+ * unknown couples every frame of its group, so the normal equations are bordered block-diagonal, an ARROWHEAD: N pose
+ * blocks A_b [26 x 26], one shared block R [K x K], a coupling C_b [26 x K] per frame.  shr_pose_lm_step cannot take a shared
+ * unknown; the sequence steps are chains over the frames, this one is parallel over them with one reduction in the middle.
+ * The step is generic in the shared block, 0 <= K <= 64: what sigma means is decided by the entry that forms C, R and gs.
+ * Layout: B = G N frames, the N frames of a group adjacent; frame b belongs to group b / N.
+ * The first user is the data-to-model term with the RADII as the shared parameters (K = J).  One evaluation of that fit is
+ *   shr_pose_keypoints_jacobian(trial) -> shr_view_vertices_fwd (NV := J) -> shr_sphere_icp_radii_normal(radii := trial_shape)
+ *     -> shr_sphere_prior_normal(accumulate = 1) -> shr_sphere_collision_normal(accumulate = 1) -> shr_pose_lm_shared_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.  The keypoint, limit and collision terms do not
+ * depend on the radii, so they add to A, g and cost only.  The render term's radius columns are not formed: a term whose
+ * radius gradient is missing from gs gives no descent direction for the cost the accept test sees, so the render entry
+ * stays out of this loop.
+ *   shr_sphere_icp_radii_normal   shr_sphere_icp_normal with one more column per sphere.  radii[G,J] fp32, one table per
+ *       group, in place of that entry's radii[J]; N frames per group.  Data points, the fp32 owner search, the fp64 residual
+ *       d = n - r, the direction u = R^T u_v, the row rule, the tiles of 1024 pixels and the summation order are
+ *       shr_sphere_icp_normal's, the same code (csrc/sphere_icp_scan.h).  Per data row of sphere j the pose part of the row
+ *       is that entry's, -u^T Jc_j, and the new column is d d / d r_j = -1, in the column of sphere j only.  Per (frame,
+ *       sphere) the scan carries four more chains, sum u (3, model frame) and sum d, in the order and by the
+ *       one-owner-per-entry scheme of the twelve: moments[B,J,16] (may be NULL) = the twelve, then sum u, then sum d.
+ *       -> A[B,26,26], g[B,26], cost[B], count[B], dist, owner: shr_sphere_icp_normal's.  With G = 1 and the same radii they
+ *       and moments[..., :12] are that entry's BITS.
+ *       -> C[B,26,J] fp64, the coupling sum row_pose^T row_radius: C[b,a,j] = (Jc[0,a] su_0 + Jc[1,a] su_1) + Jc[2,a] su_2,
+ *       Jc = jac[3j .. 3j + 2, :] promoted to fp64, su = sphere j's sum u; an exact +0 for a sphere without a row.
+ *       -> R[G,J,J] fp64, written dense: R_jj = the chain over the group's frames, ascending, of the rows of sphere j (an
+ *       integer: exact); every off-diagonal entry an exact +0.  gs[G,J] fp64 = 0 - the chain over the frames, ascending, of
+ *       sum d: the gradient of 1/2 sum d^2 in r_j.
+ *       Radius guard: a group with a radius that is not finite or not > 0 is void -- cost = +inf and A = g = C = 0 for
+ *       every frame of it, R = gs = 0 -- so that the step rejects it; moments, count, dist and owner are still the scan's.
+ *       (shr_sphere_icp_normal's behaviour for such radii is what it was.)
+ *       No atomics, fixed-order fp64 chains, nothing contracted: bitwise reproducible, and a group does not depend on the
+ *       batch it is in.  workspace: shr_sphere_icp_radii_normal_workspace_bytes(B, V, J, W, H) bytes (-1 on a negative
+ *       size), 16-byte aligned.
+ *       Argument rules: shr_sphere_icp_normal's, and 1 <= N, B % N == 0 (SHR_EINVAL), checked before the B == 0 no-op;
+ *       C, R and gs given and 8-byte aligned.
+ *   shr_pose_lm_shared_begin, shr_pose_lm_shared_step   shr_pose_lm_seq_begin / shr_pose_lm_seq_step's contract with the unit
+ *       of decision the GROUP: one lambda, one cost, one cost0 and one accept decision per group.
+ *       state: shr_pose_lm_shared_state_bytes(B, G, K) = 8 (760 B + G K (K + 3) + 26 B K) bytes: shr_pose_lm_step's state
+ *       of the B frames, 760 doubles each, the group's total cost, lambda and counters in its FIRST frame; BEHIND them per
+ *       group the accepted sigma, shape0, gs [K] and R [K x K], and behind those per frame the accepted C [26 x K].
+ *       workspace: shr_pose_lm_shared_workspace_bytes(B, G, K) = 8 (B (704 + 26 K) + G (8 + K)) bytes: per frame L_b, z_b,
+ *       the factor's verdict and Y_b; per group the decision, the verdict and d sigma.  Both 8-byte aligned, -1 on a negative
+ *       size.  The workspace is needed by EVERY step (it carries the decision to the frames), except with K == 0 and N == 1.
+ *       begin(params0 [B,26], shape0 [G,K]): trial <- params0, trial_shape <- shape0.
+ *       Cost and accept.  total = the chain from 0 over the group's frames, ascending, of shr_pose_lm_step's per-frame total
+ *       (cost_data_b + the stiffness term, i ascending), then + nu_k (sigma_k - prior_k)^2, k ascending, sigma the fp32
+ *       trial_shape in fp64, prior = shape_prior [G,K] or, NULL, shape0; nu = shape_stiffness [K] >= 0 or, NULL, 0.  The
+ *       trial of the WHOLE group -- poses and sigma -- is accepted iff total is finite and below the state's; lambda x 0.3
+ *       on accept, x 10 on reject, clamped to [1e-9, 1e6], the first accepted step leaving it.  On accept A, g, C, R, gs,
+ *       the poses and sigma become the state's.  cost0 [G] is written by the first step after begin; cost [G];
+ *       params [B,26] and shape [G,K] are the state's pose and sigma after the decision.
+ *       The solve (solve != 0), on the accepted p, sigma, A, g, C, R, gs; all fp64, every sum in index order:
+ *         per frame   M_b = A_b + diag(mu); L_b L_b^T = M_b + lambda diag(M_b) by shr_pose_lm_step's column recurrence;
+ *                     z_b = L_b^-1 (-(g_b + mu (p_b - prior_b))) by its forward substitution; Y_b = L_b^-1 C_b, column k
+ *                     by Y[m,k] = (((C[m,k] - L[m,0] Y[0,k]) - L[m,1] Y[1,k]) - ...) / L[m,m]: K independent substitutions.
+ *         per group   T = R + diag(nu), the LOWER triangle of R read.  S_kl = T_kl, on the diagonal T_kk + lambda T_kk, then
+ *                     - Y_b[m,k] Y_b[m,l] subtracted entry by entry, frames ascending, m ascending inside; rhs_k =
+ *                     -(gs_k + nu_k (sigma_k - prior_k)), then - Y_b[m,k] z_b[m] in the same order; S = L_s L_s^T by the
+ *                     same column recurrence at size K; d sigma by the two substitutions of shr_pose_lm_step at size K.
+ *         per frame   L_b^T delta_b = z_b - Y_b d sigma, the product a chain from 0, k ascending.
+ *       trial_out [B,26] = (float)(p + delta_b) (may be trial), trial_shape_out [G,K] = (float)(sigma + d sigma) (may be
+ *       trial_shape).  A pivot that is not positive and finite, in ANY frame's factor or in S, writes trial_out = p and
+ *       trial_shape_out = sigma for the WHOLE group; a group does not depend on the other groups of the batch.
+ *       K == 0 (C, R, gs and the shape arrays are not read and may be NULL): no shared block; the frames' steps are
+ *       shr_pose_lm_step's own, a bad pivot staying with its frame, and the decision is the group's.  With K == 0 and N == 1
+ *       the call IS shr_pose_lm_step's on the state's leading part: every output and the state BIT FOR BIT.
+ *       Launch shape: a wave per group (decision), a wave per frame (factor, z, Y), a workgroup of 256 threads per group
+ *       (S, d sigma; skipped with K == 0), a wave per frame (back); four launches on one stream, no atomics, no host
+ *       synchronisation: capturable in a hipGraph.
+ *   Argument rules, checked before the B == 0 no-op: state given and 8-byte aligned, B >= 0, 1 <= N, B % N == 0, K >= 0
+ *   (SHR_EINVAL otherwise); K above 64, B above 2^24: SHR_ETOOLARGE.  lambda0 > 0; NULLs other than prior, stiffness,
+ *   shape_prior, shape_stiffness, trial_out and trial_shape_out without solve, and with K == 0 every shared array;
+ *   misaligned pointers (4 bytes; A, g, C, R, gs, cost_data, workspace 8): SHR_EINVAL. */
+long long shr_sphere_icp_radii_normal_workspace_bytes(int B, int V, int J, int W, int H);
+int shr_sphere_icp_radii_normal(const float *observed, const float *view_centres /* [B,V,J,4] */,
+                                const float *radii /* [G,J] */, const float *view, const float *jac /* [B,3J,26] */,
+                                int B, int V, int J, int W, int H, int N, float ax, float bx, float ay, float by, float fg_max,
+                                float max_dist, double *A, double *g, double *cost, int32_t *count /* [B] */,
+                                double *C /* [B,26,J] */, double *R /* [G,J,J] */, double *gs /* [G,J] */,
+                                double *moments /* [B,J,16] or NULL */, float *dist, int32_t *owner /* [B,V,H,W] or NULL */,
+                                void *workspace, void *stream);
+long long shr_pose_lm_shared_state_bytes(int B, int G, int K);
+long long shr_pose_lm_shared_workspace_bytes(int B, int G, int K);
+int shr_pose_lm_shared_begin(const float *params0, const float *shape0 /* [G,K] */, int B, int N, int K, float lambda0,
+                             void *state, float *trial, float *trial_shape /* [G,K] */, void *stream);
+int shr_pose_lm_shared_step(void *state, const double *A, const double *g, const double *C /* [B,26,K] */,
+                            const double *R /* [G,K,K] */, const double *gs /* [G,K] */, const double *cost_data,
+                            const float *trial, const float *trial_shape /* [G,K] */, const float *prior,
+                            const float *stiffness, const float *shape_prior /* [G,K] or NULL */,
+                            const float *shape_stiffness /* [K] or NULL */, int solve, int B, int N, int K, float *trial_out,
+                            float *trial_shape_out /* [G,K] */, float *params, float *shape /* [G,K] */, float *cost /* [G] */,
+                            float *cost0 /* [G] */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3056,6 +3056,234 @@ def sphere_icp_trajectory(observed, view, params0, offset, offset_inv, bone, wv,
                                  temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight)
 
 
+PoseLmSharedMaxK = 64        # shared parameters of a group at most (shr_pose_lm_shared_step)
+
+
+def _pose_lm_shared_args(B, group_size, K):
+    try:
+        N, K = int(group_size), int(K)
+    except (TypeError, ValueError):
+        raise RuntimeError("group_size and the number of shared parameters must be integers")
+    if N < 1 or B % N != 0:
+        raise RuntimeError("group_size must be >= 1 and divide the %d frames of the batch, not %r" % (B, group_size))
+    if not 0 <= K <= PoseLmSharedMaxK:
+        raise RuntimeError("0 to %d shared parameters are taken, not %d" % (PoseLmSharedMaxK, K))
+    return N, K, B // N
+
+
+def pose_lm_shared_begin(params0, shape0, group_size, lambda0=1e-3):
+    """pose_lm_begin for groups of frames that share parameters (shr_pose_lm_shared_begin): params0 [B,26], B = G group_size,
+    shape0 [G,K] fp32 (None: K = 0, no shared block) -> (state, trial [B,26], trial_shape [G,K] or None)."""
+    _check_input(params0, "start parameters")
+    if params0.dim() != 2 or params0.shape[1] != 26:
+        raise RuntimeError("start parameters must be [B,26]")
+    if not float(lambda0) > 0:
+        raise RuntimeError("lambda0 must be > 0")
+    B = params0.shape[0]
+    if shape0 is not None:
+        _check_input(shape0, "start shape")
+        if shape0.dim() != 2 or shape0.device != params0.device:
+            raise RuntimeError("start shape must be [G,K] on the start parameters' device")
+    N, K, G = _pose_lm_shared_args(B, group_size, 0 if shape0 is None else shape0.shape[1])
+    if shape0 is not None and shape0.shape[0] != G:
+        raise RuntimeError("start shape must be [%d,K], one row per group" % G)
+    lib = _lib.lib()
+    dev = params0.device
+    with _on(dev):
+        state = torch.empty((max(1, lib.shr_pose_lm_shared_state_bytes(B, G, K) // 8),), dtype=torch.float64, device=dev)
+        trial = torch.empty((B, 26), dtype=torch.float32, device=dev)
+        trial_shape = torch.empty((G, K), dtype=torch.float32, device=dev) if K else None
+        _lib.check(lib.shr_pose_lm_shared_begin(_ptr(params0), _ptr(shape0) if K else None, B, N, K, float(lambda0), _ptr(state),
+                                                _ptr(trial), _ptr(trial_shape) if K else None, _stream()),
+                   "shr_pose_lm_shared_begin")
+    return state, trial, trial_shape
+
+
+def pose_lm_shared_step(state, A, g, C, R, gs, cost_data, trial, trial_shape, group_size, prior=None, stiffness=None,
+                        shape_prior=None, shape_stiffness=None, solve=True, out=None, workspace=None):
+    """One step of the loop over groups with shared parameters (shr_pose_lm_shared_step): A [B,26,26], g [B,26],
+    cost_data [B] fp64 of the poses `trial` [B,26] and, of the shared parameters `trial_shape` [G,K], the coupling
+    C [B,26,K], the shared block R [G,K,K] (lower triangle read) and its gradient gs [G,K], fp64 -> (trial_out [B,26],
+    trial_shape_out [G,K] -- both None without `solve` --, params [B,26], shape [G,K], cost [G], cost0 [G]), G = B /
+    group_size: one decision, one lambda and one cost per group, the step from the Schur complement on the shared block.
+    prior, stiffness: pose_lm_step's; shape_prior [G,K] (default: the start shape) and shape_stiffness [K] >= 0 add
+    sum_k shape_stiffness_k (shape_k - shape_prior_k)^2 to a group's cost.  C = R = gs = trial_shape = None: K = 0, no shared
+    block; the shape outputs are then None and with group_size 1 every output is pose_lm_step's bit for bit.
+    out = (trial_out, trial_shape_out, params, shape, cost, cost0): buffers to write instead of new ones; workspace:
+    shr_pose_lm_shared_workspace_bytes(B, G, K) bytes to use instead of a new buffer."""
+    _check_input(trial, "trial")
+    B = trial.shape[0]
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    dev = trial.device
+    shared = (C, R, gs, trial_shape)
+    if any(t is None for t in shared) and not all(t is None for t in shared):
+        raise RuntimeError("C, R, gs and trial_shape are given together or not at all")
+    if trial_shape is not None:
+        _check_input(trial_shape, "trial_shape")
+        if trial_shape.dim() != 2 or trial_shape.device != dev:
+            raise RuntimeError("trial_shape must be [G,K] on trial's device")
+    N, K, G = _pose_lm_shared_args(B, group_size, 0 if trial_shape is None else trial_shape.shape[1])
+    if K == 0 and trial_shape is not None:
+        C = R = gs = trial_shape = None
+    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (C, "C", (B, 26, K)),
+                           (R, "R", (G, K, K)), (gs, "gs", (G, K)), (cost_data, "cost_data", (B,))):
+        if t is None:
+            continue
+        _check_input(t, name, torch.float64)
+        if (shape is not None and tuple(t.shape) != shape) or t.device != dev:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    if trial_shape is not None and tuple(trial_shape.shape) != (G, K):
+        raise RuntimeError("trial_shape must be [%d,%d]" % (G, K))
+    lib = _lib.lib()
+    if state.numel() * 8 < lib.shr_pose_lm_shared_state_bytes(B, G, K):
+        raise RuntimeError("state is pose_lm_shared_begin's, for the same B, group_size and K")
+    for t, name, shape in ((prior, "prior", (B, 26)), (stiffness, "stiffness", (26,)), (shape_prior, "shape_prior", (G, K)),
+                           (shape_stiffness, "shape_stiffness", (K,))):
+        if t is None:
+            continue
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("%s must be %s on trial's device" % (name, list(shape)))
+    if K == 0:
+        shape_prior = shape_stiffness = None
+    with _on(dev):
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+            out = (new(B, 26) if solve else None, new(G, K) if solve and K else None, new(B, 26), new(G, K) if K else None,
+                   new(G), new(G))
+        if workspace is None:
+            workspace = torch.empty((max(1, lib.shr_pose_lm_shared_workspace_bytes(B, G, K) // 8),), dtype=torch.float64,
+                                    device=dev)
+        elif workspace.numel() * workspace.element_size() < lib.shr_pose_lm_shared_workspace_bytes(B, G, K):
+            raise RuntimeError("workspace is too small for this B, group_size and K")
+        trial_out, trial_shape_out, params, shape, cost, cost0 = out
+        _lib.check(lib.shr_pose_lm_shared_step(
+            _ptr(state), _ptr(A), _ptr(g), _ptr(C) if K else None, _ptr(R) if K else None, _ptr(gs) if K else None,
+            _ptr(cost_data), _ptr(trial), _ptr(trial_shape) if K else None, _ptr(prior), _ptr(stiffness), _ptr(shape_prior),
+            _ptr(shape_stiffness), int(bool(solve)), B, N, K, _ptr(trial_out) if solve else None,
+            _ptr(trial_shape_out) if solve and K else None, _ptr(params), _ptr(shape) if K else None, _ptr(cost), _ptr(cost0),
+            _ptr(workspace), _stream()), "shr_pose_lm_shared_step")
+    return (trial_out if solve else None), (trial_shape_out if solve and K else None), params, (shape if K else None), cost, cost0
+
+
+def _sphere_radii_args(observed, view, params, offset, offset_inv, bone, wv, radii, group_size, pixel_to_model, max_dist,
+                       name="parameters"):
+    _check_input(radii, "radii")
+    if radii.dim() != 2:
+        raise RuntimeError("radii must be [G,J], one table per group of frames")
+    one = radii[0] if radii.shape[0] else radii.new_empty((radii.shape[1],))
+    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, one, pixel_to_model,
+                                                    max_dist, name)
+    N, _, G = _pose_lm_shared_args(B, group_size, J)
+    if radii.shape[0] != G:
+        raise RuntimeError("radii must be [%d,%d]: %d frames in groups of %d" % (G, J, B, N))
+    return B, V, H, W, J, N, G, p2m, max_dist
+
+
+def sphere_icp_radii_normal(observed, view, params, offset, offset_inv, bone, wv, radii, group_size, right_hand=True,
+                            pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), want_maps=False):
+    """sphere_icp_normal with the sphere radii among the unknowns (shr_sphere_icp_radii_normal): radii [G,J], one table per
+    group of group_size adjacent frames, B = G group_size -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32,
+    C [B,26,J], R [G,J,J], gs [G,J] fp64 -- what pose_lm_shared_step takes beside A and g --, moments [B,J,16] fp64: the
+    twelve of sphere_icp_normal, then sum u and sum d); with want_maps also (dist, owner).  A group with a radius that is not
+    finite or not > 0 has cost = +inf and zero equations."""
+    B, V, H, W, J, N, G, p2m, max_dist = _sphere_radii_args(observed, view, params, offset, offset_inv, bone, wv, radii,
+                                                            group_size, pixel_to_model, max_dist)
+    lib = _lib.lib()
+    dev = observed.device
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
+        _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        A, g, cost, C, R, gs, moments = f64(B, 26, 26), f64(B, 26), f64(B), f64(B, 26, J), f64(G, J, J), f64(G, J), f64(B, J, 16)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        dist = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
+        owner = torch.empty((B, V, H, W), dtype=torch.int32, device=dev) if want_maps else None
+        ws = torch.empty((max(16, lib.shr_sphere_icp_radii_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.shr_sphere_icp_radii_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W,
+                                                   H, N, *p2m, float(fg_max), max_dist, _ptr(A), _ptr(g), _ptr(cost), _ptr(count),
+                                                   _ptr(C), _ptr(R), _ptr(gs), _ptr(moments), _ptr(dist), _ptr(owner), _ptr(ws),
+                                                   _stream()), "shr_sphere_icp_radii_normal")
+    return (A, g, cost, count, C, R, gs, moments) + ((dist, owner) if want_maps else ())
+
+
+def sphere_icp_calibrate(observed, view, params0, offset, offset_inv, bone, wv, radii0, group_size, right_hand=True,
+                         pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                         stiffness=None, prior=None, shape_stiffness=None, shape_prior=None, keypoints=None, confidence=None,
+                         kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0, collision=None,
+                         collision_weight=0.0):
+    """Calibrate the sphere radii to the hand in the frames: sphere_icp_priors' loop without the render term, the radii [G,J]
+    of every group of group_size adjacent frames fitted with the frames' poses -> (params [B,26], radii [G,J], cost0 [G],
+    cost [G]).  `iters` Levenberg-Marquardt iterations from (params0 [B,26], radii0 [G,J]) on the group's energy
+    sum over its frames of (sum dist^2 + sum_i stiffness_i (p_i - prior_i)^2 + the keypoint, limit and collision terms of
+    sphere_icp_priors) + sum_j shape_stiffness_j (r_j - shape_prior_j)^2, shape_prior [G,J] (default radii0).  Each of the
+    iters + 1 evaluations is shr_pose_keypoints_jacobian -> shr_view_vertices_fwd -> shr_sphere_icp_radii_normal with the
+    trial radii -> shr_sphere_prior_normal / shr_sphere_collision_normal (accumulate = 1: they do not depend on the radii
+    and add to A, g and the cost only) -> shr_pose_lm_shared_step, on torch's current stream, into buffers allocated once
+    before the loop; nothing returns to the host: capturable in a graph.  The collision table is NOT rebuilt from the trial
+    radii.  iters = 0 returns the starts and cost = cost0."""
+    B, V, H, W, J, N, G, p2m, max_dist = _sphere_radii_args(observed, view, params0, offset, offset_inv, bone, wv, radii0,
+                                                            group_size, pixel_to_model, max_dist, "start parameters")
+    dev = observed.device
+    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
+                                                                       limits, limit_weight)
+    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
+    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
+                                                                           "collision_weight")
+    collide = K > 0 and collision_weight > 0.0
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError("iters must be >= 0")
+    for t, name, shape in ((prior, "prior", (B, 26)), (stiffness, "stiffness", (26,)), (shape_prior, "shape_prior", (G, J)),
+                           (shape_stiffness, "shape_stiffness", (J,))):
+        if t is None:
+            continue
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("%s must be %s on observed's device" % (name, list(shape)))
+    state, trial, trial_shape = pose_lm_shared_begin(params0, radii0, N, lambda0)
+    lib = _lib.lib()
+    right, fg_max = int(bool(right_hand)), float(fg_max)
+    with _on(dev):
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        C, R, gs = f64(B, 26, J), f64(G, J, J), f64(G, J)
+        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
+        params, radii, cost0, cost = f32(B, 26), f32(G, J), f32(G), f32(G)
+        ws = torch.empty((max(16, lib.shr_sphere_icp_radii_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        lm_ws = torch.empty((max(1, lib.shr_pose_lm_shared_workspace_bytes(B, G, J) // 8),), dtype=torch.float64, device=dev)
+        stream = _stream()
+        for it in range(iters + 1):
+            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+            _lib.check(lib.shr_sphere_icp_radii_normal(_ptr(observed), _ptr(centres), _ptr(trial_shape), _ptr(view), _ptr(jac), B,
+                                                       V, J, W, H, N, *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                       _ptr(count), _ptr(C), _ptr(R), _ptr(gs), None, None, None, _ptr(ws),
+                                                       stream), "shr_sphere_icp_radii_normal")
+            if priors:
+                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
+                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
+                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
+            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
+                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
+                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
+            solve = int(it < iters)
+            _lib.check(lib.shr_pose_lm_shared_step(
+                _ptr(state), _ptr(A), _ptr(g), _ptr(C), _ptr(R), _ptr(gs), _ptr(cost_data), _ptr(trial), _ptr(trial_shape),
+                _ptr(prior), _ptr(stiffness), _ptr(shape_prior), _ptr(shape_stiffness), solve, B, N, J,
+                _ptr(trial) if solve else None, _ptr(trial_shape) if solve else None, _ptr(params), _ptr(radii), _ptr(cost),
+                _ptr(cost0), _ptr(lm_ws), stream), "shr_pose_lm_shared_step")
+    return params, radii, cost0, cost
+
+
 def _depth_normals_args(depth, scale, max_step):
     _check_input(depth, "depth")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:

@@ -1230,6 +1230,85 @@ class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
                                        self.acc_max, self._frame_weight(triple_weight), (A, g, cost), E)
 
 
+class SphereRadiiCalibrator(SphereCollisionPoseFitter):
+    """The sphere RADII calibrated to the hand in the frames: every fitter above takes the 41 radii as a constant of the
+    shipped model, and they are a fat proxy.  The batch's B = G group_size frames are G groups, the
+    frames of one adjacent -- one person's hand in group_size poses; each frame keeps its own pose, the frames of a group
+    SHARE one radius table, and both are fitted jointly: `iters` Levenberg-Marquardt iterations on the group's energy
+        the sum over its frames of SphereCollisionPoseFitter's energy (without the render term)
+        + sum_j shape_stiffness_j (r_j - radii0_j)^2
+    (ops.sphere_icp_calibrate; include/spherehand_hip.h, shr_sphere_icp_radii_normal and shr_pose_lm_shared_step).  A
+    shared unknown couples every frame of its group, so the normal equations are an arrowhead -- the pose blocks, one
+    41 x 41 radius block and a coupling per frame -- solved by the Schur complement on the radius block, and lambda, the
+    cost and the accept decision belong to the group.
+        solve(observed, params0, view=None, prior=None, keypoints=None, confidence=None, radii0=None)
+            -> (params [B,26], radii [G,41], cost0 [G], cost [G])
+        normal_equations(observed, params, view=None, keypoints=None, confidence=None, radii=None)
+            -> (A, g, cost, count [B], C [B,26,41], R [G,41,41], gs [G,41]): A, g and cost the SUM of the four terms', count
+               the data term's rows; C, R and gs are the data term's own (no other term depends on the radii)
+    radii0 [G,41] (or [41] for every group) defaults to the shipped table.  shape_stiffness: [41] or a number, each >= 0,
+    None: DEFAULT_SHAPE_STIFFNESS, from DESIGN.md 4.4v's grid; with 0 a sphere that owns no data point in any frame of its
+    group leaves the radius block singular, and the step, which has no special case for a bad pivot, stays.  The result is used by handing a group's table to any of the fitters above: fitter.radii.copy_(radii[g]).
+    render_weight other than 0 raises ValueError: the render rows' d D / d r columns are out of scope here, and a term
+    whose radius gradient is missing gives no descent direction for the cost the accept test sees.  The collision table
+    stays the one built at construction, from the shipped radii.  Data points are explained by the sphere SURFACE nearest to
+    them, so one view constrains a radius only where that sphere owns points; shape_stiffness holds the others.  Everything
+    else is SphereCollisionPoseFitter's: a refinement from a start, NO autograd through the solve, the rotation NOT checked."""
+
+    # DESIGN.md 4.4v: the grid's row
+    DEFAULT_SHAPE_STIFFNESS = 1.0
+
+    def __init__(self, mesh, width, height, group_size, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3,
+                 stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=0.0,
+                 max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
+                 collision_weight=None, min_dist=None, radius_scale=None, shape_stiffness=None):
+        if render_weight is None or float(render_weight) != 0.0:
+            raise ValueError("SphereRadiiCalibrator has no render term: its radius columns are not formed (render_weight must be 0)")
+        super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist, 0.0,
+                         max_resid, background, kp_weight, kp_max, limit_weight, limits, collision_weight, min_dist,
+                         radius_scale)
+        self.group_size = int(group_size)
+        if self.group_size < 1:
+            raise ValueError("group_size must be >= 1")
+        nu = np.asarray(self.DEFAULT_SHAPE_STIFFNESS if shape_stiffness is None else shape_stiffness, np.float32)
+        nu = np.full(self.num_spheres, nu, np.float32) if nu.ndim == 0 else nu.reshape(self.num_spheres)
+        if not (nu >= 0).all():
+            raise ValueError("shape_stiffness must be >= 0")
+        self.register_buffer('shape_stiffness', torch.from_numpy(nu.copy()))
+
+    def _radii(self, radii, B):
+        if B % self.group_size != 0:
+            raise RuntimeError("the batch's %d frames are not groups of %d" % (B, self.group_size))
+        G = B // self.group_size
+        if radii is None:
+            radii = self.radii
+        radii = radii.detach().float().to(self.radii.device)
+        return (radii.unsqueeze(0).expand(G, -1) if radii.dim() == 1 else radii).contiguous()
+
+    @torch.no_grad()
+    def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None, radii0=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        return ops.sphere_icp_calibrate(observed, view, params0.detach().contiguous().float(), *self._tables()[:4],
+                                        self._radii(radii0, observed.shape[0]), self.group_size, self.right_hand,
+                                        self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                        None if prior is None else prior.detach().contiguous().float(), self.shape_stiffness,
+                                        None, keypoints, confidence, self.kp_weight, self.kp_max, limits, self.limit_weight,
+                                        self._pairs(), self.collision_weight)
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, radii=None):
+        observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
+        params = params.detach().contiguous().float()
+        A, g, cost, count, C, R, gs = ops.sphere_icp_radii_normal(
+            observed, view, params, *self._tables()[:4], self._radii(radii, observed.shape[0]), self.group_size, self.right_hand,
+            self.pixel_to_model, self.fg_max, self.max_dist)[:7]
+        A, g, cost = ops.sphere_prior_normal(view, params, *self._tables()[:4], self.right_hand, keypoints, confidence,
+                                             self.kp_weight, self.kp_max, limits, self.limit_weight, (A, g, cost))[:3]
+        A, g, cost = ops.sphere_collision_normal(params, *self._tables()[:4], self.right_hand, self._pairs(),
+                                                 self.collision_weight, (A, g, cost))[:3]
+        return A, g, cost, count, C, R, gs
+
+
 class DepthRender(nn.Module):
     """mesh/render.py:315-331.  forward(T[B,17,4,4], rand_fx[B]=None) -> depth
     [B,S,S] in mm, background 100: skinning + camera (one launch), triangle raster
