@@ -38,6 +38,48 @@ def test_loader_signatures_cover_the_header():
     assert b"invalid" in h.shr_error_string(-1)
 
 
+def declared_signatures():
+    """{name: ([class of each parameter], class of the return type)} of every shr_* declaration of the header, comments
+    stripped; a class is pointer, int (int, int32_t), unsigned, float, double or longlong."""
+    src = open(os.path.join(ROOT, "include", "spherehand_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = re.sub(r"^[ \t]*#[^\n]*", ";", src, flags=re.M)          # (a preprocessor line ends what stands before it)
+
+    def classify(decl):
+        words = decl.replace("*", " * ").split()
+        if "*" in words:
+            return "pointer"
+        words = [w for w in words if w not in ("const", "signed")]
+        for cls, spelled in (("longlong", ["long", "long"]), ("unsigned", ["unsigned"]), ("unsigned", ["unsigned", "int"]),
+                             ("int", ["int"]), ("int", ["int32_t"]), ("float", ["float"]), ("double", ["double"])):
+            if words == spelled or words[:-1] == spelled:          # (with or without the parameter's name)
+                return cls
+        raise AssertionError("a type this test does not know: %r" % decl)
+
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ \t\n\*]*?)\b(shr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() in ("", "void") else [classify(p) for p in params.split(",")]
+        assert name not in out, name
+        out[name] = (params, classify(ret))
+    return out
+
+
+def test_loader_signatures_match_the_declarations():
+    """Every hand-written argument list of _lib.SIGNATURES against the header's declaration: the number of arguments, the
+    class of each in order, and the return type."""
+    from spherehand_amd import _lib
+    classes = {ctypes.c_void_p: "pointer", ctypes.c_char_p: "pointer", ctypes.c_int: "int", ctypes.c_uint: "unsigned",
+               ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_longlong: "longlong"}
+    of = lambda t: "pointer" if issubclass(t, ctypes._Pointer) else classes[t]     # noqa: E731
+    declared = declared_signatures()
+    assert sorted(declared) == declared_symbols() == sorted(_lib.SIGNATURES) and len(declared) >= 136
+    for name, (args, res) in _lib.SIGNATURES.items():
+        want_args, want_res = declared[name]
+        assert [of(t) for t in args] == want_args, "%s: the loader has %s, the header %s" % (name, [of(t) for t in args], want_args)
+        assert of(res) == want_res, "%s returns %s in the header" % (name, want_res)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from spherehand_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
