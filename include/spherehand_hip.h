@@ -1536,6 +1536,55 @@ int shr_pose_lm_seq2_step(void *state, const double *A, const double *g, const d
                           int B, int T, float *trial_out, float *params, float *cost /* [S] */, float *cost0 /* [S] */,
                           void *workspace, void *stream);
 
+/* The uncertainty of the sequence fit: marginal covariances of the banded solve --------------------------------------------------
+ * Every fit above returns a pose and a cost and does not say how well the images determined the pose: a finger the view hides
+ * (DESIGN.md 4.4t, 4.4u), the direction one depth view leaves free (4.4n), arrive as numbers like any other.  The Gauss-Newton
+ * matrix that shr_pose_lm_seq2_step factorises is the inverse covariance of the estimate (the Laplace approximation at the
+ * given pose, per unit of residual variance); this entry is the other half of that block Cholesky, the DIAGONAL blocks of the
+ * inverse of the block-pentadiagonal matrix (selected inversion), and their projection onto the spheres.  The reference has no
+ * counterpart.  Layout: the sequence steps', B = S T, the frames of a sequence adjacent.
+ *   shr_pose_lm_seq2_covariance   H is the UNDAMPED matrix of a sequence (lambda = 0): diagonal blocks M_t = A_t + diag(mu)
+ *       (the LOWER triangle of A_t read), E_t at (t, t + 1), F_t at (t, t + 2); mu = stiffness[26] or, NULL, 0 -- the prior's
+ *       information, so that a pose the images do not determine still has a finite covariance.  F == NULL: no second band.
+ *       E == NULL: no coupling (F is then not read either), every frame its own system.  With T == 1 neither is read; E of a
+ *       sequence's last frame and F of its last two are never read.
+ *       Forward over t, shr_pose_lm_seq2_step's factorisation at lambda = 0, operation for operation:
+ *         D_t = M_t - W_{t-1} W_{t-1}^T - V_{t-2} V_{t-2}^T, per entry the W product subtracted first and then the V product,
+ *               each m ascending, then the column recurrence of shr_pose_lm_step; L_t L_t^T = D_t;
+ *         W_t = (E_t^T - V_{t-1} W_{t-1}^T) L_t^-T (t <= T - 2), V_t = F_t^T L_t^-T (t <= T - 3), the product a chain from 0,
+ *               m ascending; N_t = L_t^-1; each by 26 triangular solves, row k of the transposed block
+ *               X[k][:] = (((X[k][:] - L[k][0] X[0][:]) - L[k][1] X[1][:]) - ...) / L[k][k], N_t from the identity.
+ *       Backward over t, with Z = H^-1, P_t = W_t N_t and Q_t = V_t N_t:
+ *         Z_{t+1,t} = (-(Z_{t+1,t+1} P_t)) - Z_{t+2,t+1}^T Q_t
+ *         Z_{t+2,t} = (-(Z_{t+2,t+1} P_t)) - Z_{t+2,t+2} Q_t
+ *         Z_{t,t}   = (N_t^T N_t - P_t^T Z_{t+1,t}) - Q_t^T Z_{t+2,t}
+ *       every matrix product entry by entry a chain from 0 over the inner index, ascending, all 26 terms; a term that reaches
+ *       past the end of the sequence (or whose band is absent) is not formed.  For T == 1, Z = N_0^T N_0.
+ *       -> cov[B,26,26] = Z_tt, the LOWER triangle computed and mirrored: bit-symmetric.
+ *       -> sphere_cov[B,J,6] = xx xy xz yy yz zz of C_j(t) = Jc_j(t) Z_tt Jc_j(t)^T, Jc_j = jac[3j .. 3j + 2, :] promoted to
+ *       fp64 (shr_pose_keypoints_jacobian's, MODEL frame): mm^2 per unit of residual variance.  Entry (a, b) =
+ *       sum_k (sum_m Jc[a][m] Z[m][k]) Jc[b][k], k and m ascending, chains from 0.  Written iff jac AND sphere_cov are given;
+ *       exactly one of the two NULL: SHR_EINVAL.
+ *       -> status[S] int32: 0 where the sequence factorised; 1 + t where t is the first frame with a pivot that is not
+ *       positive and finite -- every cov and sphere_cov entry of ALL that sequence's frames is then a NaN.
+ *       All fp64, every sum in index order, the W (P) term before the V (Q) term, nothing contracted, no atomics: bitwise
+ *       reproducible, whatever thread owns an entry.  A sequence does not depend on the other sequences of the batch.  Launch
+ *       shape: one workgroup of 256 threads per sequence (the chain over t is inherent), then, with jac, one workgroup per
+ *       frame for the projection; no host synchronisation: capturable in a hipGraph.
+ *       workspace: shr_pose_lm_seq2_covariance_workspace_bytes(B) = 16 320 B bytes (2040 doubles per frame: N_t, W_t and V_t,
+ *       680 each), 16-byte aligned, -1 for B < 0; written before it is read in every call.
+ *       What it is NOT: saturated rows are absent from A, so a truncated term is silent here as well; it says nothing about
+ *       another basin; the residual variance is the caller's.
+ *   Argument rules, checked before the B == 0 no-op: B >= 0, 1 <= T, B % T == 0, 1 <= J (SHR_EINVAL otherwise); J above 64,
+ *   B above 65535: SHR_ETOOLARGE.  NULLs other than E, F, stiffness and the pair (jac, sphere_cov); misaligned pointers
+ *   (4 bytes; A, E, F, cov, sphere_cov 8; workspace 16): SHR_EINVAL. */
+long long shr_pose_lm_seq2_covariance_workspace_bytes(int B);
+int shr_pose_lm_seq2_covariance(const double *A, const double *E /* or NULL */, const double *F /* or NULL */,
+                                const float *stiffness /* [26] or NULL */, const float *jac /* [B,3J,26] or NULL */,
+                                int B, int T, int J, double *cov /* [B,26,26] */,
+                                double *sphere_cov /* [B,J,6]: xx xy xz yy yz zz, or NULL */,
+                                int32_t *status /* [S] */, void *workspace, void *stream);
+
 /* Parameters that the frames of a group SHARE: the arrowhead step --------------------------------------------------------------
  * Every fit above treats the model's constants -- the sphere radii first of all -- as given, and DESIGN.md 4.4p and 4.4s name
  * them as the weakest thing left.  A constant of the hand belongs to the person, not the frame: it is one vector sigma [K]

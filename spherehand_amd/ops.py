@@ -2944,6 +2944,57 @@ def pose_lm_seq2_step(state, A, g, E, F, cost_data, trial, seq_len, prior=None, 
     return (trial_out if solve else None), params, cost, cost0
 
 
+def pose_lm_covariance(A, E, F, seq_len, stiffness=None, jac=None, workspace=None):
+    """The marginal covariances of the sequence fit (include/spherehand_hip.h, shr_pose_lm_seq2_covariance): A [B,26,26], E
+    and F [B,26,26] fp64 (or None: F None no second band, E None no coupling at all), B = S seq_len -> (cov [B,26,26] fp64,
+    the diagonal blocks of the inverse of the UNDAMPED block-pentadiagonal matrix with diagonal blocks A_t + diag(stiffness);
+    sphere_cov [B,J,3,3] fp64 = Jc_j cov Jc_j^T per sphere with jac [B,3J,26] (pose_keypoints_jacobian's), None without;
+    status [S] int32: 0, or 1 + the first frame whose pivot is not positive and finite -- that sequence's cov and sphere_cov
+    are NaN on all its frames).  The Gauss-Newton (Laplace) covariance per unit of residual variance; all fp64 in a stated
+    order, bitwise reproducible.  workspace: shr_pose_lm_seq2_covariance_workspace_bytes(B) bytes to use instead of a new
+    buffer.  One launch, two with jac, on torch's current stream; the six stored values per sphere are expanded to the
+    symmetric 3 x 3 in torch."""
+    _check_input(A, "A", torch.float64)
+    if A.dim() != 3 or tuple(A.shape[1:]) != (26, 26):
+        raise RuntimeError("A must be [B,26,26]")
+    B, dev = A.shape[0], A.device
+    T = _sphere_temporal_args(B, dev, seq_len, 0.0, 0.0, None)[0]
+    for t, name in ((E, "E"), (F, "F")):
+        if t is None:
+            continue
+        _check_input(t, name, torch.float64)
+        if tuple(t.shape) != (B, 26, 26) or t.device != dev:
+            raise RuntimeError("%s must be [B,26,26] fp64 on A's device" % name)
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,) or stiffness.device != dev:
+            raise RuntimeError("stiffness must be [26] on A's device")
+    J = 1
+    if jac is not None:
+        _check_input(jac, "jac")
+        if jac.dim() != 3 or jac.shape[0] != B or jac.shape[2] != 26 or jac.shape[1] % 3 != 0 or jac.shape[1] == 0 or jac.device != dev:
+            raise RuntimeError("jac must be [B,3J,26] on A's device")
+        J = jac.shape[1] // 3
+    lib = _lib.lib()
+    need = lib.shr_pose_lm_seq2_covariance_workspace_bytes(B)
+    if workspace is not None and workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError("workspace must hold shr_pose_lm_seq2_covariance_workspace_bytes(B) = %d bytes" % need)
+    with _on(dev):
+        cov = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+        six = None if jac is None else torch.empty((B, J, 6), dtype=torch.float64, device=dev)
+        status = torch.empty((B // T,), dtype=torch.int32, device=dev)
+        if workspace is None:
+            workspace = torch.empty((max(1, need // 8),), dtype=torch.float64, device=dev)
+        _lib.check(lib.shr_pose_lm_seq2_covariance(_ptr(A), _ptr(E), _ptr(F), _ptr(stiffness), _ptr(jac), B, T, J, _ptr(cov),
+                                                   _ptr(six), _ptr(status), _ptr(workspace), _stream()),
+                   "shr_pose_lm_seq2_covariance")
+        sphere_cov = None
+        if six is not None:                                  # (no index tensor: nothing goes from the host to the device)
+            xx, xy, xz, yy, yz, zz = six.unbind(-1)
+            sphere_cov = torch.stack((xx, xy, xz, xy, yy, yz, xz, yz, zz), -1).view(B, J, 3, 3)
+    return cov, sphere_cov, status
+
+
 def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model, fg_max,
                           max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background, keypoints, confidence,
                           kp_weight, kp_max, limits, limit_weight, collision, collision_weight, temporal_weight, ts_max,

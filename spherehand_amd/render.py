@@ -848,6 +848,8 @@ class SpherePoseFitter(nn.Module):
         solve(observed, params0, view=None, prior=None) -> (params, cost0, cost)
         normal_equations(observed, params, view=None) -> (A [B,26,26], g [B,26], cost [B] fp64, count [B] int32,
                                                           moments [B,41,12] fp64: per sphere sum u u^T, sum d u, sum d^2, rows)
+        uncertainty(observed, params, <normal_equations' further arguments>, residual_var=1.0)
+            -> (cov [B,26,26], sphere_cov [B,41,3,3], sigma [B,41] mm, ok [S]); inherited by every fitter below
         views_from_cameras(camera_poses, inv_camera_poses, ref=0) -> view [B,V,4,4]   (MultiViewMeshPoseFitter's)
     observed is [B,V,H,W] with view [B,V,4,4] rigid (x_v = R x + t; its rotation is NOT checked to be orthonormal), or
     [B,H,W] with view=None: one view, the identity.  A REFINEMENT from a start pose: the intended start is
@@ -906,6 +908,33 @@ class SpherePoseFitter(nn.Module):
         return ops.sphere_icp_normal(observed, view, params.detach().contiguous().float(), self.fk.offset, self.fk.offset_inv,
                                      self.kp_bone, self.kp_wv, self.radii, self.right_hand, self.pixel_to_model, self.fg_max,
                                      self.max_dist)
+
+    @staticmethod
+    def _bands(equations):
+        """(E, F) of what this class's normal_equations returns: the frame fitters have neither"""
+        return None, None
+
+    @torch.no_grad()
+    def uncertainty(self, observed, params, *args, residual_var=1.0, **kwargs):
+        """How well the images determine the pose `params` [B,26]: the class's own normal_equations(observed, params, ...)
+        evaluated there (the further arguments are that method's), and from its A -- and E and F where the class has them --
+        the marginal covariance of every frame (ops.pose_lm_covariance; include/spherehand_hip.h,
+        shr_pose_lm_seq2_covariance) with the fitter's stiffness as the prior's information and its seq_len (1 for the
+        frame fitters) -> (cov [B,26,26] fp64, sphere_cov [B,J,3,3] fp64 in the MODEL frame, mm^2, sigma [B,J] fp64 =
+        sqrt(trace sphere_cov), mm, ok [S] bool: False where a sequence's matrix is not positive definite, its frames NaN).
+        It is the Gauss-Newton (Laplace) covariance AT THE GIVEN POSE per unit of residual variance, times residual_var,
+        which is the caller's to estimate.  It is NOT a bound on the error: saturated rows contribute nothing, so a term cut
+        by max_dist, max_resid, kp_max, ts_max or acc_max is silent here as well; it says nothing about another basin (a
+        finger the view hides has a large sigma and can still be further off than it); without a stiffness a direction the
+        images leave free makes the matrix singular.  NO autograd through it."""
+        equations = self.normal_equations(observed, params, *args, **kwargs)
+        E, F = self._bands(equations)
+        params = params.detach().contiguous().float()
+        jac = ops.pose_keypoints_jacobian(params, self.fk.offset, self.fk.offset_inv, self.kp_bone, self.kp_wv, self.right_hand)[1]
+        cov, sphere_cov, status = ops.pose_lm_covariance(equations[0], E, F, getattr(self, 'seq_len', 1), self.stiffness, jac)
+        cov, sphere_cov = cov * float(residual_var), sphere_cov * float(residual_var)
+        sigma = (sphere_cov[..., 0, 0] + sphere_cov[..., 1, 1] + sphere_cov[..., 2, 2]).sqrt()
+        return cov, sphere_cov, sigma, status == 0
 
 
 class SphereRenderPoseFitter(SpherePoseFitter):
@@ -1161,6 +1190,10 @@ class SphereSequencePoseFitter(SphereCollisionPoseFitter):
         return ops.sphere_temporal_normal(params, *self._tables()[:4], self.seq_len, self.right_hand, self.temporal_weight,
                                           self.ts_max, self._frame_weight(frame_weight), (A, g, cost))
 
+    @staticmethod
+    def _bands(equations):
+        return equations[2], None
+
 
 class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
     """SphereSequencePoseFitter with a constant-velocity term: the energy of a sequence gains
@@ -1228,6 +1261,10 @@ class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
                                                                      frame_weight)
         return ops.sphere_accel_normal(params, *self._tables()[:4], self.seq_len, self.right_hand, self.accel_weight,
                                        self.acc_max, self._frame_weight(triple_weight), (A, g, cost), E)
+
+    @staticmethod
+    def _bands(equations):
+        return equations[2], equations[3]
 
 
 class SphereRadiiCalibrator(SphereCollisionPoseFitter):
@@ -1307,6 +1344,11 @@ class SphereRadiiCalibrator(SphereCollisionPoseFitter):
         A, g, cost = ops.sphere_collision_normal(params, *self._tables()[:4], self.right_hand, self._pairs(),
                                                  self.collision_weight, (A, g, cost))[:3]
         return A, g, cost, count, C, R, gs
+
+    def uncertainty(self, *args, **kwargs):
+        """Not available: the radii make the system an arrowhead, and the covariance of that system (the pose blocks'
+        marginals with the shared block eliminated) is out of scope."""
+        raise NotImplementedError("SphereRadiiCalibrator has no uncertainty: the arrowhead system's covariance is not implemented")
 
 
 class DepthRender(nn.Module):
