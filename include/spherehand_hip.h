@@ -1585,6 +1585,75 @@ int shr_pose_lm_seq2_covariance(const double *A, const double *E /* or NULL */, 
                                 double *sphere_cov /* [B,J,6]: xx xy xz yy yz zz, or NULL */,
                                 int32_t *status /* [S] */, void *workspace, void *stream);
 
+/* The sliding window: marginalise the frame that leaves, carry it as a prior -------------------------------------------------------
+ * The sequence fits above take their frames at once and forget them.  A fixed-lag smoother keeps a window of constant length
+ * over a stream: when the oldest frame leaves, everything the fit knew through it -- its own image terms, its stiffness, the
+ * temporal and acceleration rows that reach it and the prior it carried itself -- is folded into a Gaussian prior on the frames
+ * that stay.  That prior is the Schur complement of the leaving frame's block; for a block-pentadiagonal system it touches the
+ * next two frames only, so the window's equations stay block-pentadiagonal and shr_pose_lm_seq2_step and
+ * shr_pose_lm_seq2_covariance take them as they are.  The reference has no counterpart.  Layout: the sequence steps', B = S T.
+ *   shr_pose_window_marginalize   Input: the DEPARTING SYSTEM of each sequence, A, E (or NULL), F (or NULL), g, cost_data as
+ *       the sequence steps take them, evaluated at the poses trial [B,26] fp32; only frames 0 ... min(T, 3) - 1 of a sequence
+ *       are read.  prior [B,26] (or NULL: the trial itself, the difference an exact 0) and stiffness [26] (or NULL: 0) are
+ *       applied to FRAME 0 ONLY; the stiffness of the frames that stay remains the step's business.
+ *         M_0 = A_0 + diag(mu), the LOWER triangle of A_0 read;  b_0 = g_0 + mu (p_0 - prior_0), the differences in fp64 from
+ *         the fp32 values, as in the step's right-hand side;  b_1 = g_1, b_2 = g_2.
+ *       Arithmetic, all fp64:
+ *         1. L L^T = M_0 by the column recurrence of shr_pose_lm_step (lambda = 0);
+ *         2. X = L^-1 [E_0 | F_0 | b_0], 26 + 26 + 1 right-hand sides, by the row recurrence of shr_pose_lm_seq2_covariance:
+ *            X[k][:] = (((X[k][:] - L[k][0] X[0][:]) - L[k][1] X[1][:]) - ...) / L[k][k]; its parts are X_E, X_F and y;
+ *         3. Lambda_11 = A_1 - X_E^T X_E,  Lambda_12 = E_1 - X_E^T X_F,  Lambda_22 = A_2 - X_F^T X_F,
+ *            eta_1 = b_1 - X_E^T y,  eta_2 = b_2 - X_F^T y,
+ *            c = ((c_0 + cost_1) + cost_2) - y.y,  c_0 = cost_0 + mu_0 d_0^2 + ... + mu_25 d_25^2 (the step's chain: from
+ *            cost_0, ascending, each term mu_i (d_i d_i), d = p_0 - prior_0), the costs of frames that do not exist not added;
+ *            every product entry a chain from 0 over the inner index, ascending, all 26 terms, then subtracted ONCE;
+ *         4. a band that is absent contributes nothing: without F (F == NULL or T < 3) no X_F product is formed or
+ *            subtracted; with T == 2 the blocks and rows of frame 2 are +0; for T == 1 or E == NULL the prior is an exact +0
+ *            throughout (Lambda and eta; the LOWER triangles of A_1 and A_2 are read otherwise) and c is as above.
+ *       -> Lambda[S,52,52] fp64, frame 1 then frame 2: the LOWER triangle computed and mirrored, bit-symmetric; the
+ *       Lambda_12 block has frame 1's rows and frame 2's columns.  -> eta[S,52], offset[S] = c, fp64.
+ *       -> point[S,52] fp32: the trial poses of frames 1 and 2, the linearisation point; frames that do not exist: +0.
+ *       -> status[S] int32: 0 where every pivot of M_0 is positive and finite, 1 otherwise -- every Lambda, eta and offset
+ *       entry of THAT sequence is then an exact +0 and point is still written: the information is dropped, the tracker goes
+ *       on, the caller sees the status.
+ *       Every sum in index order, nothing contracted, no atomics, no matrix-core instruction: bitwise reproducible, whatever
+ *       thread owns an entry.  A sequence does not depend on the other sequences of the batch.  Launch shape: one workgroup of
+ *       256 threads per sequence; no host synchronisation: capturable in a hipGraph.  workspace: none is needed;
+ *       shr_pose_window_marginalize_workspace_bytes(B, T) is 0 (-1 on a negative size).
+ *       What it is NOT: the prior is the system's linearisation at `trial` and is never relinearised; rows that are saturated
+ *       there are absent from A and silent in the prior as well; a failed pivot drops the past of that sequence.
+ *   Argument rules, checked before the B == 0 no-op: B >= 0, 1 <= T, B % T == 0 (SHR_EINVAL otherwise); B above 65535:
+ *   SHR_ETOOLARGE.  NULLs other than E, F, prior, stiffness and workspace; misaligned pointers (4 bytes; A, g, E, F, cost_data,
+ *   Lambda, eta, offset 8): SHR_EINVAL.
+ *   shr_pose_window_prior_normal   The normal equations of the carried prior at the poses trial [B,26] fp32.  Per sequence,
+ *       in fp64 from the fp32 values: d = trial(frames 0, 1) - point, 52 entries (the first 26 when T == 1, and then only the
+ *       leading 26 x 26 block of Lambda and the first 26 entries of eta are read).
+ *         cost: (d^T (Lambda d) + 2 eta^T d) + offset, added to the sequence's FIRST frame; (Lambda d)_i a chain from 0 over
+ *               the columns ascending, d^T (Lambda d) and eta^T d chains from 0, i ascending (d_i (Lambda d)_i; eta_i d_i);
+ *         g:    the gradient of 1/2 the cost in the family's convention, (Lambda d)_i + eta_i, split onto frames 0 and 1;
+ *         A:    Lambda itself: Lambda_00 onto A_0 and Lambda_11 onto A_1 (the LOWER triangle of either block read),
+ *               Lambda_01 (frame 0's rows, frame 1's columns, read as stored) onto E_0.
+ *       accumulate as in shr_sphere_temporal_normal: 0 writes the term's A, g and cost of frames 0 and 1 (frame 1's cost an
+ *       exact +0); 1 ADDS, the LOWER triangle of A read and the sum written to both triangles.  accumulate_E as in
+ *       shr_sphere_accel_normal: 0 writes E_0, 1 adds to it.  Frames 2 ... T - 1, E of every frame but the first, and F are
+ *       NEVER touched.  active [S] int32 or NULL: a sequence whose entry is 0 has no term and NONE of its outputs is touched,
+ *       so that sequences without a prior yet can share a batch.  One add per entry, no atomics: bitwise reproducible.  Launch
+ *       shape: one workgroup per frame; no host synchronisation.  shr_pose_window_prior_normal_workspace_bytes(B, T) is 0
+ *       (-1 on a negative size).
+ *   Argument rules, checked before the B == 0 no-op: B >= 0, 1 <= T, B % T == 0, accumulate and accumulate_E 0 or 1 (SHR_EINVAL
+ *   otherwise); B above 65535: SHR_ETOOLARGE.  NULLs other than active, workspace and, with T == 1, E; misaligned pointers
+ *   (4 bytes; Lambda, eta, offset, A, g, E, cost 8): SHR_EINVAL. */
+long long shr_pose_window_marginalize_workspace_bytes(int B, int T);
+int shr_pose_window_marginalize(const double *A, const double *g, const double *E /* or NULL */, const double *F /* or NULL */,
+                                const double *cost_data, const float *trial, const float *prior /* [B,26] or NULL */,
+                                const float *stiffness /* [26] or NULL */, int B, int T, double *Lambda /* [S,52,52] */,
+                                double *eta /* [S,52] */, double *offset /* [S] */, float *point /* [S,52] */,
+                                int32_t *status /* [S] */, void *workspace, void *stream);
+long long shr_pose_window_prior_normal_workspace_bytes(int B, int T);
+int shr_pose_window_prior_normal(const float *trial, const double *Lambda, const double *eta, const double *offset,
+                                 const float *point, const int32_t *active /* [S] or NULL */, int B, int T, int accumulate,
+                                 int accumulate_E, double *A, double *g, double *E, double *cost, void *workspace, void *stream);
+
 /* Parameters that the frames of a group SHARE: the arrowhead step --------------------------------------------------------------
  * Every fit above treats the model's constants -- the sphere radii first of all -- as given, and DESIGN.md 4.4p and 4.4s name
  * them as the weakest thing left.  A constant of the hand belongs to the person, not the frame: it is one vector sigma [K]

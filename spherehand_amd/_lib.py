@@ -158,6 +158,10 @@ SIGNATURES = {
     "shr_pose_lm_seq2_step": ([_vp] * 9 + [_i] * 3 + [_vp] * 6, _i),
     "shr_pose_lm_seq2_covariance_workspace_bytes": ([_i], ctypes.c_longlong),
     "shr_pose_lm_seq2_covariance": ([_vp] * 5 + [_i] * 3 + [_vp] * 5, _i),
+    "shr_pose_window_marginalize_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_pose_window_marginalize": ([_vp] * 8 + [_i] * 2 + [_vp] * 7, _i),
+    "shr_pose_window_prior_normal_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_pose_window_prior_normal": ([_vp] * 6 + [_i] * 4 + [_vp] * 6, _i),
     "shr_sphere_icp_radii_normal_workspace_bytes": ([_i, _i, _i, _i, _i], ctypes.c_longlong),
     "shr_sphere_icp_radii_normal": ([_vp] * 5 + [_i] * 6 + [_f] * 6 + [_vp] * 12, _i),
     "shr_pose_lm_shared_state_bytes": ([_i, _i, _i], ctypes.c_longlong),

@@ -2995,13 +2995,112 @@ def pose_lm_covariance(A, E, F, seq_len, stiffness=None, jac=None, workspace=Non
     return cov, sphere_cov, status
 
 
+def _window_prior_args(prior, S, T, dev, active):
+    """(Lambda [S,52,52], eta [S,52], offset [S] fp64, point [S,52] fp32) of pose_window_marginalize, and active [S] int32 or
+    None, checked for a batch of S sequences on `dev`"""
+    try:
+        Lambda, eta, offset, point = prior
+    except (TypeError, ValueError):
+        raise RuntimeError("the window prior is (Lambda, eta, offset, point)")
+    for t, name, shape, dtype in ((Lambda, "Lambda", (S, 52, 52), torch.float64), (eta, "eta", (S, 52), torch.float64),
+                                  (offset, "offset", (S,), torch.float64), (point, "point", (S, 52), torch.float32)):
+        _check_input(t, name, dtype)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("%s must be %s on the parameters' device" % (name, shape))
+    if active is not None:
+        _check_input(active, "active", torch.int32)
+        if tuple(active.shape) != (S,) or active.device != dev:
+            raise RuntimeError("active must be [S] int32 on the parameters' device")
+    return Lambda, eta, offset, point, active
+
+
+def pose_window_marginalize(A, g, E, F, cost_data, trial, seq_len, prior=None, stiffness=None):
+    """The frame that leaves a sliding window folded into a Gaussian prior on the next two frames (include/spherehand_hip.h,
+    shr_pose_window_marginalize): the DEPARTING system A [B,26,26], g [B,26], E, F [B,26,26] (or None), cost_data [B] fp64
+    at the poses trial [B,26] fp32, B = S seq_len, of which frames 0 ... min(seq_len, 3) - 1 are read; prior [B,26] and
+    stiffness [26] apply to frame 0 only -> (Lambda [S,52,52], eta [S,52], offset [S] fp64, point [S,52] fp32 the trial poses
+    of frames 1 and 2, status [S] int32: 1 where frame 0's matrix has a pivot that is not positive and finite -- that
+    sequence's record is then an exact +0).  All fp64 in a stated order, bitwise reproducible; one launch on torch's current
+    stream."""
+    _check_input(trial, "trial")
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    B, dev = trial.shape[0], trial.device
+    T = _sphere_temporal_args(B, dev, seq_len, 0.0, 0.0, None)[0]
+    for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26)), (F, "F", (B, 26, 26)),
+                           (cost_data, "cost_data", (B,))):
+        if t is None and name in ("E", "F"):
+            continue
+        _check_input(t, name, torch.float64)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26) or prior.device != dev:
+            raise RuntimeError("prior must be [B,26] on trial's device")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,) or stiffness.device != dev:
+            raise RuntimeError("stiffness must be [26] on trial's device")
+    S = B // T
+    lib = _lib.lib()
+    with _on(dev):
+        Lambda = torch.empty((S, 52, 52), dtype=torch.float64, device=dev)
+        eta = torch.empty((S, 52), dtype=torch.float64, device=dev)
+        offset = torch.empty((S,), dtype=torch.float64, device=dev)
+        point = torch.empty((S, 52), dtype=torch.float32, device=dev)
+        status = torch.empty((S,), dtype=torch.int32, device=dev)
+        _lib.check(lib.shr_pose_window_marginalize(_ptr(A), _ptr(g), _ptr(E), _ptr(F), _ptr(cost_data), _ptr(trial), _ptr(prior),
+                                                   _ptr(stiffness), B, T, _ptr(Lambda), _ptr(eta), _ptr(offset), _ptr(point),
+                                                   _ptr(status), None, _stream()), "shr_pose_window_marginalize")
+    return Lambda, eta, offset, point, status
+
+
+def pose_window_prior_normal(trial, Lambda, eta, offset, point, seq_len, into=None, E=None, active=None):
+    """The normal equations of the prior a sliding window carries (include/spherehand_hip.h, shr_pose_window_prior_normal):
+    trial [B,26] fp32, B = S seq_len, and pose_window_marginalize's record -> (A [B,26,26], g [B,26], E [B,26,26], cost [B]
+    fp64).  The term is (d^T Lambda d + 2 eta^T d) + offset with d = trial(frames 0, 1) - point; it touches frames 0 and 1 of
+    a sequence and E of frame 0 alone.  into = (A, g, cost) of the other terms at the same poses: the term is ADDED to them
+    in place and they are returned; without it the three are new, +0 on the frames the term does not reach.  E: the other
+    terms' E to add to in place; without it a new one, +0 outside the term.  active [S] int32: a sequence with 0 has no term
+    and is left alone.  One launch on torch's current stream."""
+    _check_input(trial, "trial")
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    B, dev = trial.shape[0], trial.device
+    T = _sphere_temporal_args(B, dev, seq_len, 0.0, 0.0, None)[0]
+    Lambda, eta, offset, point, active = _window_prior_args((Lambda, eta, offset, point), B // T, T, dev, active)
+    if into is not None:
+        A, g, cost = into
+    for t, name, shape in (() if into is None else ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,)))) + \
+            (() if E is None else ((E, "E", (B, 26, 26)),)):
+        _check_input(t, name, torch.float64)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("the %s to accumulate into must be %s fp64 on trial's device" % (name, shape))
+    add_E = int(E is not None)
+    lib = _lib.lib()
+    with _on(dev):
+        if into is None:                                     # (an inactive sequence and frames >= 2 are not written: +0)
+            A = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.zeros((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.zeros((B,), dtype=torch.float64, device=dev)
+        if E is None:
+            E = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)
+        _lib.check(lib.shr_pose_window_prior_normal(_ptr(trial), _ptr(Lambda), _ptr(eta), _ptr(offset), _ptr(point), _ptr(active),
+                                                    B, T, int(into is not None), add_E, _ptr(A), _ptr(g), _ptr(E), _ptr(cost),
+                                                    None, _stream()), "shr_pose_window_prior_normal")
+    return A, g, E, cost
+
+
 def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model, fg_max,
                           max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background, keypoints, confidence,
                           kp_weight, kp_max, limits, limit_weight, collision, collision_weight, temporal_weight, ts_max,
-                          frame_weight, accel_weight, acc_max, triple_weight):
-    """The loop of sphere_icp_sequence and sphere_icp_trajectory.  Without a weighted acceleration term (accel_weight = 0 or
-    seq_len < 3) it is sphere_icp_sequence's: shr_pose_lm_seq_begin / _step, no F; with one, shr_sphere_accel_normal follows
-    the first-difference entry and the step is shr_pose_lm_seq2_begin / _step's."""
+                          frame_weight, accel_weight, acc_max, triple_weight, window_prior=None):
+    """The loop of sphere_icp_sequence, sphere_icp_trajectory and sphere_icp_window.  Without a weighted acceleration term
+    (accel_weight = 0 or seq_len < 3) it is sphere_icp_sequence's: shr_pose_lm_seq_begin / _step, no F; with one,
+    shr_sphere_accel_normal follows the first-difference entry and the step is shr_pose_lm_seq2_begin / _step's.
+    window_prior = (Lambda, eta, offset, point) of pose_window_marginalize (None: no prior, no launch): the carried prior's
+    entry shr_pose_window_prior_normal (accumulate = 1) follows shr_sphere_accel_normal in every evaluation."""
     B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
                                                     max_dist, "start parameters")
     max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
@@ -3016,6 +3115,8 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
     temporal = T > 1 and temporal_weight > 0.0
     accel_weight, acc_max = _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight)
     accel = T > 2 and accel_weight > 0.0
+    if window_prior is not None:
+        window_prior = _window_prior_args(window_prior, B // T, T, dev, None)
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
@@ -3077,6 +3178,10 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
                 _lib.check(lib.shr_sphere_accel_normal(_ptr(kp), _ptr(jac), _ptr(triple_weight), accel_weight, acc_max, B, T, J,
                                                        1, int(temporal), _ptr(A), _ptr(g), _ptr(E), _ptr(F), _ptr(cost_data),
                                                        _ptr(accel_rows), None, stream), "shr_sphere_accel_normal")
+            if window_prior is not None:                       # (E of frame 0: written where no entry above has written it)
+                _lib.check(lib.shr_pose_window_prior_normal(_ptr(trial), *(_ptr(t) for t in window_prior), B, T, 1,
+                                                            int(temporal or accel), _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data),
+                                                            None, stream), "shr_pose_window_prior_normal")
             solve = int(it < iters)
             tail = (_ptr(cost_data), _ptr(trial), _ptr(prior), _ptr(stiffness), solve, B, T, _ptr(trial) if solve else None,
                     _ptr(params), _ptr(cost), _ptr(cost0), _ptr(seq_ws) if solve else None, stream)
@@ -3105,6 +3210,26 @@ def sphere_icp_trajectory(observed, view, params0, offset, offset_inv, bone, wv,
                                  fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
                                  keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
                                  temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight)
+
+
+def sphere_icp_window(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand=True,
+                      pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
+                      stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
+                      keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
+                      collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None,
+                      accel_weight=1.0, acc_max=float("inf"), triple_weight=None, window_prior=None):
+    """sphere_icp_trajectory over a sliding window that carries its marginalised past: window_prior = (Lambda [S,52,52],
+    eta [S,52], offset [S] fp64, point [S,52] fp32), pose_window_marginalize's record, adds
+    (d^T Lambda d + 2 eta^T d) + offset, d = (p_0, p_1) - point, to the energy of each sequence (a record that a failed pivot
+    left +0 adds nothing) -> (params [B,26], cost0 [S], cost [S]).  Each evaluation is
+    sphere_icp_trajectory's launches with shr_pose_window_prior_normal (accumulate = 1; accumulate_E = 1 iff an entry before
+    it wrote E in this evaluation) after shr_sphere_accel_normal; the step is unchanged, the prior's blocks being blocks of
+    the same block-pentadiagonal system.  window_prior = None: no launch is added, and the loop is sphere_icp_trajectory's
+    launch for launch and bit for bit."""
+    return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
+                                 fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
+                                 keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
+                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight, window_prior)
 
 
 PoseLmSharedMaxK = 64        # shared parameters of a group at most (shr_pose_lm_shared_step)

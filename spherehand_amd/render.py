@@ -1267,6 +1267,146 @@ class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
         return equations[2], equations[3]
 
 
+class SphereWindowTracker(SphereTrajectoryPoseFitter):
+    """SphereTrajectoryPoseFitter over a STREAM of frames: a fixed-lag smoother.  seq_len is the length W of a window that
+    slides over S streams one frame at a time; when the oldest frame leaves, everything the fit knew through it -- its own
+    image, keypoint, limit and collision terms, its stiffness, the temporal and acceleration rows that reach it and the prior
+    it carried itself -- is folded into a Gaussian prior on the next two frames (ops.pose_window_marginalize;
+    include/spherehand_hip.h, shr_pose_window_marginalize), the Schur complement of its block, and the window is fitted
+    again with that prior as one more term (ops.sphere_icp_window, shr_pose_window_prior_normal).  The window's equations
+    stay block-pentadiagonal.  On a quadratic energy marginalise-and-slide IS the full-batch fit of the newest frames
+    (DESIGN.md 4.4z); on this one it is that fit's linearisation.
+        begin(observed, params0, view=None, keypoints=None, confidence=None) -> (window, params [S W,26], cost0 [S], cost [S])
+            the first W frames of S streams in solve's layout (B = S W, a stream's frames adjacent), fitted without a prior:
+            SphereTrajectoryPoseFitter.solve bit for bit.  window: a dict of the fitted poses `params`, the poses the fit
+            started from `start`, the per-frame `inputs` and the carried `prior` (None), for advance
+        advance(window, observed_new, params_new=None, view_new=None, keypoints_new=None, confidence_new=None)
+            -> (window, params [S W,26], cost0 [S], cost [S], status [S] int32, left [S,26])
+            one new frame per stream ([S,H,W], or [S,V,H,W] with view_new [S,V,4,4]): the oldest frame is marginalised at the
+            window's fitted poses, the window shifts by one frame, the new frame starts from params_new [S,26] or, without it,
+            from the constant-velocity extrapolation 2 p_{W-1} - p_{W-2}, and the window is fitted with the new prior.
+            left: the pose the leaving frame left with, the fixed-lag smoothed estimate; status: the marginalisation's, 1
+            where the leaving frame's matrix had a pivot that is not positive and finite.  The new window also holds
+            `departing`, the equations (A, g, E, F, cost, trial) that were marginalised, and `record`, the entry's outputs
+        track(observed [S,N,...], params0 [S,N,26] or [S,W,26], view=None, keypoints=None, confidence=None)
+            -> (smoothed [S,N,26], filtered [S,N,26], status [S,N-W])
+            the loop over advance for a recorded stream: smoothed is each frame's pose when it left the window (the last
+            window's poses at the end), filtered its pose after the first fit it was part of.  N == W is solve bit for bit
+        normal_equations(..., window=None) -> SphereTrajectoryPoseFitter's, with the prior's term added when a window that
+            carries one is given: uncertainty(observed, params, ..., window=window) then returns marginals that carry the
+            marginalised past.
+    The departing system is formed from the existing entries alone, nothing restated: frame 0's own terms by
+    SphereCollisionPoseFitter.normal_equations on frame 0, the temporal entry weighted so that only the pair (0, 1) remains,
+    the acceleration entry weighted so that only the triple centred at 1 remains, both over sub-sequences of min(W, 3)
+    frames, and the carried prior by shr_pose_window_prior_normal.
+    What it does NOT do: the prior is linearised ONCE, at the poses the frame left with, and never relinearised -- a later
+    fit that moves frames 1 and 2 far from there meets a quadratic that no longer is the energy's; rows that are saturated at
+    that moment (max_dist, max_resid, kp_max, ts_max, acc_max) are silent in the prior for good, as in DESIGN.md 4.4y, so a
+    finger hidden when its frame leaves is not remembered; a failed pivot drops the whole past of that stream (status); there
+    is still ONE accept decision per window; frame_weight, triple_weight and an explicit prior pose are not taken.
+    Everything else is SphereTrajectoryPoseFitter's: a refinement from a start pose, NO autograd, the rotation NOT checked."""
+
+    def _fit(self, inputs, params0, prior):
+        observed, view, keypoints, confidence, limits = inputs
+        return ops.sphere_icp_window(observed, view, params0, *self._tables(), self.seq_len, self.right_hand,
+                                     self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
+                                     None, self.render_weight, self.max_resid, self.background, keypoints, confidence,
+                                     self.kp_weight, self.kp_max, limits, self.limit_weight, self._pairs(), self.collision_weight,
+                                     self.temporal_weight, self.ts_max, None, self.accel_weight, self.acc_max, None, prior)
+
+    @torch.no_grad()
+    def begin(self, observed, params0, view=None, keypoints=None, confidence=None):
+        inputs = self._targets(observed, view, keypoints, confidence)
+        start = params0.detach().contiguous().float()
+        if start.dim() != 2 or start.shape[0] % self.seq_len != 0:
+            raise RuntimeError("begin takes params0 [S W,26], the first W = %d frames of every stream" % self.seq_len)
+        params, cost0, cost = self._fit(inputs, start, None)
+        return dict(params=params, start=start, inputs=inputs, prior=None), params, cost0, cost
+
+    def _departing(self, window):
+        """(A, g, E, F, cost, trial) over sub-sequences of n = min(W, 3) frames: every term that involves frame 0"""
+        W, n = self.seq_len, min(self.seq_len, 3)
+        observed, view, keypoints, confidence, _ = window['inputs']
+        S = window['params'].shape[0] // W
+        first = lambda t: None if t is None else t.view((S, W) + tuple(t.shape[1:]))[:, 0].contiguous()   # noqa: E731
+        trial = window['params'].view(S, W, 26)[:, :n].reshape(S * n, 26).contiguous()
+        A0, g0, c0 = SphereCollisionPoseFitter.normal_equations(self, first(observed), first(window['params']), first(view),
+                                                                first(keypoints), first(confidence))[:3]
+        dev = trial.device
+        A = torch.zeros((S * n, 26, 26), dtype=torch.float64, device=dev)
+        g = torch.zeros((S * n, 26), dtype=torch.float64, device=dev)
+        cost = torch.zeros((S * n,), dtype=torch.float64, device=dev)
+        A.view(S, n, 26, 26)[:, 0].copy_(A0)
+        g.view(S, n, 26)[:, 0].copy_(g0)
+        cost.view(S, n)[:, 0].copy_(c0)
+        at = lambda t: torch.zeros((S, n), device=dev).index_fill_(1, torch.tensor([t], device=dev), 1.0).reshape(S * n)   # noqa: E731
+        A, g, E, cost, _ = ops.sphere_temporal_normal(trial, *self._tables()[:4], n, self.right_hand, self.temporal_weight,
+                                                      self.ts_max, at(0), (A, g, cost))
+        F = None
+        if n == 3:
+            A, g, E, F, cost, _ = ops.sphere_accel_normal(trial, *self._tables()[:4], n, self.right_hand, self.accel_weight,
+                                                          self.acc_max, at(1), (A, g, cost), E)
+        if window['prior'] is not None:
+            A, g, E, cost = ops.pose_window_prior_normal(trial, *window['prior'], n, (A, g, cost), E)
+        return A, g, E, F, cost, trial
+
+    @torch.no_grad()
+    def advance(self, window, observed_new, params_new=None, view_new=None, keypoints_new=None, confidence_new=None):
+        W, n = self.seq_len, min(self.seq_len, 3)
+        params = window['params']
+        S = params.shape[0] // W
+        new = self._targets(observed_new, view_new, keypoints_new, confidence_new)
+        if new[0].shape[0] != S or any((a is None) != (b is None) for a, b in zip(new[:4], window['inputs'][:4])):
+            raise RuntimeError("advance takes one new frame for each of the %d streams, with the inputs begin was given" % S)
+        departing = self._departing(window)
+        A, g, E, F, cost, trial = departing
+        prior0 = window['start'].view(S, W, 26)[:, :n].reshape(S * n, 26).contiguous()
+        record = ops.pose_window_marginalize(A, g, E, F, cost, trial, n, prior0, self.stiffness)
+        p = params.view(S, W, 26)
+        left = p[:, 0].clone()
+        if params_new is None:
+            params_new = 2.0 * p[:, W - 1] - p[:, W - 2] if W > 1 else p[:, 0]
+        params_new = params_new.detach().float().reshape(S, 1, 26)
+        shift = lambda old, t: None if old is None else \
+            torch.cat((old.view((S, W) + tuple(old.shape[1:]))[:, 1:], t.unsqueeze(1)), 1).reshape(old.shape).contiguous()   # noqa: E731
+        inputs = tuple(shift(a, b) for a, b in zip(window['inputs'][:4], new[:4])) + (new[4],)
+        start = torch.cat((p[:, 1:], params_new), 1).reshape(S * W, 26).contiguous()
+        prior = record[:4]
+        fitted, cost0, cost_w = self._fit(inputs, start, prior)
+        window = dict(params=fitted, start=start, inputs=inputs, prior=prior, departing=departing, record=record)
+        return window, fitted, cost0, cost_w, record[4], left
+
+    @torch.no_grad()
+    def track(self, observed, params0, view=None, keypoints=None, confidence=None):
+        W = self.seq_len
+        S, N = observed.shape[:2]
+        if N < W or params0.dim() != 3 or params0.shape[0] != S or params0.shape[1] not in (N, W):
+            raise RuntimeError("track takes observed [S,N,...], N >= W = %d, and params0 [S,N,26] or [S,W,26]" % W)
+        head = lambda t: None if t is None else t[:, :W].reshape((S * W,) + tuple(t.shape[2:]))   # noqa: E731
+        frame = lambda t, k: None if t is None else t[:, k]   # noqa: E731
+        window, params, _, _ = self.begin(head(observed), head(params0), head(view), head(keypoints), head(confidence))
+        filtered = torch.empty((S, N, 26), dtype=torch.float32, device=params.device)
+        smoothed = torch.empty_like(filtered)
+        filtered[:, :W] = params.view(S, W, 26)
+        status = torch.zeros((S, N - W), dtype=torch.int32, device=params.device)
+        for k in range(W, N):
+            window, params, _, _, st, left = self.advance(window, frame(observed, k), frame(params0, k) if params0.shape[1] == N
+                                                          else None, frame(view, k), frame(keypoints, k), frame(confidence, k))
+            smoothed[:, k - W], filtered[:, k], status[:, k - W] = left, params.view(S, W, 26)[:, W - 1], st
+        smoothed[:, N - W:] = params.view(S, W, 26)
+        return smoothed, filtered, status
+
+    @torch.no_grad()
+    def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, frame_weight=None,
+                         triple_weight=None, window=None):
+        A, g, E, F, cost, count = SphereTrajectoryPoseFitter.normal_equations(self, observed, params, view, keypoints, confidence,
+                                                                              frame_weight, triple_weight)
+        if window is not None and window['prior'] is not None:
+            A, g, E, cost = ops.pose_window_prior_normal(params.detach().contiguous().float(), *window['prior'], self.seq_len,
+                                                         (A, g, cost), E)
+        return A, g, E, F, cost, count
+
+
 class SphereRadiiCalibrator(SphereCollisionPoseFitter):
     """The sphere RADII calibrated to the hand in the frames: every fitter above takes the 41 radii as a constant of the
     shipped model, and they are a fat proxy.  The batch's B = G group_size frames are G groups, the
