@@ -7,12 +7,12 @@
 //   chain     one workgroup of 256 threads per sequence; the frames are taken one after the other, forward and then back,
 //             so a sequence is a latency chain of 2 T frames.  Every output entry is ONE fixed-order fp64 chain, so its
 //             bits do not depend on the thread that owns it: the 676 entries of a block are dealt over the 256 threads.
-//   forward   lm_seq2.hip's factorisation at lambda = 0, the same operations per entry in the same order:
+//   forward   lm_band.h's factorisation at lambda = 0, the same operations per entry in the same order:
 //             D_t = M_t - W_{t-1} W_{t-1}^T - V_{t-2} V_{t-2}^T, M_t = A_t + diag(mu), per entry the W product subtracted
 //             first, then the V product, each m ascending; L_t L_t^T = D_t by lm_solve.h's column recurrence, taken
 //             RIGHT-LOOKING (column m is subtracted from every later column as soon as it is finished: per entry the same
 //             subtractions, m ascending); W_t = (E_t^T - V_{t-1} W_{t-1}^T) L_t^-T, V_t = F_t^T L_t^-T and N_t = L_t^-1
-//             by the row recurrence of lm_seq2.hip's s2_rows, the three side by side and right-looking likewise.
+//             by the row recurrence of lm_solve.h's lm_columns, the three side by side and right-looking likewise.
 //             N_t, W_t and V_t go to the workspace.
 //   back      backward over t, with P_t = W_t N_t and Q_t = V_t N_t (chains from 0, k ascending):
 //             Z_{t+1,t} = (-(Z_{t+1,t+1} P_t)) - Z_{t+2,t+1}^T Q_t;  Z_{t+2,t} = (-(Z_{t+2,t+1} P_t)) - Z_{t+2,t+2} Q_t;
@@ -22,7 +22,7 @@
 //   Everything fp64, every sum in index order, the W (P) term before the V (Q) term, nothing contracted, no atomics.
 //   LDS: nine blocks [26 x 26] -- forward D/L, N, the two W and three V; backward N, P, Q, the three kept Z blocks and the
 //   three being formed, W_t and V_t staged where Z_{t+1,t} and Z_{t+2,t} are formed afterwards -- 48 672 bytes.  W and V are
-//   held TRANSPOSED (W[k * 26 + i] = W_t[i][k]) as in lm_seq2.hip, so that a wave reads consecutive doubles.
+//   held TRANSPOSED (W[k * 26 + i] = W_t[i][k]) as in lm_band.h, so that a wave reads consecutive doubles.
 #include "lm_solve.h"
 
 namespace shr {
@@ -36,7 +36,7 @@ struct CvLds {
   double blk[9][kCvNN];
 };
 
-// X (and Y, unless it is null) := the solution of L X = X row by row, in place: s2_rows' recurrence for every column at
+// X (and Y, unless it is null) := the solution of L X = X row by row, in place: lm_columns' recurrence for every column at
 // once, right-looking.  X[k][:] = (X[k][:] - sum_{m<k} L[k][m] X[m][:]) / L[k][k], m ascending.  With Z the same for Z.
 __device__ __forceinline__ void cv_rows(const double *L, double *X, double *Y, double *Z, int tid) {
   const int which = tid >> 6, col = tid & 63;              // wave 0: X, wave 1: Y, wave 2: Z

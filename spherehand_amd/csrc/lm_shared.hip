@@ -25,7 +25,7 @@
 //   to shr_pose_lm_step, whose state is the leading part of this one.
 //   LDS: frame 24 344 bytes (A, L [26 x 26], x [26], the pivot, Y [26 x 64]), schur 47 328 bytes (S [64 x 65], Y [26 x 64],
 //   z [26], x [64], the pivot and the verdict), back 6 128 bytes.
-#include "lm_solve.h"
+#include "lm_state.h"
 
 extern "C" int shr_pose_lm_step(void *state, const double *A, const double *g, const double *cost_data, const float *trial,
                                 const float *prior, const float *stiffness, int solve, int B, float *trial_out, float *params,
@@ -36,16 +36,15 @@ namespace shr {
 constexpr int kShMaxK = 64;          // shared parameters at most: one wave owns the rows of S
 constexpr int kShLd = kShMaxK + 1;   // the row stride of S in LDS
 constexpr int kShThreads = 256;      // the schur pass
-// A frame's state is shr_pose_lm_step's, in doubles: A [26 x 26], g [26], the pose, params0, and -- read in the FIRST frame
-// of a group only -- the group's total cost, lambda, `fresh`, `moved`, the accept and reject counters.
-constexpr int kShA = 0, kShG = kLmN * kLmN, kShP = kShG + kLmN, kShP0 = kShP + kLmN, kShCost = kShP0 + kLmN, kShLambda = kShCost + 1,
-              kShFresh = kShCost + 2, kShMoved = kShCost + 3, kShAccepts = kShCost + 4, kShRejects = kShCost + 5, kShState = 760;
-static_assert(kShRejects < kShState, "the state's fields");
+// A frame's state is shr_pose_lm_step's (lm_state.h's frame without E), the group's fields in the group's FIRST frame: with
+// K == 0 and N == 1 the step is handed to that entry, which must find every field where this unit's begin put it.
+using St = LmCropState;
 // BEHIND the B frames: per group sigma [K], shape0 [K], gs [K], R [K x K]; behind the groups, per frame C [26 x K].
-__host__ __device__ inline size_t sh_group_doubles(int K) { return (size_t)K * (3 + K); }
-__host__ __device__ inline size_t sh_state_doubles(int B, int G, int K) {
-  return (size_t)B * kShState + (size_t)G * sh_group_doubles(K) + (size_t)B * kLmN * K;
+__host__ __device__ constexpr size_t sh_group_doubles(int K) { return (size_t)K * (3 + K); }
+__host__ __device__ constexpr size_t sh_state_doubles(int B, int G, int K) {
+  return (size_t)B * St::kSize + (size_t)G * sh_group_doubles(K) + (size_t)B * kLmN * K;
 }
+static_assert(sh_state_doubles(5, 5, 0) == 5 * LmCropState::kSize, "without a shared block the state is shr_pose_lm_step's");
 // The workspace, in doubles: per frame L [26 x 26], z [26], the factor's verdict (704 with the padding), Y [26 x K]; behind
 // the frames, per group: accept, lambda, the group's verdict (8 with the padding), d sigma [K].
 constexpr int kShWsZ = kLmN * kLmN, kShWsOk = kShWsZ + kLmN, kShWsY = 704, kShWsGroup = 8;
@@ -59,26 +58,14 @@ __global__ void __launch_bounds__(64)
 pose_lm_shared_begin_kernel(const float *__restrict__ params0, const float *__restrict__ shape0, float lambda0, int B, int N, int K,
                             double *__restrict__ state, float *__restrict__ trial, float *__restrict__ trial_shape) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  double *st = state + (size_t)b * kShState;
-  for (int e = lane; e < kShP; e += 64) st[e] = 0.0;
-  if (lane < kLmN) {
-    const float p = params0[(size_t)b * kLmN + lane];
-    st[kShP + lane] = st[kShP0 + lane] = (double)p;
-    trial[(size_t)b * kLmN + lane] = p;
-  }
-  if (lane == 0) {
-    st[kShCost] = __builtin_inf();
-    st[kShLambda] = (double)lambda0;
-    st[kShFresh] = 1.0;
-    st[kShMoved] = st[kShAccepts] = st[kShRejects] = 0.0;
-  }
+  lm_begin_frame<St>(params0, lambda0, state + (size_t)b * St::kSize, trial, (size_t)b, lane);
   if (K == 0) return;
   const int G = B / N;
-  double *sc = state + (size_t)B * kShState + (size_t)G * sh_group_doubles(K) + (size_t)b * kLmN * K;
+  double *sc = state + (size_t)B * St::kSize + (size_t)G * sh_group_doubles(K) + (size_t)b * kLmN * K;
   for (int e = lane; e < kLmN * K; e += 64) sc[e] = 0.0;
   if (b % N != 0) return;
   const int q = b / N;
-  double *sg = state + (size_t)B * kShState + (size_t)q * sh_group_doubles(K);
+  double *sg = state + (size_t)B * St::kSize + (size_t)q * sh_group_doubles(K);
   if (lane < K) {
     const float v = shape0[(size_t)q * K + lane];
     sg[lane] = sg[K + lane] = (double)v;
@@ -102,31 +89,12 @@ pose_lm_shared_decide_kernel(double *__restrict__ state, const double *__restric
   __shared__ ShDecideLds s;
   const int q = blockIdx.x, lane = threadIdx.x;
   const size_t first = (size_t)q * N;
-  double *sq = state + first * kShState;                   // the group's fields live in its first frame
-  double *sg = state + (size_t)B * kShState + (size_t)q * sh_group_doubles(K);
+  double *sq = state + first * St::kSize;                   // the group's fields live in its first frame
+  double *sg = state + (size_t)B * St::kSize + (size_t)q * sh_group_doubles(K);
   double *wg = ws + (size_t)B * sh_ws_frame(K) + (size_t)q * (kShWsGroup + K);
-  const bool own = lane < kLmN;
-  const double mu = own && stiffness ? (double)stiffness[lane] : 0.0;
-  const double cur = sq[kShCost], lam0 = sq[kShLambda];
-  const bool fresh = sq[kShFresh] != 0.0, moved = sq[kShMoved] != 0.0;
-  const double accepts = sq[kShAccepts], rejects = sq[kShRejects];
-  // total: the frames' totals, ascending; a frame's total is shr_pose_lm_step's chain
-  double total = 0.0;
-#pragma unroll 1
-  for (int t = 0; t < N; t++) {
-    const size_t f = first + t;
-    if (own) {
-      const double pr = prior ? (double)prior[f * kLmN + lane] : state[f * kShState + kShP0 + lane];
-      const double d = (double)trial[f * kLmN + lane] - pr;
-      s.x[lane] = mu * (d * d);
-    }
-    __syncthreads();
-    double mine = cost_data[f];
-#pragma unroll 1
-    for (int i = 0; i < kLmN; i++) mine += s.x[i];
-    total = t == 0 ? mine : total + mine;
-    __syncthreads();
-  }
+  const double mu = lane < kLmN && stiffness ? (double)stiffness[lane] : 0.0;
+  const LmBook bk = lm_book<St>(sq);
+  double total = lm_frames_total<St>(s, state, first, N, cost_data, trial, prior, mu, lane);
   const float ts = lane < K ? trial_shape[(size_t)q * K + lane] : 0.f;
   if (K > 0) {                                             // + nu_k (sigma_k - prior_k)^2, k ascending
     if (lane < K) {
@@ -138,8 +106,8 @@ pose_lm_shared_decide_kernel(double *__restrict__ state, const double *__restric
 #pragma unroll 1
     for (int k = 0; k < K; k++) total += s.x[k];
   }
-  const bool accept = total < cur && total > -__builtin_inf();        // (false for a NaN, and for +inf)
-  const double lam = fmin(fmax(lam0 * (accept ? (moved ? 0.3 : 1.0) : 10.0), 1e-9), 1e6);
+  const LmDecision dec = lm_decide(bk, total);
+  const bool accept = dec.accept;
   if (lane < K) {
     const double sa = accept ? (double)ts : sg[lane];
     if (accept) {
@@ -151,16 +119,9 @@ pose_lm_shared_decide_kernel(double *__restrict__ state, const double *__restric
   if (accept)
     for (int e = lane; e < K * K; e += 64) sg[3 * K + e] = R[(size_t)q * K * K + e];
   if (lane == 0) {
-    sq[kShCost] = accept ? total : cur;
-    sq[kShLambda] = lam;
-    sq[kShFresh] = 0.0;
-    sq[kShMoved] = (moved || accept) ? 1.0 : 0.0;
-    sq[kShAccepts] = accepts + (accept ? 1.0 : 0.0);
-    sq[kShRejects] = rejects + (accept ? 0.0 : 1.0);
-    cost[q] = (float)(accept ? total : cur);
-    if (fresh) cost0[q] = (float)total;
+    lm_record<St>(sq, bk, total, dec, cost + q, cost0 + q);
     wg[0] = accept ? 1.0 : 0.0;                            // what the frames' waves need of the decision
-    wg[1] = lam;
+    wg[1] = dec.lam;
     wg[2] = 1.0;
   }
 }
@@ -176,28 +137,28 @@ pose_lm_shared_frame_kernel(double *__restrict__ state, const double *__restrict
                             double *__restrict__ ws) {
   __shared__ ShFrameLds s;
   const int b = blockIdx.x, lane = threadIdx.x, G = B / N, q = b / N;
-  double *st = state + (size_t)b * kShState;
-  double *sc = state + (size_t)B * kShState + (size_t)G * sh_group_doubles(K) + (size_t)b * kLmN * K;
+  double *st = state + (size_t)b * St::kSize;
+  double *sc = state + (size_t)B * St::kSize + (size_t)G * sh_group_doubles(K) + (size_t)b * kLmN * K;
   const double *wg = ws + (size_t)B * sh_ws_frame(K) + (size_t)q * (kShWsGroup + K);
   double *wf = ws + (size_t)b * sh_ws_frame(K);
   const bool accept = wg[0] != 0.0;
   const double lam = wg[1];
   const bool own = lane < kLmN;
   const float tq = own ? trial[(size_t)b * kLmN + lane] : 0.f;
-  const double pr = !own ? 0.0 : prior ? (double)prior[(size_t)b * kLmN + lane] : st[kShP0 + lane];
+  const double pr = !own ? 0.0 : prior ? (double)prior[(size_t)b * kLmN + lane] : st[St::kP0 + lane];
   const double mu = own && stiffness ? (double)stiffness[lane] : 0.0;
   // the accepted pose and its equations: the trial's where the group is accepted, the state's otherwise
-  const double *As = accept ? A + (size_t)b * kLmN * kLmN : st + kShA;
+  const double *As = accept ? A + (size_t)b * kLmN * kLmN : st + St::kA;
   for (int e = lane; e < kLmN * kLmN; e += 64) s.A[e] = As[e];
   const double *Cs = accept ? C + (size_t)b * kLmN * K : sc;
   for (int e = lane; e < kLmN * K; e += 64) s.Y[e] = Cs[e];
-  const double pa = !own ? 0.0 : accept ? (double)tq : st[kShP + lane];
-  const double ga = !own ? 0.0 : accept ? g[(size_t)b * kLmN + lane] : st[kShG + lane];
+  const double pa = !own ? 0.0 : accept ? (double)tq : st[St::kP + lane];
+  const double ga = !own ? 0.0 : accept ? g[(size_t)b * kLmN + lane] : st[St::kG + lane];
   __syncthreads();
   if (accept) {
-    for (int e = lane; e < kLmN * kLmN; e += 64) st[kShA + e] = s.A[e];
+    for (int e = lane; e < kLmN * kLmN; e += 64) st[St::kA + e] = s.A[e];
     for (int e = lane; e < kLmN * K; e += 64) sc[e] = s.Y[e];
-    if (own) { st[kShG + lane] = ga; st[kShP + lane] = pa; }
+    if (own) { st[St::kG + lane] = ga; st[St::kP + lane] = pa; }
   }
   if (own) params[(size_t)b * kLmN + lane] = (float)pa;
   if (!solve) return;
@@ -210,23 +171,8 @@ pose_lm_shared_frame_kernel(double *__restrict__ state, const double *__restrict
     if (lane == 0) wf[kShWsOk] = 0.0;
     return;
   }
-  const double rhs = -(ga + mu * (pa - pr));
-  double acc = 0.0;
-#pragma unroll 1
-  for (int k = 0; k < kLmN; k++) {                                     // lm_solve's forward substitution
-    if (lane == k) s.x[k] = (rhs - acc) / s.L[k * kLmN + k];
-    __syncthreads();
-    if (lane > k && lane < kLmN) acc += s.L[lane * kLmN + k] * s.x[k];
-  }
-  if (lane < K) {                                                      // column `lane` of Y: L y = C[:, lane], in place
-#pragma unroll 1
-    for (int m = 0; m < kLmN; m++) {
-      double v = s.Y[m * K + lane];
-#pragma unroll 2
-      for (int j = 0; j < m; j++) v -= s.L[m * kLmN + j] * s.Y[j * K + lane];
-      s.Y[m * K + lane] = v / s.L[m * kLmN + m];
-    }
-  }
+  lm_forward(s, -(ga + mu * (pa - pr)), lane);
+  if (lane < K) lm_columns(s, s.Y, K, lane);                           // column `lane` of Y: L y = C[:, lane], in place
   __syncthreads();
   for (int e = lane; e < kLmN * kLmN; e += 64) wf[e] = s.L[e];
   for (int e = lane; e < kLmN * K; e += 64) wf[kShWsY + e] = s.Y[e];
@@ -246,7 +192,7 @@ pose_lm_shared_schur_kernel(const double *__restrict__ state, const float *__res
   __shared__ ShSchurLds s;
   const int q = blockIdx.x, tid = threadIdx.x;
   const size_t first = (size_t)q * N;
-  const double *sg = state + (size_t)B * kShState + (size_t)q * sh_group_doubles(K);
+  const double *sg = state + (size_t)B * St::kSize + (size_t)q * sh_group_doubles(K);
   double *wg = ws + (size_t)B * sh_ws_frame(K) + (size_t)q * (kShWsGroup + K);
   const double lam = wg[1];
   const bool mine = tid < K;
@@ -348,11 +294,11 @@ pose_lm_shared_back_kernel(const double *__restrict__ state, int B, int N, int K
                            const double *__restrict__ ws) {
   __shared__ ShBackLds s;
   const int b = blockIdx.x, lane = threadIdx.x, q = b / N;
-  const double *st = state + (size_t)b * kShState;
+  const double *st = state + (size_t)b * St::kSize;
   const double *wg = ws + (size_t)B * sh_ws_frame(K) + (size_t)q * (kShWsGroup + K);
   const double *wf = ws + (size_t)b * sh_ws_frame(K);
   const bool own = lane < kLmN;
-  const double pa = own ? st[kShP + lane] : 0.0;
+  const double pa = own ? st[St::kP + lane] : 0.0;
   // with a shared block the verdict is the group's (which holds every frame's); without one the frame's own
   const bool ok = K > 0 ? wg[2] != 0.0 : wf[kShWsOk] != 0.0;
   if (!ok) {
@@ -369,13 +315,7 @@ pose_lm_shared_back_kernel(const double *__restrict__ state, int B, int N, int K
     for (int k = 0; k < K; k++) c += wf[kShWsY + lane * K + k] * s.v[k];
     z = z - c;
   }
-  double acc = 0.0;
-#pragma unroll 1
-  for (int k = kLmN - 1; k >= 0; k--) {                    // lm_solve's backward substitution
-    if (lane == k) s.x[k] = (z - acc) / s.L[k * kLmN + k];
-    __syncthreads();
-    if (lane < k) acc += s.L[k * kLmN + lane] * s.x[k];
-  }
+  lm_backward(s, z, lane);
   __syncthreads();
   if (own) trial_out[(size_t)b * kLmN + lane] = (float)(pa + s.x[lane]);
 }

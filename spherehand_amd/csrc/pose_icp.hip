@@ -19,6 +19,7 @@
 //   lm       one wave per crop: the accept test, lambda, and lm_solve.h's damped solve -- pose_ik.hip's iteration, split
 //            where the cost evaluation needs other kernels.
 #include "icp_tile.h"
+#include "lm_state.h"
 
 namespace shr {
 
@@ -39,28 +40,12 @@ pose_icp_reduce_kernel(const double *__restrict__ part, int tiles, double *__res
   icp_reduce_body(part, tiles, (int)blockIdx.x, (int)threadIdx.x, A, g, cost, count);
 }
 
-// A crop's state, in doubles: the accepted pose's A [26 x 26] and g [26], the pose itself, params0, its total cost, lambda,
-// `fresh` (no step since begin), `moved` (a trial has been accepted since begin), the accept and reject counters.
-constexpr int kLmA = 0, kLmG = kLmN * kLmN, kLmP = kLmG + kLmN, kLmP0 = kLmP + kLmN, kLmCost = kLmP0 + kLmN, kLmLambda = kLmCost + 1,
-              kLmFresh = kLmCost + 2, kLmMoved = kLmCost + 3, kLmAccepts = kLmCost + 4, kLmRejects = kLmCost + 5, kLmState = 760;
-static_assert(kLmRejects < kLmState, "the state's fields");
+using St = LmCropState;              // a crop's state: lm_state.h's frame without E, the crop its own unit of decision
 
 __global__ void __launch_bounds__(64)
 pose_lm_begin_kernel(const float *__restrict__ params0, float lambda0, double *__restrict__ state, float *__restrict__ trial) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  double *st = state + (size_t)b * kLmState;
-  for (int e = lane; e < kLmP; e += 64) st[e] = 0.0;
-  if (lane < kLmN) {
-    const float p = params0[(size_t)b * kLmN + lane];
-    st[kLmP + lane] = st[kLmP0 + lane] = (double)p;
-    trial[(size_t)b * kLmN + lane] = p;
-  }
-  if (lane == 0) {
-    st[kLmCost] = __builtin_inf();
-    st[kLmLambda] = (double)lambda0;
-    st[kLmFresh] = 1.0;
-    st[kLmMoved] = st[kLmAccepts] = st[kLmRejects] = 0.0;
-  }
+  const int b = blockIdx.x;
+  lm_begin_frame<St>(params0, lambda0, state + (size_t)b * St::kSize, trial, (size_t)b, (int)threadIdx.x);
 }
 
 struct LmLds {
@@ -74,44 +59,27 @@ pose_lm_step_kernel(double *__restrict__ state, const double *__restrict__ A, co
                     float *__restrict__ cost, float *__restrict__ cost0) {
   __shared__ LmLds s;
   const int b = blockIdx.x, lane = threadIdx.x;
-  double *st = state + (size_t)b * kLmState;
+  double *st = state + (size_t)b * St::kSize;
   const bool own = lane < kLmN;
-  const float tq = own ? trial[(size_t)b * kLmN + lane] : 0.f;
-  const double pr = !own ? 0.0 : prior ? (double)prior[(size_t)b * kLmN + lane] : st[kLmP0 + lane];
   const double mu = own && stiffness ? (double)stiffness[lane] : 0.0;
-  if (own) {
-    const double d = (double)tq - pr;
-    s.x[lane] = mu * (d * d);
-  }
-  const double cur = st[kLmCost], lam0 = st[kLmLambda];
-  const bool fresh = st[kLmFresh] != 0.0, moved = st[kLmMoved] != 0.0;
-  const double accepts = st[kLmAccepts], rejects = st[kLmRejects];
-  __syncthreads();
-  double total = cost_data[b];
-#pragma unroll 1
-  for (int i = 0; i < kLmN; i++) total += s.x[i];
-  const bool accept = total < cur && total > -__builtin_inf();        // (false for a NaN, and for +inf)
-  const double lam = fmin(fmax(lam0 * (accept ? (moved ? 0.3 : 1.0) : 10.0), 1e-9), 1e6);
+  const LmBook bk = lm_book<St>(st);
+  const double total = lm_frames_total<St>(s, state, (size_t)b, 1, cost_data, trial, prior, mu, lane);
+  const float tq = own ? trial[(size_t)b * kLmN + lane] : 0.f;
+  const double pr = !own ? 0.0 : prior ? (double)prior[(size_t)b * kLmN + lane] : st[St::kP0 + lane];
+  const LmDecision dec = lm_decide(bk, total);
+  const bool accept = dec.accept;
+  const double lam = dec.lam;
   // the accepted pose and its equations: the trial's where it is accepted, the state's otherwise -- all read before the state is written
-  const double *As = accept ? A + (size_t)b * kLmN * kLmN : st + kLmA;
+  const double *As = accept ? A + (size_t)b * kLmN * kLmN : st + St::kA;
   for (int e = lane; e < kLmN * kLmN; e += 64) s.A[e] = As[e];
-  const double pa = !own ? 0.0 : accept ? (double)tq : st[kLmP + lane];
-  const double ga = !own ? 0.0 : accept ? g[(size_t)b * kLmN + lane] : st[kLmG + lane];
+  const double pa = !own ? 0.0 : accept ? (double)tq : st[St::kP + lane];
+  const double ga = !own ? 0.0 : accept ? g[(size_t)b * kLmN + lane] : st[St::kG + lane];
   __syncthreads();
   if (accept) {
-    for (int e = lane; e < kLmN * kLmN; e += 64) st[kLmA + e] = s.A[e];
-    if (own) { st[kLmG + lane] = ga; st[kLmP + lane] = pa; }
+    for (int e = lane; e < kLmN * kLmN; e += 64) st[St::kA + e] = s.A[e];
+    if (own) { st[St::kG + lane] = ga; st[St::kP + lane] = pa; }
   }
-  if (lane == 0) {
-    st[kLmCost] = accept ? total : cur;
-    st[kLmLambda] = lam;
-    st[kLmFresh] = 0.0;
-    st[kLmMoved] = (moved || accept) ? 1.0 : 0.0;
-    st[kLmAccepts] = accepts + (accept ? 1.0 : 0.0);
-    st[kLmRejects] = rejects + (accept ? 0.0 : 1.0);
-    cost[b] = (float)(accept ? total : cur);
-    if (fresh) cost0[b] = (float)total;
-  }
+  if (lane == 0) lm_record<St>(st, bk, total, dec, cost + b, cost0 + b);
   if (own) params[(size_t)b * kLmN + lane] = (float)pa;
   if (!solve) return;
   __syncthreads();
@@ -163,18 +131,12 @@ extern "C" int shr_pose_icp_normal(const float *observed, const float *vertices,
 
 extern "C" long long shr_pose_lm_state_bytes(int B) {
   if (B < 0) return -1;
-  return (long long)B * kLmState * 8;
-}
-
-static int lm_check(const void *state, int B) {
-  if (!state || B < 0 || (((uintptr_t)state) & 7u) != 0) return SHR_EINVAL;
-  if (B > (1 << 24)) return SHR_ETOOLARGE;
-  return SHR_OK;
+  return (long long)B * St::kSize * 8;
 }
 
 extern "C" int shr_pose_lm_begin(const float *params0, int B, float lambda0, void *state, float *trial, void *stream) {
   if (B == 0) return SHR_OK;
-  if (int rc = lm_check(state, B)) return rc;
+  if (int rc = lm_check(state, B, 1)) return rc;
   if (!params0 || !trial || !(lambda0 > 0.0f) || (((uintptr_t)params0 | (uintptr_t)trial) & 3u) != 0) return SHR_EINVAL;
   hipLaunchKernelGGL(pose_lm_begin_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, params0, lambda0,
                      reinterpret_cast<double *>(state), trial);
@@ -185,7 +147,7 @@ extern "C" int shr_pose_lm_step(void *state, const double *A, const double *g, c
                                 const float *prior, const float *stiffness, int solve, int B, float *trial_out, float *params,
                                 float *cost, float *cost0, void *stream) {
   if (B == 0) return SHR_OK;
-  if (int rc = lm_check(state, B)) return rc;
+  if (int rc = lm_check(state, B, 1)) return rc;
   if (!A || !g || !cost_data || !trial || !params || !cost || !cost0 || (solve && !trial_out)) return SHR_EINVAL;
   if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost_data) & 7u) != 0) return SHR_EINVAL;
   if ((((uintptr_t)trial | (uintptr_t)prior | (uintptr_t)stiffness | (uintptr_t)trial_out | (uintptr_t)params | (uintptr_t)cost |

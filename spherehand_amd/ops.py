@@ -2015,6 +2015,18 @@ def pose_icp_normal(observed, vertices, faces, dist, face, params, offset, offse
     return A, g, cost, count
 
 
+def _lm_prior_args(prior, stiffness, B):
+    """The stiffness term's arguments as every Levenberg-Marquardt step takes them: prior [B,26] and stiffness [26], or None."""
+    if prior is not None:
+        _check_input(prior, "prior")
+        if tuple(prior.shape) != (B, 26):
+            raise RuntimeError("prior must be [B,26]")
+    if stiffness is not None:
+        _check_input(stiffness, "stiffness")
+        if tuple(stiffness.shape) != (26,):
+            raise RuntimeError("stiffness must be [26]")
+
+
 def pose_lm_begin(params0, lambda0=1e-3):
     """Start a Levenberg-Marquardt loop on the device (shr_pose_lm_begin): params0 [B,26] -> (state, trial [B,26]): the
     opaque per-crop state pose_lm_step takes and the first pose to evaluate, params0."""
@@ -2049,14 +2061,7 @@ def pose_lm_step(state, A, g, cost_data, trial, prior=None, stiffness=None, solv
     lib = _lib.lib()
     if state.numel() * 8 < lib.shr_pose_lm_state_bytes(B):
         raise RuntimeError("state is pose_lm_begin's, for the same B")
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     with _on(trial.device):
         if out is None:
             new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
@@ -2091,14 +2096,7 @@ def pose_icp(observed, params0, faces, offset, offset_inv, skin_vertex_start, sk
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
     state, trial = pose_lm_begin(params0, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
@@ -2218,14 +2216,7 @@ def pose_icp_views(observed, view, params0, faces, offset, offset_inv, skin_vert
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
     state, trial = pose_lm_begin(params0, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
@@ -2322,14 +2313,7 @@ def sphere_icp(observed, view, params0, offset, offset_inv, bone, wv, radii, rig
         raise RuntimeError("iters must be >= 0")
     dev = observed.device
     state, trial = pose_lm_begin(params0, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
@@ -2424,14 +2408,7 @@ def sphere_icp_render(observed, view, params0, offset, offset_inv, bone, wv, rad
         raise RuntimeError("iters must be >= 0")
     dev = observed.device
     state, trial = pose_lm_begin(params0, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
@@ -2630,14 +2607,7 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
     state, trial = pose_lm_begin(params0, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
@@ -2736,8 +2706,8 @@ def sphere_temporal_normal(params, offset, offset_inv, bone, wv, seq_len, right_
     return A, g, E, cost, count
 
 
-def pose_lm_seq_begin(params0, seq_len, lambda0=1e-3):
-    """pose_lm_begin for sequences (shr_pose_lm_seq_begin): params0 [B,26], B = S seq_len -> (state, trial [B,26])."""
+def _lm_band_begin(entry, params0, seq_len, lambda0):
+    """pose_lm_seq_begin / pose_lm_seq2_begin: `entry` names the C entry, whose state size is shr_<entry>_state_bytes."""
     _check_input(params0, "start parameters")
     if params0.dim() != 2 or params0.shape[1] != 26:
         raise RuntimeError("start parameters must be [B,26]")
@@ -2747,11 +2717,54 @@ def pose_lm_seq_begin(params0, seq_len, lambda0=1e-3):
     T = _sphere_temporal_args(B, params0.device, seq_len, 0.0, 0.0, None)[0]
     lib = _lib.lib()
     with _on(params0.device):
-        state = torch.empty((max(1, lib.shr_pose_lm_seq_state_bytes(B) // 8),), dtype=torch.float64, device=params0.device)
+        state = torch.empty((max(1, getattr(lib, "shr_%s_state_bytes" % entry)(B) // 8),), dtype=torch.float64,
+                            device=params0.device)
         trial = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
-        _lib.check(lib.shr_pose_lm_seq_begin(_ptr(params0), B, T, float(lambda0), _ptr(state), _ptr(trial), _stream()),
-                   "shr_pose_lm_seq_begin")
+        _lib.check(getattr(lib, "shr_%s_begin" % entry)(_ptr(params0), B, T, float(lambda0), _ptr(state), _ptr(trial), _stream()),
+                   "shr_%s_begin" % entry)
     return state, trial
+
+
+def _lm_band_step(entry, state, A, g, E, F, cost_data, trial, seq_len, prior, stiffness, solve, out, workspace):
+    """pose_lm_seq_step / pose_lm_seq2_step: `entry` names the C entry; F = () for the entry that takes none, else a 1-tuple."""
+    _check_input(trial, "trial")
+    B = trial.shape[0]
+    if trial.dim() != 2 or trial.shape[1] != 26:
+        raise RuntimeError("trial must be [B,26]")
+    T = _sphere_temporal_args(B, trial.device, seq_len, 0.0, 0.0, None)[0]
+    if E is None and T > 1:
+        raise RuntimeError("E is needed with seq_len > 1")
+    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26))) + \
+            tuple((f, "F", (B, 26, 26)) for f in F) + ((cost_data, "cost_data", (B,)),):
+        if t is None:
+            continue
+        _check_input(t, name, torch.float64)
+        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
+            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
+    lib = _lib.lib()
+    if state.numel() * 8 < getattr(lib, "shr_%s_state_bytes" % entry)(B):
+        raise RuntimeError("state is %s_begin's, for the same B" % entry)
+    _lm_prior_args(prior, stiffness, B)
+    S = B // T
+    with _on(trial.device):
+        if out is None:
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
+            out = (new(B, 26) if solve else None, new(B, 26), new(S), new(S))
+        if workspace is None and solve:
+            workspace = torch.empty((max(1, getattr(lib, "shr_%s_workspace_bytes" % entry)(B) // 8),), dtype=torch.float64,
+                                    device=trial.device)
+        trial_out, params, cost, cost0 = out
+        _lib.check(getattr(lib, "shr_%s_step" % entry)(_ptr(state), _ptr(A), _ptr(g), _ptr(E), *(_ptr(f) for f in F),
+                                                       _ptr(cost_data), _ptr(trial), _ptr(prior), _ptr(stiffness),
+                                                       int(bool(solve)), B, T, _ptr(trial_out) if solve else None, _ptr(params),
+                                                       _ptr(cost), _ptr(cost0), _ptr(workspace) if solve else None, _stream()),
+                   "shr_%s_step" % entry)
+    return (trial_out if solve else None), params, cost, cost0
+
+
+def pose_lm_seq_begin(params0, seq_len, lambda0=1e-3):
+    """pose_lm_begin for sequences (shr_pose_lm_seq_begin): params0 [B,26], B = S seq_len -> (state, trial [B,26])."""
+    return _lm_band_begin("pose_lm_seq", params0, seq_len, lambda0)
 
 
 def pose_lm_seq_step(state, A, g, E, cost_data, trial, seq_len, prior=None, stiffness=None, solve=True, out=None, workspace=None):
@@ -2760,45 +2773,7 @@ def pose_lm_seq_step(state, A, g, E, cost_data, trial, seq_len, prior=None, stif
     cost0 [S]), S = B / seq_len: one decision, one lambda and one cost per sequence, the step from the block-tridiagonal
     solve.  prior, stiffness, out: pose_lm_step's; workspace: shr_pose_lm_seq_workspace_bytes(B) bytes to use instead of a
     new buffer."""
-    _check_input(trial, "trial")
-    B = trial.shape[0]
-    if trial.dim() != 2 or trial.shape[1] != 26:
-        raise RuntimeError("trial must be [B,26]")
-    T = _sphere_temporal_args(B, trial.device, seq_len, 0.0, 0.0, None)[0]
-    if E is None and T > 1:
-        raise RuntimeError("E is needed with seq_len > 1")
-    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26)),
-                           (cost_data, "cost_data", (B,))):
-        if t is None:
-            continue
-        _check_input(t, name, torch.float64)
-        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
-            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
-    lib = _lib.lib()
-    if state.numel() * 8 < lib.shr_pose_lm_seq_state_bytes(B):
-        raise RuntimeError("state is pose_lm_seq_begin's, for the same B")
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
-    S = B // T
-    with _on(trial.device):
-        if out is None:
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
-            out = (new(B, 26) if solve else None, new(B, 26), new(S), new(S))
-        if workspace is None and solve:
-            workspace = torch.empty((max(1, lib.shr_pose_lm_seq_workspace_bytes(B) // 8),), dtype=torch.float64,
-                                    device=trial.device)
-        trial_out, params, cost, cost0 = out
-        _lib.check(lib.shr_pose_lm_seq_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(trial), _ptr(prior),
-                                            _ptr(stiffness), int(bool(solve)), B, T, _ptr(trial_out) if solve else None,
-                                            _ptr(params), _ptr(cost), _ptr(cost0), _ptr(workspace) if solve else None,
-                                            _stream()), "shr_pose_lm_seq_step")
-    return (trial_out if solve else None), params, cost, cost0
+    return _lm_band_step("pose_lm_seq", state, A, g, E, (), cost_data, trial, seq_len, prior, stiffness, solve, out, workspace)
 
 
 def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand=True,
@@ -2881,20 +2856,7 @@ def sphere_accel_normal(params, offset, offset_inv, bone, wv, seq_len, right_han
 def pose_lm_seq2_begin(params0, seq_len, lambda0=1e-3):
     """pose_lm_seq_begin for the block-pentadiagonal step (shr_pose_lm_seq2_begin): params0 [B,26], B = S seq_len ->
     (state, trial [B,26])."""
-    _check_input(params0, "start parameters")
-    if params0.dim() != 2 or params0.shape[1] != 26:
-        raise RuntimeError("start parameters must be [B,26]")
-    if not float(lambda0) > 0:
-        raise RuntimeError("lambda0 must be > 0")
-    B = params0.shape[0]
-    T = _sphere_temporal_args(B, params0.device, seq_len, 0.0, 0.0, None)[0]
-    lib = _lib.lib()
-    with _on(params0.device):
-        state = torch.empty((max(1, lib.shr_pose_lm_seq2_state_bytes(B) // 8),), dtype=torch.float64, device=params0.device)
-        trial = torch.empty((B, 26), dtype=torch.float32, device=params0.device)
-        _lib.check(lib.shr_pose_lm_seq2_begin(_ptr(params0), B, T, float(lambda0), _ptr(state), _ptr(trial), _stream()),
-                   "shr_pose_lm_seq2_begin")
-    return state, trial
+    return _lm_band_begin("pose_lm_seq2", params0, seq_len, lambda0)
 
 
 def pose_lm_seq2_step(state, A, g, E, F, cost_data, trial, seq_len, prior=None, stiffness=None, solve=True, out=None,
@@ -2903,45 +2865,7 @@ def pose_lm_seq2_step(state, A, g, E, F, cost_data, trial, seq_len, prior=None, 
     (shr_pose_lm_seq2_step): the step is from the block-PENTAdiagonal solve.  F None: no second band, and every output is
     pose_lm_seq_step's bit for bit.  state: pose_lm_seq2_begin's; workspace: shr_pose_lm_seq2_workspace_bytes(B) bytes to use
     instead of a new buffer."""
-    _check_input(trial, "trial")
-    B = trial.shape[0]
-    if trial.dim() != 2 or trial.shape[1] != 26:
-        raise RuntimeError("trial must be [B,26]")
-    T = _sphere_temporal_args(B, trial.device, seq_len, 0.0, 0.0, None)[0]
-    if E is None and T > 1:
-        raise RuntimeError("E is needed with seq_len > 1")
-    for t, name, shape in ((state, "state", None), (A, "A", (B, 26, 26)), (g, "g", (B, 26)), (E, "E", (B, 26, 26)),
-                           (F, "F", (B, 26, 26)), (cost_data, "cost_data", (B,))):
-        if t is None:
-            continue
-        _check_input(t, name, torch.float64)
-        if (shape is not None and tuple(t.shape) != shape) or t.device != trial.device:
-            raise RuntimeError("%s must be %s fp64 on trial's device" % (name, shape))
-    lib = _lib.lib()
-    if state.numel() * 8 < lib.shr_pose_lm_seq2_state_bytes(B):
-        raise RuntimeError("state is pose_lm_seq2_begin's, for the same B")
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
-    S = B // T
-    with _on(trial.device):
-        if out is None:
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=trial.device)   # noqa: E731
-            out = (new(B, 26) if solve else None, new(B, 26), new(S), new(S))
-        if workspace is None and solve:
-            workspace = torch.empty((max(1, lib.shr_pose_lm_seq2_workspace_bytes(B) // 8),), dtype=torch.float64,
-                                    device=trial.device)
-        trial_out, params, cost, cost0 = out
-        _lib.check(lib.shr_pose_lm_seq2_step(_ptr(state), _ptr(A), _ptr(g), _ptr(E), _ptr(F), _ptr(cost_data), _ptr(trial),
-                                             _ptr(prior), _ptr(stiffness), int(bool(solve)), B, T,
-                                             _ptr(trial_out) if solve else None, _ptr(params), _ptr(cost), _ptr(cost0),
-                                             _ptr(workspace) if solve else None, _stream()), "shr_pose_lm_seq2_step")
-    return (trial_out if solve else None), params, cost, cost0
+    return _lm_band_step("pose_lm_seq2", state, A, g, E, (F,), cost_data, trial, seq_len, prior, stiffness, solve, out, workspace)
 
 
 def pose_lm_covariance(A, E, F, seq_len, stiffness=None, jac=None, workspace=None):
@@ -3121,14 +3045,7 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
     state, trial = (pose_lm_seq2_begin if accel else pose_lm_seq_begin)(params0, T, lambda0)
-    if prior is not None:
-        _check_input(prior, "prior")
-        if tuple(prior.shape) != (B, 26):
-            raise RuntimeError("prior must be [B,26]")
-    if stiffness is not None:
-        _check_input(stiffness, "stiffness")
-        if tuple(stiffness.shape) != (26,):
-            raise RuntimeError("stiffness must be [26]")
+    _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
     right, fg_max = int(bool(right_hand)), float(fg_max)
     S = B // T

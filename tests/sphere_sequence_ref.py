@@ -166,7 +166,7 @@ def chain(centres32, jac32, T, temporal_weight=1.0, ts_max=INF, frame_weight=Non
 
 # ---- the solve ----------------------------------------------------------------------------------------------------------
 def _cholesky(M, lam, Wt):
-    """lm_seq.hip's sq_cholesky: column by column, the diagonal damped first, the previous factor's outer product subtracted
+    """lm_band.h's lm_band_cholesky without the second band: column by column, the diagonal damped first, the previous factor's outer product subtracted
     entry by entry (k ascending), then the columns' own.  (L, ok)."""
     n = M.shape[0]
     L = np.zeros((n, n))

@@ -187,7 +187,7 @@ def chain(centres32, jac32, T, accel_weight=1.0, acc_max=INF, triple_weight=None
 
 # ---- the solve ----------------------------------------------------------------------------------------------------------
 def _cholesky(M, lam, Wt, Vt):
-    """lm_seq2.hip's s2_cholesky: column by column, the diagonal damped first, W_{t-1}'s outer product subtracted entry by
+    """lm_band.h's lm_band_cholesky: column by column, the diagonal damped first, W_{t-1}'s outer product subtracted entry by
     entry (m ascending), then V_{t-2}'s, then the columns' own.  (L, ok)."""
     n = M.shape[0]
     L = np.zeros((n, n))

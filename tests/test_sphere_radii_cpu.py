@@ -113,7 +113,8 @@ def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
     """lm_shared.hip: five kernels, no scratch, no spills, no atomics.  begin uses no LDS; decide 512 bytes (the cost terms);
     frame A, L [26 x 26], x [26], the pivot and Y [26 x 64] in fp64: 24 344 bytes; schur S [64 x 65] (factored in place),
     a frame's Y [26 x 64], z [26], x [64], the pivot and the verdict: 47 328 bytes, three groups per CU by LDS; back L, x
-    and d sigma: 6 128 bytes.  DESIGN.md 4.4v tables the figures.  The unit includes lm_solve.h alone."""
+    and d sigma: 6 128 bytes.  DESIGN.md 4.4v tables the figures.  The unit includes lm_state.h alone (which includes
+    lm_solve.h alone)."""
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("### 4.4v"):design.index("### 4.5 ")]
     assert design.index("### 4.4u") < design.index("### 4.4v")
@@ -135,9 +136,11 @@ def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
     assert seen == set(want)
     assert want["frame"][0] == 24344 and want["schur"][0] == 47328 and want["back"][0] == 6128
     assert "24 344" in section and "47 328" in section and "6 128" in section
-    text = open(os.path.join(ROOT, "spherehand_amd", "csrc", "lm_shared.hip")).read()
-    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', text) == ["lm_solve.h"]
-    assert "atomic" not in text.lower()
+    inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
+                                  open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
+    assert inc("lm_shared.hip") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["common.h"]
+    for unit in ("lm_shared.hip", "lm_state.h", "lm_solve.h"):
+        assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
 
 
 def group_args(sys_, q, N, lam=1e-3):

@@ -159,7 +159,8 @@ def test_units_compile_for_gfx950_without_scratch(tmp_path):
     """sphere_temporal.hip: one kernel, one workgroup of 256 threads per FRAME, no scratch, no spills, no atomics; two 192 x 26
     fp32 Jacobians (2 x 19 968 bytes), both pairs' e [64 x 3] fp64, cost terms and flags in LDS: 44 544 bytes.  lm_seq.hip: the
     step is one wave per SEQUENCE with A, L, W [26 x 26] fp64, x, y and the pivot in LDS: 16 648 bytes; begin uses none.
-    DESIGN.md 4.4t tables the figures.  sphere_temporal.hip includes common.h alone, lm_seq.hip lm_solve.h alone."""
+    DESIGN.md 4.4t tables the figures.  sphere_temporal.hip includes common.h alone, lm_seq.hip lm_band.h alone (which
+    includes lm_state.h alone, which includes lm_solve.h alone)."""
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("### 4.4t"):design.index("### 4.5 ")]
     assert design.index("### 4.4s") < design.index("### 4.4t")
@@ -185,8 +186,9 @@ def test_units_compile_for_gfx950_without_scratch(tmp_path):
     assert "44 544" in section and "16 648" in section
     inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
                                   open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
-    assert inc("sphere_temporal.hip") == ["common.h"] and inc("lm_seq.hip") == ["lm_solve.h"]
-    for unit in ("sphere_temporal.hip", "lm_seq.hip"):
+    assert inc("sphere_temporal.hip") == ["common.h"] and inc("lm_seq.hip") == ["lm_band.h"]
+    assert inc("lm_band.h") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["common.h"]
+    for unit in ("sphere_temporal.hip", "lm_seq.hip", "lm_band.h", "lm_state.h", "lm_solve.h"):
         assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
 
 

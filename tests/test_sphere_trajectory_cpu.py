@@ -182,7 +182,8 @@ def test_units_compile_for_gfx950_without_scratch(tmp_path):
     fp32 Jacobians (3 x 19 968 bytes), the three triples' a [64 x 3] fp64, cost terms and flags in LDS: 66 816 bytes.
     lm_seq2.hip: the step is one wave per SEQUENCE with A, L, W, two V blocks and the cross product [26 x 26] fp64, x, y, the
     vector before it and the pivot in LDS: 33 080 bytes; begin uses none.  DESIGN.md 4.4u tables the figures.
-    sphere_accel.hip includes common.h alone, lm_seq2.hip lm_solve.h alone."""
+    sphere_accel.hip includes common.h alone, lm_seq2.hip lm_band.h alone (which includes lm_state.h alone, which includes
+    lm_solve.h alone)."""
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("### 4.4u"):design.index("### 4.5 ")]
     assert design.index("### 4.4t") < design.index("### 4.4u")
@@ -204,14 +205,15 @@ def test_units_compile_for_gfx950_without_scratch(tmp_path):
         if "step" in name:
             assert "pose_lm_seq2_step_kernel" in name and "pose_lm_seq2_step_kernel" in section
             assert k["group_segment_fixed_size"] == (6 * 26 * 26 + 3 * 26 + 1) * 8 == 33080
-            assert k["vgpr_count"] <= 64 and k["sgpr_count"] <= 90    # 62 and 86: lm_seq.hip's ceiling of 64 VGPRs holds
+            assert k["vgpr_count"] <= 64 and k["sgpr_count"] <= 90    # 60 and 86: the tridiagonal step's ceiling of 64 VGPRs holds
         else:
             assert "pose_lm_seq2_begin_kernel" in name and k["group_segment_fixed_size"] == 0 and k["vgpr_count"] <= 16
     assert "66 816" in section and "33 080" in section
     inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
                                   open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
-    assert inc("sphere_accel.hip") == ["common.h"] and inc("lm_seq2.hip") == ["lm_solve.h"]
-    for unit in ("sphere_accel.hip", "lm_seq2.hip"):
+    assert inc("sphere_accel.hip") == ["common.h"] and inc("lm_seq2.hip") == ["lm_band.h"]
+    assert inc("lm_band.h") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["common.h"]
+    for unit in ("sphere_accel.hip", "lm_seq2.hip", "lm_band.h", "lm_state.h", "lm_solve.h"):
         assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
 
 
