@@ -1359,6 +1359,73 @@ int shr_sphere_collision_normal(const float *centres   /* [B,J,4]: shr_pose_keyp
                                 double *A, double *g, double *cost, int32_t *count /* [B] */,
                                 double *penetration /* [B,K] or NULL */, void *workspace, void *stream);
 
+/* The pose-VAE prior of the sphere fit: which hand poses are plausible ----------------------------------------------------------
+ * None of the terms above knows which poses a hand takes: where the view hides a finger, nothing holds it.  The reference
+ * has such a term, the frozen PoseVae behind --prior (network/pose_vae.py:11-99), a 123-256-256-32-256-256-123 MLP with
+ * GroupNorm(16, 256) and ReLU trained on the model-frame keypoints / 100 (network/pose_vae.py:169), used first-order as
+ * 1e-2 prior_loss(xyz / 100) (network/create_network_and_criterion.py:164, 238-243).  The reference has no counterpart of the
+ * normal equations.  Here it is a Gauss-Newton term over the J = 41 sphere centres c (mm, MODEL frame, as the collision
+ * term reads them): with x = c / 100 (123 values, one IEEE fp32 division each),
+ *   r = 100 (x - recon(x))  [123, mm],   mu = mu(x)  [32],   z = mu: NO reparameterisation draw and NO logvar term,
+ *   energy = weight (sum_i r_i^2 + latent_weight sum_k mu_k^2).
+ * There is NO truncation of r: a saturating cut is what silences the other terms where this one is needed.  One evaluation
+ * of the fit is
+ *   shr_pose_keypoints_jacobian(trial) -> ... -> shr_sphere_collision_normal(accumulate = 1)
+ *     -> shr_pose_vae_normal(accumulate = 1) -> shr_pose_lm_step
+ * on one stream, without a host synchronisation: capturable in a hipGraph.
+ *   shr_pose_vae_normal   the normal equations of 1/2 energy with respect to the 26 pose parameters.  kp[B,J,4] and
+ *       jac[B,3J,26]: shr_pose_keypoints_jacobian's (component 3 of kp is not read).
+ *       Forward mode.  The exact Jacobian is J_r = (I - D) jac with D the network's 123 x 123 input Jacobian, which is NOT
+ *       formed: M0 = [x | jac] (123 x 27: the value column and the 26 pose tangents; the layers are linear in a tangent,
+ *       so the tangents carry jac itself and the 100 of x and the 100 of r cancel) passes through the network as one
+ *       matrix, all fp32:
+ *         linear     W M, the bias added to column 0 only.  Every element is ONE fmaf chain over k = 0 .. K - 1 ascending
+ *                    (v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate) that starts from the bias (column 0) or +0.  The
+ *                    exception is mu (256 -> 32): four chains P_v over k = 64 v .. 64 v + 63, P_0 starting from the bias,
+ *                    summed ((P_0 + P_1) + P_2) + P_3.
+ *         GroupNorm  16 groups of 16 channels, eps 1e-5, biased variance.  Value column: s = the 16 entries summed as
+ *                    (chain over channels 0-3, 8-11 of the group) + (chain over 4-7, 12-15), m = s / 16, d = h - m,
+ *                    q = sum d d in the same order, rs = 1 / sqrt(q / 16 + eps) (both correctly rounded), h^ = d rs,
+ *                    y = h^ gamma + beta.  Tangent column: y' = (gamma rs) ((h' - m1) - h^ m2), m1 = sum h' / 16,
+ *                    m2 = sum (h^ h') / 16, the sums in that order.
+ *         ReLU       y where y > 0, else +0; a tangent passes where the VALUE column's y > 0.
+ *       Rows, fp64 from the fp32 results: r_i = 100 ((double)x_i - (double)recon_i),
+ *       J_r[i][c] = (double)jac[i][c] - (double)recon'[i][c]; latent row k is (mu_k, mu'_k), exact conversions.
+ *       -> residual[B,123] fp64 (or NULL): r in mm.  latent[B,32] fp64 (or NULL): mu.  relu_mask[B,32] uint32 (or NULL):
+ *       the 1024 ReLU decisions of the value column, unit u = 256 l + channel with l = 0 .. 3 the GroupNorm layers in network
+ *       order (base 1, base 2, decoder 1, decoder 2): bit u & 31 of word u >> 5 is set iff y > 0.  The three are the term's
+ *       own, not weighted, and are written whatever the weight.
+ *       weight and accumulate.  With S = sum_i J_r[i] J_r[i]^T, G = sum_i r_i J_r[i], C = sum_i r_i r_i over rows 0 .. 122
+ *       and S_l, G_l, C_l the same over the 32 latent rows, lw = (double)latent_weight and w = (double)weight:
+ *         A_r = S + lw S_l, g_r = G + lw G_l, cost_r = C + lw C_l  (one product and one sum; lw == 0: A_r = S and so on)
+ *         accumulate == 0:  A = w A_r, g = w g_r, cost = w cost_r
+ *         accumulate == 1:  A += w A_r, g += w g_r, cost += w cost_r: one product and one sum per entry on top of what the
+ *                           buffers hold.  The LOWER triangle of A is read and the sum written to both triangles.
+ *         weight == 0:      A, g and cost are NOT touched, in either mode (they may be NULL); with no optional output
+ *                           either, nothing is launched.
+ *       Summation order (the contract): fixed-order fp64 chains from 0 in ascending row index, no atomics, nothing
+ *       contracted; entry (a, c), a >= c, is written to both triangles: bit-symmetric.  Bitwise reproducible; a frame's
+ *       result does not depend on the batch it is in or on B (one workgroup per frame); no host synchronisation.
+ *       blob: the network packed by the host, blob_floats = shr_pose_vae_blob_floats() = 215 200 fp32.  Per linear layer in
+ *       network order (base.0, base.3, mu, decoder.0, decoder.3, decoder.6; K = 124, 256, 256, 32, 256, 256 with the 123
+ *       inputs padded to even K by a zero row, OUT = 256, 256, 32, 256, 256, 128 with the 123 outputs padded by zero rows):
+ *       the weight, k-major, element ((q OUT + o) 2 + h) 2 + s = W[o][4 q + 2 s + h]; the bias [OUT]; and behind the four
+ *       layers followed by a GroupNorm its gamma [256] and beta [256].
+ *       workspace: none is needed; shr_pose_vae_normal_workspace_bytes(B, J) is 0 (-1 on a negative size).
+ *   Argument rules, checked before the B == 0 no-op: J == 41; B >= 0; weight and latent_weight finite and >= 0; accumulate
+ *   0 or 1; blob_floats == shr_pose_vae_blob_floats() (SHR_EINVAL otherwise); B above 65535: SHR_ETOOLARGE.  B == 0 is a
+ *   no-op.  NULL kp, jac or blob, NULL A, g or cost with weight > 0, and misaligned pointers (4 bytes; A, g, cost, residual,
+ *   latent 8; kp, blob, workspace 16): SHR_EINVAL.  kp and jac are taken to be finite (NOT checked). */
+int shr_pose_vae_blob_floats(void);
+long long shr_pose_vae_normal_workspace_bytes(int B, int J);
+int shr_pose_vae_normal(const float *kp        /* [B,J,4]: shr_pose_keypoints_jacobian's keypoints, MODEL frame */,
+                        const float *jac       /* [B,3J,26]: shr_pose_keypoints_jacobian's */,
+                        const float *blob      /* [blob_floats]: the packed network */, int blob_floats,
+                        float weight, float latent_weight, int B, int J, int accumulate,
+                        double *A, double *g, double *cost, double *residual /* [B,123] or NULL */,
+                        double *latent /* [B,32] or NULL */, uint32_t *relu_mask /* [B,32] or NULL */,
+                        void *workspace, void *stream);
+
 /* A sequence of frames fitted jointly: the temporal term and the block-tridiagonal step ----------------------------------------
  * Every sample of the entries above is an island, and the data is video.  The reference carries the term for that as
  * TemporalSmoothnessLoss (network/util_modules.py:360-381), ClampedL2lLoss(2500) (network/util_modules.py:349-358) between

@@ -144,6 +144,9 @@ SIGNATURES = {
     "shr_sphere_prior_normal": ([_vp] * 6 + [_f, _f, _vp, _vp, _f] + [_i] * 4 + [_vp] * 7, _i),
     "shr_sphere_collision_normal_workspace_bytes": ([_i, _i, _i], ctypes.c_longlong),
     "shr_sphere_collision_normal": ([_vp] * 5 + [_f] + [_i] * 4 + [_vp] * 7, _i),
+    "shr_pose_vae_blob_floats": ([], _i),
+    "shr_pose_vae_normal_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "shr_pose_vae_normal": ([_vp] * 3 + [_i, _f, _f] + [_i] * 3 + [_vp] * 8, _i),
     "shr_sphere_temporal_normal_workspace_bytes": ([_i, _i, _i], ctypes.c_longlong),
     "shr_sphere_temporal_normal": ([_vp] * 3 + [_f, _f] + [_i] * 4 + [_vp] * 7, _i),
     "shr_pose_lm_seq_state_bytes": ([_i], ctypes.c_longlong),

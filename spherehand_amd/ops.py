@@ -2576,11 +2576,76 @@ def sphere_collision_normal(params, offset, offset_inv, bone, wv, right_hand=Tru
     return A, g, cost, count, penetration
 
 
+def _pose_vae_args(J, dev, blob, weight, latent_weight, name="weight"):
+    """(blob, weight, latent_weight) of the pose-VAE term: the blob of pose_vae.pack_fit_weights on `dev`."""
+    weight, latent_weight = float(weight), float(latent_weight)
+    if not (weight >= 0.0 and weight < float("inf")):
+        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
+    if not (latent_weight >= 0.0 and latent_weight < float("inf")):
+        raise RuntimeError("latent_weight must be finite and >= 0, not %r" % (latent_weight,))
+    if J != 41:
+        raise RuntimeError("the pose-VAE term is built for the hand's 41 spheres, not %d" % J)
+    _check_input(blob, "the pose-VAE blob")
+    if blob.dim() != 1 or blob.shape[0] != _lib.lib().shr_pose_vae_blob_floats() or blob.device != dev:
+        raise RuntimeError("the pose-VAE blob must be pose_vae.pack_fit_weights' [%d] on the parameters' device"
+                           % _lib.lib().shr_pose_vae_blob_floats())
+    return blob, weight, latent_weight
+
+
+def _pose_prior_args(J, dev, pose_prior):
+    """The loops' pose_prior = (blob, weight, latent_weight) checked, or None where the loop issues no launch of the entry
+    (no prior, or weight 0)."""
+    if pose_prior is None:
+        return None
+    try:
+        blob, weight, latent_weight = pose_prior
+    except (TypeError, ValueError):
+        raise RuntimeError("pose_prior must be (blob, weight, latent_weight)")
+    blob, weight, latent_weight = _pose_vae_args(J, dev, blob, weight, latent_weight, "pose_prior's weight")
+    return (blob, weight, latent_weight) if weight > 0.0 else None
+
+
+def pose_vae_normal(params, offset, offset_inv, bone, wv, right_hand, blob, weight, latent_weight=0.0, accumulate_into=None):
+    """The normal equations of the sphere fit's pose-VAE prior (include/spherehand_hip.h, shr_pose_vae_normal): params
+    [B,26], the key-point tables of pose_keypoints_jacobian (J = 41), blob = pose_vae.pack_fit_weights(module) ->
+    (A [B,26,26], g [B,26], cost [B] fp64, residual [B,123] fp64: r = c - 100 recon(c / 100) in mm, latent [B,32] fp64: mu,
+    relu_mask [B,32] int32: the 1024 ReLU decisions of the value column, the header's bit order).  A, g and cost carry
+    `weight` and the latent rows `latent_weight` on top; residual, latent and relu_mask are the term's own.
+    accumulate_into = (A, g, cost) of the other terms at the same pose: weight x the term is ADDED to them in place and they
+    are the A, g, cost returned.  With weight = 0 the three are not touched (without accumulate_into they come back
+    uninitialised).  Two launches: shr_pose_keypoints_jacobian -> shr_pose_vae_normal."""
+    B, J = _ik_tables(params, offset, offset_inv, bone, wv, "parameters")
+    dev = params.device
+    if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
+        raise RuntimeError("every tensor must be on the parameters' device")
+    blob, weight, latent_weight = _pose_vae_args(J, dev, blob, weight, latent_weight)
+    if accumulate_into is not None:
+        A, g, cost = accumulate_into
+        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+            _check_input(t, name, torch.float64)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    lib = _lib.lib()
+    with _on(dev):
+        kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
+        if accumulate_into is None:
+            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
+            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
+            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        residual = torch.empty((B, 123), dtype=torch.float64, device=dev)
+        latent = torch.empty((B, 32), dtype=torch.float64, device=dev)
+        relu_mask = torch.empty((B, 32), dtype=torch.int32, device=dev)
+        _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(blob), blob.shape[0], weight, latent_weight, B, J,
+                                           int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(cost), _ptr(residual),
+                                           _ptr(latent), _ptr(relu_mask), None, _stream()), "shr_pose_vae_normal")
+    return A, g, cost, residual, latent, relu_mask
+
+
 def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
                       pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
                       stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
                       keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
-                      collision=None, collision_weight=0.0):
+                      collision=None, collision_weight=0.0, pose_prior=None):
     """sphere_icp_render with the keypoint and joint-limit terms: `iters` Levenberg-Marquardt iterations on
     sphere_icp_render's energy + kp_weight sum w min(|k - c|, kp_max)^2 + limit_weight sum_i h_i^2, k the predicted
     keypoints [B,V,J,3] in each view's frame with confidence w [B,V,J] (None: 1), c the sphere centres in that frame, h_i the
@@ -2592,7 +2657,10 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     collision = (a [K] int32, b [K] int32, m [K] fp32), hand_model.collision_table's pairs, with collision_weight > 0 adds
     collision_weight sum_k max(m_k - |c_a - c_b|, 0)^2 over the model-frame centres: shr_sphere_collision_normal
     (accumulate = 1) after the prior entry in every evaluation.  Without a weighted collision term no launch of it is
-    issued and the loop is what it is without the two arguments, bit for bit."""
+    issued and the loop is what it is without the two arguments, bit for bit.
+    pose_prior = (blob, weight, latent_weight), the pose-VAE prior (pose_vae_normal) with weight > 0, adds
+    weight (sum r^2 + latent_weight sum mu^2): shr_pose_vae_normal (accumulate = 1) after the collision entry in every
+    evaluation.  With pose_prior = None or weight = 0 no launch of it is issued: the loop without the argument, bit for bit."""
     B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
                                                     max_dist, "start parameters")
     max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
@@ -2603,6 +2671,7 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
                                                                            "collision_weight")
     collide = K > 0 and collision_weight > 0.0
+    vae = _pose_prior_args(J, dev, pose_prior)
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
@@ -2643,6 +2712,10 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
                 _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
                                                            collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
                                                            _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
+            if vae is not None:
+                _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(vae[0]), vae[0].shape[0], vae[1], vae[2], B, J, 1,
+                                                   _ptr(A), _ptr(g), _ptr(cost_data), None, None, None, None, stream),
+                           "shr_pose_vae_normal")
             solve = int(it < iters)
             _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
                                             _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
@@ -2780,7 +2853,8 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
                         pixel_to_model=(1.0, 0.0, 1.0, 0.0), fg_max=1000.0, max_dist=float("inf"), iters=10, lambda0=1e-3,
                         stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
                         keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
-                        collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None):
+                        collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None,
+                        pose_prior=None):
     """sphere_icp_priors over SEQUENCES: the B = S seq_len frames are S sequences of seq_len consecutive frames (adjacent in
     the batch), fitted jointly by `iters` Levenberg-Marquardt iterations on the sum over a sequence's frames of
     sphere_icp_priors' energy + temporal_weight sum_t frame_weight[t] sum_j min(|c_j(t + 1) - c_j(t)|, ts_max)^2, c the
@@ -2793,7 +2867,7 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
     return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
                                  fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
                                  keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
-                                 temporal_weight, ts_max, frame_weight, 0.0, float("inf"), None)
+                                 temporal_weight, ts_max, frame_weight, 0.0, float("inf"), None, pose_prior=pose_prior)
 
 
 def _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight):
@@ -3019,8 +3093,9 @@ def pose_window_prior_normal(trial, Lambda, eta, offset, point, seq_len, into=No
 def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model, fg_max,
                           max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background, keypoints, confidence,
                           kp_weight, kp_max, limits, limit_weight, collision, collision_weight, temporal_weight, ts_max,
-                          frame_weight, accel_weight, acc_max, triple_weight, window_prior=None):
-    """The loop of sphere_icp_sequence, sphere_icp_trajectory and sphere_icp_window.  Without a weighted acceleration term
+                          frame_weight, accel_weight, acc_max, triple_weight, window_prior=None, pose_prior=None):
+    """The loop of sphere_icp_sequence, sphere_icp_trajectory and sphere_icp_window.  pose_prior: sphere_icp_priors', a
+    per-frame term: shr_pose_vae_normal (accumulate = 1) follows the collision entry.  Without a weighted acceleration term
     (accel_weight = 0 or seq_len < 3) it is sphere_icp_sequence's: shr_pose_lm_seq_begin / _step, no F; with one,
     shr_sphere_accel_normal follows the first-difference entry and the step is shr_pose_lm_seq2_begin / _step's.
     window_prior = (Lambda, eta, offset, point) of pose_window_marginalize (None: no prior, no launch): the carried prior's
@@ -3035,6 +3110,7 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
     pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
                                                                            "collision_weight")
     collide = K > 0 and collision_weight > 0.0
+    vae = _pose_prior_args(J, dev, pose_prior)
     T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
     temporal = T > 1 and temporal_weight > 0.0
     accel_weight, acc_max = _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight)
@@ -3087,6 +3163,10 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
                 _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
                                                            collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
                                                            _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
+            if vae is not None:
+                _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(vae[0]), vae[0].shape[0], vae[1], vae[2], B, J, 1,
+                                                   _ptr(A), _ptr(g), _ptr(cost_data), None, None, None, None, stream),
+                           "shr_pose_vae_normal")
             if temporal:
                 _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T,
                                                           J, 1, _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(temporal_rows),
@@ -3114,7 +3194,7 @@ def sphere_icp_trajectory(observed, view, params0, offset, offset_inv, bone, wv,
                           stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
                           keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
                           collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None,
-                          accel_weight=1.0, acc_max=float("inf"), triple_weight=None):
+                          accel_weight=1.0, acc_max=float("inf"), triple_weight=None, pose_prior=None):
     """sphere_icp_sequence with the constant-velocity term: the energy of a sequence gains
     accel_weight sum_k triple_weight[k] sum_j min(|c_j(k - 1) - 2 c_j(k) + c_j(k + 1)|, acc_max)^2 over its triples of
     consecutive frames -> (params [B,26], cost0 [S], cost [S]).  Each of the iters + 1 evaluations is sphere_icp_sequence's
@@ -3126,7 +3206,8 @@ def sphere_icp_trajectory(observed, view, params0, offset, offset_inv, bone, wv,
     return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
                                  fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
                                  keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
-                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight)
+                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight,
+                                 pose_prior=pose_prior)
 
 
 def sphere_icp_window(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand=True,
@@ -3134,7 +3215,7 @@ def sphere_icp_window(observed, view, params0, offset, offset_inv, bone, wv, rad
                       stiffness=None, prior=None, render_weight=1.0, max_resid=float("inf"), background=100.0,
                       keypoints=None, confidence=None, kp_weight=1.0, kp_max=float("inf"), limits=None, limit_weight=0.0,
                       collision=None, collision_weight=0.0, temporal_weight=1.0, ts_max=float("inf"), frame_weight=None,
-                      accel_weight=1.0, acc_max=float("inf"), triple_weight=None, window_prior=None):
+                      accel_weight=1.0, acc_max=float("inf"), triple_weight=None, window_prior=None, pose_prior=None):
     """sphere_icp_trajectory over a sliding window that carries its marginalised past: window_prior = (Lambda [S,52,52],
     eta [S,52], offset [S] fp64, point [S,52] fp32), pose_window_marginalize's record, adds
     (d^T Lambda d + 2 eta^T d) + offset, d = (p_0, p_1) - point, to the energy of each sequence (a record that a failed pivot
@@ -3146,7 +3227,8 @@ def sphere_icp_window(observed, view, params0, offset, offset_inv, bone, wv, rad
     return _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv, radii, seq_len, right_hand, pixel_to_model,
                                  fg_max, max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background,
                                  keypoints, confidence, kp_weight, kp_max, limits, limit_weight, collision, collision_weight,
-                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight, window_prior)
+                                 temporal_weight, ts_max, frame_weight, accel_weight, acc_max, triple_weight, window_prior,
+                                 pose_prior)
 
 
 PoseLmSharedMaxK = 64        # shared parameters of a group at most (shr_pose_lm_shared_step)

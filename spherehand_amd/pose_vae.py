@@ -74,6 +74,55 @@ class PoseVae(nn.Module):
         return self.decoder(mu).view(num_batch, num_view, -1, 3)
 
 
+# ---- the network as the sphere fit's Gauss-Newton term reads it (include/spherehand_hip.h, shr_pose_vae_normal) ----------
+# Per linear layer in network order: (state-dict prefix, K padded to a multiple of 4, OUT padded to a multiple of 32, the
+# prefix of the GroupNorm behind it or None).  The logvar head is not part of the term (z = mu).
+FIT_LAYERS = (("base.0", 124, 256, "base.1"), ("base.3", 256, 256, "base.4"), ("mu", 256, 32, None),
+              ("decoder.0", 32, 256, "decoder.1"), ("decoder.3", 256, 256, "decoder.4"), ("decoder.6", 256, 128, None))
+FIT_BLOB_FLOATS = sum(k * o + o + (512 if gn else 0) for _, k, o, gn in FIT_LAYERS)      # 215 200
+
+
+def pack_fit_weights(module):
+    """The fp32 blob shr_pose_vae_normal reads, [FIT_BLOB_FLOATS] on the module's device: per layer of FIT_LAYERS the
+    weight k-major -- element ((q OUT + o) 2 + h) 2 + s is W[o][4 q + 2 s + h], zero where o or k is padding (the 123
+    inputs are padded to K = 124, the 123 outputs to 128) -- then the bias [OUT], then gamma [256] and beta [256] of the
+    GroupNorm behind it, if any.  unpack_fit_weights inverts it exactly."""
+    if (module.pose_fea, module.latent_fea) != (123, 32):
+        raise RuntimeError("the fit's term is built for PoseVae(123, 32)")
+    sd = {k: v.detach().to(torch.float32) for k, v in module.state_dict().items()}
+    parts = []
+    for name, K, OUT, gn in FIT_LAYERS:
+        W, b = sd[name + ".weight"], sd[name + ".bias"]
+        if W.shape[0] > OUT or W.shape[1] > K or (gn is not None and tuple(sd[gn + ".weight"].shape) != (256,)):
+            raise RuntimeError("%s is not a layer of the 123-256-256-32-256-256-123 network" % name)
+        Wp = W.new_zeros(OUT, K)
+        Wp[:W.shape[0], :W.shape[1]] = W
+        parts.append(Wp.view(OUT, K // 4, 2, 2).permute(1, 0, 3, 2).reshape(-1))      # [o][q][s][h] -> [q][o][h][s]
+        bp = b.new_zeros(OUT)
+        bp[:b.shape[0]] = b
+        parts.append(bp)
+        if gn is not None:
+            parts += [sd[gn + ".weight"], sd[gn + ".bias"]]
+    blob = torch.cat(parts).contiguous()
+    assert blob.numel() == FIT_BLOB_FLOATS
+    return blob
+
+
+def unpack_fit_weights(blob):
+    """{state-dict name: fp32 tensor} of the arrays pack_fit_weights packed (the padding dropped)."""
+    shapes = {"base.0": (256, 123), "base.3": (256, 256), "mu": (32, 256), "decoder.0": (256, 32), "decoder.3": (256, 256),
+              "decoder.6": (123, 256)}
+    out, at = {}, 0
+    for name, K, OUT, gn in FIT_LAYERS:
+        o, k = shapes[name]
+        Wp = blob[at:at + K * OUT].view(K // 4, OUT, 2, 2).permute(1, 0, 3, 2).reshape(OUT, K)
+        out[name + ".weight"], at = Wp[:o, :k].contiguous(), at + K * OUT
+        out[name + ".bias"], at = blob[at:at + o].clone(), at + OUT
+        if gn is not None:
+            out[gn + ".weight"], out[gn + ".bias"], at = blob[at:at + 256].clone(), blob[at + 256:at + 512].clone(), at + 512
+    return out
+
+
 def default_pose_vae():
     """The prior MultiTaskLoss builds when `--prior` is on (PoseVae(41*3, 32, 'mesh/model/pose_vae.pth'))."""
     if not os.path.exists(DEFAULT_WEIGHTS):

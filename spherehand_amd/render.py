@@ -1068,6 +1068,36 @@ class SpherePriorPoseFitter(SphereRenderPoseFitter):
                                        self.kp_weight, self.kp_max, limits, self.limit_weight, (A, g, cost))
 
 
+class PoseVaePrior(nn.Module):
+    """The frozen pose VAE as a Gauss-Newton term of the sphere fit (include/spherehand_hip.h, shr_pose_vae_normal):
+        weight (sum_i r_i^2 + latent_weight sum_k mu_k^2),  r = c - 100 recon(c / 100) in mm
+    over the 41 model-frame sphere centres c, mu the network's latent mean (z = mu: no draw, no logvar term).  The
+    reference's PoseVae behind --prior (network/pose_vae.py:11-99) is a first-order training term; here its exact Jacobian
+    enters the normal equations.  Holds the packed network (pose_vae.pack_fit_weights) as a buffer; hand it to a fitter as
+    `pose_prior=`.  weight None: DEFAULT_WEIGHT, DESIGN.md 4.4zzz's.  What the term does NOT give: the network saw the global
+    pose in training, so r is not invariant under a translation of the hand (DESIGN.md 4.4zzz has the figures), and r of a
+    plausible pose is not zero (rms 5.8 mm on the sampler's poses): it is a loose prior, no observation."""
+
+    # DESIGN.md 4.4zzz: no row of the study helps the hidden finger, and every weight from 0.1 on costs the well-observed
+    # frames, so the default is the reference's ratio of its prior weight (1e-2) to its data weight (mv_projection, 1)
+    DEFAULT_WEIGHT = 1e-2
+
+    def __init__(self, weights=None, weight=None, latent_weight=0.0):
+        super().__init__()
+        from . import pose_vae
+        self.weight = float(self.DEFAULT_WEIGHT if weight is None else weight)
+        self.latent_weight = float(latent_weight)
+        if not (self.weight >= 0.0 and self.weight < float("inf")) or \
+                not (self.latent_weight >= 0.0 and self.latent_weight < float("inf")):
+            raise ValueError("weight and latent_weight must be finite and >= 0")
+        module = pose_vae.PoseVae(41 * 3, 32, model_path=pose_vae.DEFAULT_WEIGHTS if weights is None else weights)
+        self.register_buffer('blob', pose_vae.pack_fit_weights(module))
+
+    def term(self):
+        """(blob, weight, latent_weight): the loops' pose_prior argument."""
+        return self.blob, self.weight, self.latent_weight
+
+
 class SphereCollisionPoseFitter(SpherePriorPoseFitter):
     """SpherePriorPoseFitter with the term a sphere-model tracker carries against self-penetration: `iters`
     Levenberg-Marquardt iterations on
@@ -1095,10 +1125,13 @@ class SphereCollisionPoseFitter(SpherePriorPoseFitter):
     def __init__(self, mesh, width, height, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3, stiffness=None,
                  fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None, max_resid=None,
                  background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None, collision_weight=None,
-                 min_dist=None, radius_scale=None):
+                 min_dist=None, radius_scale=None, *, pose_prior=None):
         super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
                          render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits)
         from .hand_model import collision_table
+        if pose_prior is not None and not isinstance(pose_prior, PoseVaePrior):
+            raise ValueError("pose_prior must be a PoseVaePrior or None")
+        self.pose_prior = pose_prior                           # (a submodule: it moves with the fitter)
         self.collision_weight = float(self.DEFAULT_COLLISION_WEIGHT if collision_weight is None else collision_weight)
         if not (self.collision_weight >= 0.0 and self.collision_weight < float("inf")):
             raise ValueError("collision_weight must be finite and >= 0")
@@ -1112,6 +1145,10 @@ class SphereCollisionPoseFitter(SpherePriorPoseFitter):
     def _pairs(self):
         return self.pair_a, self.pair_b, self.pair_min
 
+    def _pose_prior(self):
+        """The loops' pose_prior: (blob, weight, latent_weight), or None without a weighted prior."""
+        return None if self.pose_prior is None or self.pose_prior.weight == 0.0 else self.pose_prior.term()
+
     @torch.no_grad()
     def solve(self, observed, params0, view=None, prior=None, keypoints=None, confidence=None):
         observed, view, keypoints, confidence, limits = self._targets(observed, view, keypoints, confidence)
@@ -1119,14 +1156,19 @@ class SphereCollisionPoseFitter(SpherePriorPoseFitter):
                                      self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
                                      None if prior is None else prior.detach().contiguous().float(), self.render_weight,
                                      self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
-                                     limits, self.limit_weight, collision=self._pairs(), collision_weight=self.collision_weight)
+                                     limits, self.limit_weight, collision=self._pairs(), collision_weight=self.collision_weight,
+                                     pose_prior=self._pose_prior())
 
     @torch.no_grad()
     def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None):
         params = params.detach().contiguous().float()
         A, g, cost = SpherePriorPoseFitter.normal_equations(self, observed, params, view, keypoints, confidence)[:3]
-        return ops.sphere_collision_normal(params, *self._tables()[:4], self.right_hand, self._pairs(), self.collision_weight,
-                                           (A, g, cost))
+        out = ops.sphere_collision_normal(params, *self._tables()[:4], self.right_hand, self._pairs(), self.collision_weight,
+                                          (A, g, cost))
+        term = self._pose_prior()
+        if term is not None:                                   # added in place: `out` holds the same A, g and cost
+            ops.pose_vae_normal(params, *self._tables()[:4], self.right_hand, *term, accumulate_into=(A, g, cost))
+        return out
 
 
 class SphereSequencePoseFitter(SphereCollisionPoseFitter):
@@ -1157,10 +1199,11 @@ class SphereSequencePoseFitter(SphereCollisionPoseFitter):
     def __init__(self, mesh, width, height, seq_len, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3,
                  stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None,
                  max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
-                 collision_weight=None, min_dist=None, radius_scale=None, temporal_weight=None, ts_max=None):
+                 collision_weight=None, min_dist=None, radius_scale=None, temporal_weight=None, ts_max=None, *,
+                 pose_prior=None):
         super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
                          render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits, collision_weight,
-                         min_dist, radius_scale)
+                         min_dist, radius_scale, pose_prior=pose_prior)
         self.seq_len = int(seq_len)
         self.temporal_weight = float(self.DEFAULT_TEMPORAL_WEIGHT if temporal_weight is None else temporal_weight)
         self.ts_max = float(self.DEFAULT_TS_MAX if ts_max is None else ts_max)
@@ -1181,7 +1224,7 @@ class SphereSequencePoseFitter(SphereCollisionPoseFitter):
                                        None if prior is None else prior.detach().contiguous().float(), self.render_weight,
                                        self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
                                        limits, self.limit_weight, self._pairs(), self.collision_weight, self.temporal_weight,
-                                       self.ts_max, self._frame_weight(frame_weight))
+                                       self.ts_max, self._frame_weight(frame_weight), pose_prior=self._pose_prior())
 
     @torch.no_grad()
     def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, frame_weight=None):
@@ -1231,10 +1274,10 @@ class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
                  stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=None,
                  max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
                  collision_weight=None, min_dist=None, radius_scale=None, temporal_weight=None, ts_max=None,
-                 accel_weight=None, acc_max=None):
+                 accel_weight=None, acc_max=None, *, pose_prior=None):
         super().__init__(mesh, width, height, seq_len, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist,
                          render_weight, max_resid, background, kp_weight, kp_max, limit_weight, limits, collision_weight,
-                         min_dist, radius_scale, temporal_weight, ts_max)
+                         min_dist, radius_scale, temporal_weight, ts_max, pose_prior=pose_prior)
         self.accel_weight = float(self.DEFAULT_ACCEL_WEIGHT if accel_weight is None else accel_weight)
         self.acc_max = float(self.DEFAULT_ACC_MAX if acc_max is None else acc_max)
         if not (self.accel_weight >= 0.0 and self.accel_weight < float("inf")) or not self.acc_max >= 0.0:
@@ -1251,7 +1294,7 @@ class SphereTrajectoryPoseFitter(SphereSequencePoseFitter):
                                          self.max_resid, self.background, keypoints, confidence, self.kp_weight, self.kp_max,
                                          limits, self.limit_weight, self._pairs(), self.collision_weight, self.temporal_weight,
                                          self.ts_max, self._frame_weight(frame_weight), self.accel_weight, self.acc_max,
-                                         self._frame_weight(triple_weight))
+                                         self._frame_weight(triple_weight), pose_prior=self._pose_prior())
 
     @torch.no_grad()
     def normal_equations(self, observed, params, view=None, keypoints=None, confidence=None, frame_weight=None,
@@ -1312,7 +1355,8 @@ class SphereWindowTracker(SphereTrajectoryPoseFitter):
                                      self.pixel_to_model, self.fg_max, self.max_dist, self.iters, self.lambda0, self.stiffness,
                                      None, self.render_weight, self.max_resid, self.background, keypoints, confidence,
                                      self.kp_weight, self.kp_max, limits, self.limit_weight, self._pairs(), self.collision_weight,
-                                     self.temporal_weight, self.ts_max, None, self.accel_weight, self.acc_max, None, prior)
+                                     self.temporal_weight, self.ts_max, None, self.accel_weight, self.acc_max, None, prior,
+                                     self._pose_prior())
 
     @torch.no_grad()
     def begin(self, observed, params0, view=None, keypoints=None, confidence=None):
@@ -1438,7 +1482,9 @@ class SphereRadiiCalibrator(SphereCollisionPoseFitter):
     def __init__(self, mesh, width, height, group_size, pixel_to_model=None, right_hand=True, iters=10, lambda0=1e-3,
                  stiffness=None, fg_max=MeshDataToModelLoss.REFERENCE_FG_MAX, max_dist=50.0, render_weight=0.0,
                  max_resid=None, background=100.0, kp_weight=None, kp_max=None, limit_weight=None, limits=None,
-                 collision_weight=None, min_dist=None, radius_scale=None, shape_stiffness=None):
+                 collision_weight=None, min_dist=None, radius_scale=None, shape_stiffness=None, *, pose_prior=None):
+        if pose_prior is not None:
+            raise ValueError("SphereRadiiCalibrator takes no pose_prior: its loop does not issue the term")
         if render_weight is None or float(render_weight) != 0.0:
             raise ValueError("SphereRadiiCalibrator has no render term: its radius columns are not formed (render_weight must be 0)")
         super().__init__(mesh, width, height, pixel_to_model, right_hand, iters, lambda0, stiffness, fg_max, max_dist, 0.0,
