@@ -16,9 +16,8 @@ namespace shr {
 constexpr int kIcpThreads = 256;
 constexpr int kIcpRounds = 4;
 constexpr int kIcpTilePix = kIcpThreads * kIcpRounds;   // the unit of the summation order: part of the contract
-constexpr int kIcpTri = kLmN * (kLmN + 1) / 2;          // 351
 constexpr int kIcpSlots = 384;                          // doubles of a tile's record in the workspace: A's lower triangle, g,
-static_assert(kIcpTri + kLmN + 2 <= kIcpSlots, "");     // cost, count (379), one thread of the reduction each
+static_assert(kNeqTri + kLmN + 2 <= kIcpSlots, "");     // cost, count (379), one thread of the reduction each
 constexpr int kIcpRow = kLmN + 1;                       // a row's stride in LDS (27: the threads' rows start in different banks)
 
 struct IcpLds {
@@ -35,13 +34,14 @@ enum { kIcpA = 0, kIcpG = 1, kIcpCost = 2, kIcpCount = 3, kIcpNone = 4 };
 // entry idx of a tile's record: (kind, a, c)
 __device__ __forceinline__ int icp_entry(int idx, int &a, int &c) {
   a = c = 0;
-  if (idx < kIcpTri) {
-    while ((a + 1) * (a + 2) / 2 <= idx) a++;
-    c = idx - a * (a + 1) / 2;                          // a >= c
+  if (idx < kNeqTri) {
+    const NeqEntry e = neq_entry(idx);
+    a = e.a;
+    c = e.c;
     return kIcpA;
   }
-  if (idx < kIcpTri + kLmN) { a = idx - kIcpTri; return kIcpG; }
-  return idx == kIcpTri + kLmN ? kIcpCost : idx == kIcpTri + kLmN + 1 ? kIcpCount : kIcpNone;
+  if (idx < kNeqTri + kLmN) { a = idx - kNeqTri; return kIcpG; }
+  return idx == kNeqTri + kLmN ? kIcpCost : idx == kNeqTri + kLmN + 1 ? kIcpCount : kIcpNone;
 }
 
 // A workgroup-uniform float re-read from its scalar register where it is used.  The nine entries of a view's rotation are

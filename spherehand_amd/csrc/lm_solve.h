@@ -4,11 +4,11 @@
 // order: the same bits wherever it runs.
 // S: the wave's LDS, with double A[26 * 26] (lower triangle read), L[26 * 26], x[26] and piv.
 #pragma once
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kLmN = 26;             // pose parameters
+constexpr int kLmN = kNeqN;          // pose parameters (normal_eq.h)
 
 // L L^T = A + lam diag(A), column by column, lane i owning row i.  false: a pivot that is not positive and finite.
 template <class S>

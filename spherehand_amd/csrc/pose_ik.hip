@@ -22,7 +22,6 @@ namespace shr {
 
 constexpr int kIkPoints = 64;        // key-points per crop (lane j owns point j)
 constexpr int kIkN = kLmN;           // pose parameters
-constexpr int kIkTri = kIkN * (kIkN + 1) / 2;
 
 struct IkPoint {                     // lane j's point: bone, rest position, weight and the keypoint at the last evaluation
   int bone;
@@ -134,11 +133,10 @@ __device__ __forceinline__ void ik_jacobian(IkLds &s, const IkPoint &pt, const f
 template <bool WANT_G>
 __device__ __forceinline__ void ik_normal(IkLds &s, const float *p, int lane, int J) {
 #pragma unroll 1
-  for (int idx = lane; idx < kIkTri + (WANT_G ? kIkN : 0); idx += 64) {
-    if (idx < kIkTri) {
-      int a = 0;
-      while ((a + 1) * (a + 2) / 2 <= idx) a++;
-      const int c = idx - a * (a + 1) / 2;          // a >= c
+  for (int idx = lane; idx < kNeqTri + (WANT_G ? kIkN : 0); idx += 64) {
+    if (idx < kNeqTri) {
+      const NeqEntry e = neq_entry(idx);
+      const int a = e.a, c = e.c;
       double acc = 0.0;
       if (!(c >= 6 && (a - 6) / 4 != (c - 6) / 4)) {
 #pragma unroll 2
@@ -152,7 +150,7 @@ __device__ __forceinline__ void ik_normal(IkLds &s, const float *p, int lane, in
       if (a == c) acc += (double)s.mu[a];
       s.A[a * kIkN + c] = acc;
     } else {
-      const int a = idx - kIkTri;
+      const int a = idx - kNeqTri;
       double acc = 0.0;
 #pragma unroll 1
       for (int j = 0; j < J; j++) {

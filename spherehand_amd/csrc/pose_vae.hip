@@ -26,18 +26,15 @@
 //   rows      r_i = 100 ((double)x_i - (double)recon_i), J_r[i][c] = (double)jac[i][c] - (double)recon'[i][c]: the tangent
 //             columns carry jac itself (the layers are linear in the tangent, so the 100 of x = c / 100 and the 100 of r
 //             cancel) and the identity part is exact.
-//   add       thread t owns entries t, t + 256 of A's 351 lower entries and g's 26 as sphere_collision_kernel does: fp64
+//   add       thread t owns entries t, t + 256 of A's 351 lower entries and g's 26 (normal_eq.h's neq_owned): fp64
 //             chains over rows 0 .. 122, then the 32 latent rows; the last thread runs the cost chains.
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kPvThreads = 256;
 constexpr int kPvJ = 41;
 constexpr int kPvIn = 3 * kPvJ;                            // 123
-constexpr int kPvN = 26;
-constexpr int kPvCols = kPvN + 1;                          // 27: the value and the tangents
-constexpr int kPvTri = kPvN * (kPvN + 1) / 2;              // 351
+constexpr int kPvCols = kNeqN + 1;                          // 27: the value and the tangents
 constexpr int kPvHidden = 256;
 constexpr int kPvLatent = 32;
 constexpr float kPvEps = 1e-5f;
@@ -173,19 +170,16 @@ __device__ __forceinline__ void pv_hidden(PvLds &s, const float *__restrict__ bl
   __syncthreads();
 }
 
-// mode 0: A, g, cost = the term's; 1: they are added to what the buffers hold; 2: A, g and cost are left alone
-enum { kPvWrite = 0, kPvAdd = 1, kPvKeep = 2 };
-
-__global__ void __launch_bounds__(kPvThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, const float *__restrict__ blob, double w, double lw,
                 int mode, double *__restrict__ A, double *__restrict__ g, double *__restrict__ cost,
                 double *__restrict__ residual, double *__restrict__ latent, uint32_t *__restrict__ relu_mask) {
   __shared__ PvLds s;
   const int tid = threadIdx.x, b = blockIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const float *jb = jac + (size_t)b * kPvIn * kPvN;
+  const float *jb = jac + (size_t)b * kPvIn * kNeqN;
   // M0 = [x | jac], x = c / 100 (one IEEE division); row 123 and columns 27 .. 31 are +0
-  for (int idx = tid; idx < kPvK1 * 32; idx += kPvThreads) {
+  for (int idx = tid; idx < kPvK1 * 32; idx += kNeqThreads) {
     const int i = idx >> 5, c = idx & 31;
     float v = 0.f;
     if (i < kPvIn) {
@@ -194,7 +188,7 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
         const int a = i - 3 * (i / 3);
         v = (a == 0 ? p.x : (a == 1 ? p.y : p.z)) / 100.0f;
       } else if (c < kPvCols) {
-        v = jb[i * kPvN + c - 1];
+        v = jb[i * kNeqN + c - 1];
       }
     }
     s.act[idx] = v;
@@ -208,7 +202,7 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
     __syncthreads();
     pv_store<1>(s.act + wave * 1024, part, 0, lane);
     __syncthreads();
-    for (int idx = tid; idx < 1024; idx += kPvThreads)
+    for (int idx = tid; idx < 1024; idx += kNeqThreads)
       s.lat[idx] = ((s.act[idx] + s.act[1024 + idx]) + s.act[2048 + idx]) + s.act[3072 + idx];
     __syncthreads();
   }
@@ -230,7 +224,7 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
           const float x = (a == 0 ? p.x : (a == 1 ? p.y : p.z)) / 100.0f;
           v = 100.0 * ((double)x - (double)acc[0][r]);
         } else {
-          v = (double)jb[i * kPvN + col - 1] - (double)acc[0][r];
+          v = (double)jb[i * kNeqN + col - 1] - (double)acc[0][r];
         }
         s.rows[i * kPvCols + col] = v;
       }
@@ -238,23 +232,13 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
     __syncthreads();
   }
   if (residual)
-    for (int i = tid; i < kPvIn; i += kPvThreads) residual[(size_t)b * kPvIn + i] = s.rows[i * kPvCols];
+    for (int i = tid; i < kPvIn; i += kNeqThreads) residual[(size_t)b * kPvIn + i] = s.rows[i * kPvCols];
   if (latent && tid < kPvLatent) latent[(size_t)b * kPvLatent + tid] = (double)s.lat[tid * 32];
   if (relu_mask && tid < 32) relu_mask[(size_t)b * 32 + tid] = s.mask[tid];
-  if (mode == kPvKeep) return;
-  // the entries this thread owns (sphere_collision_kernel's assignment)
-  int a0 = 0;
-  while ((a0 + 1) * (a0 + 2) / 2 <= tid) a0++;
-  const int c0 = tid - a0 * (a0 + 1) / 2;
-  const int idx1 = tid + kPvThreads;
-  int a1 = a0, c1 = -1;
-  if (idx1 < kPvTri) {
-    while ((a1 + 1) * (a1 + 2) / 2 <= idx1) a1++;
-    c1 = idx1 - a1 * (a1 + 1) / 2;
-  } else if (idx1 < kPvTri + kPvN) {
-    a1 = idx1 - kPvTri;
-  }
-  const bool own_g = idx1 >= kPvTri && idx1 < kPvTri + kPvN;
+  if (mode == kNeqKeep) return;
+  const NeqOwned own = neq_owned(tid);
+  const int a0 = own.a0, c0 = own.c0, a1 = own.a1, c1 = own.c1;
+  const bool add = mode == kNeqAdd;
   const bool with_latent = lw > 0.0;
   // the second entry's two columns of a row: A's (1 + a1, 1 + c1), g's (0, 1 + a1); a thread without one sums what it drops
   const int p1 = c1 >= 0 ? 1 + c1 : 0, q1 = 1 + a1;
@@ -274,7 +258,7 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
     acc0 = acc0 + lw * l0;
     acc1 = acc1 + lw * l1;
   }
-  if (tid == kPvThreads - 1) {
+  if (tid == kNeqThreads - 1) {
     double C = 0.0;
     for (int i = 0; i < kPvIn; i++) C += s.rows[i * kPvCols] * s.rows[i * kPvCols];
     if (with_latent) {
@@ -282,27 +266,11 @@ pose_vae_kernel(const float4 *__restrict__ kp, const float *__restrict__ jac, co
       for (int k = 0; k < kPvLatent; k++) L += (double)s.lat[k * 32] * (double)s.lat[k * 32];
       C = C + lw * L;
     }
-    const double c = w * C;
-    cost[b] = mode == kPvAdd ? cost[b] + c : c;
+    neq_emit_cost(cost, b, w * C, add);
   }
-  {
-    const double mine = w * acc0;
-    double *low = A + ((size_t)b * kPvN + a0) * kPvN + c0;
-    const double v = mode == kPvAdd ? *low + mine : mine;
-    *low = v;
-    A[((size_t)b * kPvN + c0) * kPvN + a0] = v;
-  }
-  if (c1 >= 0) {
-    const double mine = w * acc1;
-    double *low = A + ((size_t)b * kPvN + a1) * kPvN + c1;
-    const double v = mode == kPvAdd ? *low + mine : mine;
-    *low = v;
-    A[((size_t)b * kPvN + c1) * kPvN + a1] = v;
-  } else if (own_g) {
-    const double mine = w * acc1;
-    double *out = g + (size_t)b * kPvN + a1;
-    *out = mode == kPvAdd ? *out + mine : mine;
-  }
+  neq_emit_A(A, b, a0, c0, w * acc0, add);
+  if (c1 >= 0) neq_emit_A(A, b, a1, c1, w * acc1, add);
+  else if (own.own_g) neq_emit_g(g, b, a1, w * acc1, add);
 }
 
 }  // namespace shr
@@ -319,20 +287,18 @@ extern "C" long long shr_pose_vae_normal_workspace_bytes(int B, int J) {
 extern "C" int shr_pose_vae_normal(const float *kp, const float *jac, const float *blob, int blob_floats, float weight,
                                    float latent_weight, int B, int J, int accumulate, double *A, double *g, double *cost,
                                    double *residual, double *latent, uint32_t *relu_mask, void *workspace, void *stream) {
-  const float finite = 3.40282346638528859812e38f;
   if (B < 0 || J != kPvJ || (accumulate != 0 && accumulate != 1)) return SHR_EINVAL;
-  if (!(weight >= 0.f) || !(weight <= finite) || !(latent_weight >= 0.f) || !(latent_weight <= finite)) return SHR_EINVAL;
+  if (!neq_weight_ok(weight) || !neq_weight_ok(latent_weight)) return SHR_EINVAL;
   if (blob_floats != kPvBlob) return SHR_EINVAL;
-  if (B > 65535) return SHR_ETOOLARGE;
+  if (neq_too_large(B, 1, J)) return SHR_ETOOLARGE;
   if (B == 0) return SHR_OK;
   const bool used = weight > 0.f;
   if (!kp || !jac || !blob || (used && (!A || !g || !cost))) return SHR_EINVAL;
-  if ((((uintptr_t)jac | (uintptr_t)relu_mask) & 3u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost | (uintptr_t)residual | (uintptr_t)latent) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)kp | (uintptr_t)blob | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if (!neq_aligned(4, jac, relu_mask) || !neq_aligned(8, A, g, cost, residual, latent) || !neq_aligned(16, kp, blob, workspace))
+    return SHR_EINVAL;
   if (!used && !residual && !latent && !relu_mask) return SHR_OK;     // nothing to write: no launch
-  const int mode = !used ? kPvKeep : (accumulate ? kPvAdd : kPvWrite);
-  hipLaunchKernelGGL(pose_vae_kernel, dim3((unsigned)B), dim3(kPvThreads), 0, (hipStream_t)stream,
+  const int mode = !used ? kNeqKeep : (accumulate ? kNeqAdd : kNeqWrite);
+  hipLaunchKernelGGL(pose_vae_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4 *>(kp), jac, blob, (double)weight, (double)latent_weight, mode, A, g, cost,
                      residual, latent, relu_mask);
   return (int)hipGetLastError();

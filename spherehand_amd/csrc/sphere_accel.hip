@@ -17,40 +17,23 @@
 //   decide    thread 64 which + j decides (triple `which`, sphere j): a in fp64 from the fp32 centres of b - 2 ... b + 2, n2,
 //             the cost term min(n2, cap2) and whether the sphere has rows (n2 < cap2; a NaN n2: no term at all).
 //   add       thread t owns entries t, t + 256 of A's 351 lower entries and g's 26, and entries t, t + 256, t + 512 of E's and
-//             F's 676 each: chains from 0 over the spheres with rows, ascending, a sphere's three axes summed first.  The
+//             F's 676 each: normal_eq.h's chains from 0 over the spheres with rows, ascending, a sphere's three axes summed first.  The
 //             last thread runs prev's cost chain: the triple's cost is stored with its last frame.
 //   A frame reads its neighbours' inputs and writes only its own outputs; a sequence does not see the other sequences.
 //   LDS banks: in the add loops a wave's lanes read jac[3j + axis][r] and [c] of ONE sphere: 26 consecutive dwords, distinct
 //   entries in distinct banks, equal entries one address; a, term and act are read at one address by all lanes.
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kSanThreads = 256;
-constexpr int kSanMaxJ = 64;
-constexpr int kSanN = 26;                                  // pose parameters
-constexpr int kSanTri = kSanN * (kSanN + 1) / 2;           // 351
-
 struct SanLds {
-  float jac[3][kSanMaxJ * 3 * kSanN];                      // frame b's, b + 1's, b + 2's
-  double a[3][kSanMaxJ][3];                                // prev, mid, next: (c(k - 1) + c(k + 1)) - 2 c(k)
-  double term[3][kSanMaxJ];                                // min(n2, cap2); 0 where the sphere has no term
-  int act[3][kSanMaxJ];                                    // the sphere has rows
+  float jac[3][kNeqMaxJ * 3 * kNeqN];                      // frame b's, b + 1's, b + 2's
+  double a[3][kNeqMaxJ][3];                                // prev, mid, next: (c(k - 1) + c(k + 1)) - 2 c(k)
+  double term[3][kNeqMaxJ];                                // min(n2, cap2); 0 where the sphere has no term
+  int act[3][kNeqMaxJ];                                    // the sphere has rows
 };
 
-// the chain over the spheres with rows of triple `which` of sum_axis x[3j + axis][r] y[3j + axis][c]
-__device__ __forceinline__ double san_gram(const SanLds &s, int which, const float *x, const float *y, int r, int c, int J) {
-  double acc = 0.0;
-  for (int j = 0; j < J; j++) {
-    if (!s.act[which][j]) continue;                        // a sphere without rows adds nothing
-    const float *q0 = x + 3 * j * kSanN + r, *q1 = y + 3 * j * kSanN + c;
-    acc += ((double)q0[0] * (double)q1[0] + (double)q0[kSanN] * (double)q1[kSanN]) +
-           (double)q0[2 * kSanN] * (double)q1[2 * kSanN];
-  }
-  return acc;
-}
-
-__global__ void __launch_bounds__(kSanThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_accel_kernel(const float4 *__restrict__ centres, const float *__restrict__ jac, const float *__restrict__ triple_weight,
                     double aw, double cap2, int T, int J, int add, int add_E, int used, double *__restrict__ A,
                     double *__restrict__ g, double *__restrict__ E, double *__restrict__ F, double *__restrict__ cost,
@@ -66,13 +49,13 @@ sphere_accel_kernel(const float4 *__restrict__ centres, const float *__restrict_
   const bool live_p = fp > 0.f, live_m = fm > 0.f, live_n = fn > 0.f;      // (a NaN weight: no term)
   const bool use_p = used && live_p, use_m = used && live_m, use_n = used && live_n;
   const double wp = use_p ? aw * (double)fp : 0.0, wm = use_m ? aw * (double)fm : 0.0, wn = use_n ? aw * (double)fn : 0.0;
-  const int jsize = 3 * J * kSanN;
+  const int jsize = 3 * J * kNeqN;
   if (use_p || use_m || use_n)
-    for (int idx = tid; idx < jsize; idx += kSanThreads) s.jac[0][idx] = jac[(size_t)b * jsize + idx];
+    for (int idx = tid; idx < jsize; idx += kNeqThreads) s.jac[0][idx] = jac[(size_t)b * jsize + idx];
   if (use_m || use_n)                                      // (frame b + 1 is in the sequence: t <= T - 2)
-    for (int idx = tid; idx < jsize; idx += kSanThreads) s.jac[1][idx] = jac[(size_t)(b + 1) * jsize + idx];
+    for (int idx = tid; idx < jsize; idx += kNeqThreads) s.jac[1][idx] = jac[(size_t)(b + 1) * jsize + idx];
   if (use_n)                                               // (frame b + 2 is in the sequence: t <= T - 3)
-    for (int idx = tid; idx < jsize; idx += kSanThreads) s.jac[2][idx] = jac[(size_t)(b + 2) * jsize + idx];
+    for (int idx = tid; idx < jsize; idx += kNeqThreads) s.jac[2][idx] = jac[(size_t)(b + 2) * jsize + idx];
   if (tid < 3 * 64) {                                      // decide: wave 0 prev, wave 1 mid, wave 2 next
     const int which = tid >> 6, j = tid & 63;
     if (j < J) {
@@ -104,13 +87,13 @@ sphere_accel_kernel(const float4 *__restrict__ centres, const float *__restrict_
     count[b] = rows;
   }
   // F: always written; +0 where the frame is not the first of a weighted triple.  E: written, or added to what it holds
-  for (int idx = tid; idx < kSanN * kSanN; idx += kSanThreads) {
-    const int r = idx / kSanN, c = idx - r * kSanN;
-    F[(size_t)b * kSanN * kSanN + idx] = use_n ? wn * san_gram(s, 2, s.jac[0], s.jac[2], r, c, J) : 0.0;
-    double *out = E + (size_t)b * kSanN * kSanN + idx;
+  for (int idx = tid; idx < kNeqN * kNeqN; idx += kNeqThreads) {
+    const int r = idx / kNeqN, c = idx - r * kNeqN;
+    F[(size_t)b * kNeqN * kNeqN + idx] = use_n ? wn * neq_gram(s.act[2], s.jac[0], s.jac[2], r, c, J) : 0.0;
+    double *out = E + (size_t)b * kNeqN * kNeqN + idx;
     if (use_m || use_n) {
-      const double XM = use_m ? san_gram(s, 1, s.jac[0], s.jac[1], r, c, J) : 0.0;
-      const double XN = use_n ? san_gram(s, 2, s.jac[0], s.jac[1], r, c, J) : 0.0;
+      const double XM = use_m ? neq_gram(s.act[1], s.jac[0], s.jac[1], r, c, J) : 0.0;
+      const double XN = use_n ? neq_gram(s.act[2], s.jac[0], s.jac[1], r, c, J) : 0.0;
       const double mine = (0.0 - (2.0 * wm) * XM) - (2.0 * wn) * XN;
       *out = add_E ? *out + mine : mine;
     } else if (!add_E) {
@@ -118,47 +101,27 @@ sphere_accel_kernel(const float4 *__restrict__ centres, const float *__restrict_
     }
   }
   if (add && !use_p && !use_m && !use_n) return;           // nothing with a weight: A, g and cost are not touched
-  if (tid == kSanThreads - 1) {                            // the prev triple's cost: the spheres' terms ascending
+  if (tid == kNeqThreads - 1) {                            // the prev triple's cost: the spheres' terms ascending
     double C = 0.0;
     if (use_p)
       for (int j = 0; j < J; j++) C += s.term[0][j];
-    const double c = wp * C;
-    if (add) {
-      if (use_p) cost[b] = cost[b] + c;
-    } else {
-      cost[b] = c;
-    }
+    if (!add || use_p) neq_emit_cost(cost, b, wp * C, add);
   }
-  for (int idx = tid; idx < kSanTri + kSanN; idx += kSanThreads) {
+  for (int idx = tid; idx < kNeqTri + kNeqN; idx += kNeqThreads) {
     double P = 0.0, M = 0.0, N = 0.0;
-    if (idx < kSanTri) {
-      int r = 0;
-      while ((r + 1) * (r + 2) / 2 <= idx) r++;
-      const int c = idx - r * (r + 1) / 2;                 // r >= c
-      if (use_p) P = san_gram(s, 0, s.jac[0], s.jac[0], r, c, J);
-      if (use_m) M = san_gram(s, 1, s.jac[0], s.jac[0], r, c, J);
-      if (use_n) N = san_gram(s, 2, s.jac[0], s.jac[0], r, c, J);
-      const double mine = (wp * P + (4.0 * wm) * M) + wn * N;
-      double *low = A + ((size_t)b * kSanN + r) * kSanN + c;
-      const double v = add ? *low + mine : mine;
-      *low = v;
-      A[((size_t)b * kSanN + c) * kSanN + r] = v;
+    if (idx < kNeqTri) {
+      const NeqEntry e = neq_entry(idx);
+      if (use_p) P = neq_gram(s.act[0], s.jac[0], s.jac[0], e.a, e.c, J);
+      if (use_m) M = neq_gram(s.act[1], s.jac[0], s.jac[0], e.a, e.c, J);
+      if (use_n) N = neq_gram(s.act[2], s.jac[0], s.jac[0], e.a, e.c, J);
+      neq_emit_A(A, b, e.a, e.c, (wp * P + (4.0 * wm) * M) + wn * N, add);
     } else {
-      const int r = idx - kSanTri;
-      for (int which = 0; which < 3; which++) {
-        if (!(which == 0 ? use_p : which == 1 ? use_m : use_n)) continue;
-        double acc = 0.0;
-        for (int j = 0; j < J; j++) {
-          if (!s.act[which][j]) continue;
-          const float *q = s.jac[0] + 3 * j * kSanN;
-          const double *a = s.a[which][j];
-          acc += ((double)q[r] * a[0] + (double)q[kSanN + r] * a[1]) + (double)q[2 * kSanN + r] * a[2];
-        }
-        if (which == 0) P = acc; else if (which == 1) M = acc; else N = acc;
-      }
-      const double mine = (wp * P - (2.0 * wm) * M) + wn * N;          // the centre of a triple is pulled against its ends
-      double *out = g + (size_t)b * kSanN + r;
-      *out = add ? *out + mine : mine;
+      const int r = neq_g_entry(idx);
+      if (use_p) P = neq_gram_g(s.act[0], s.jac[0], s.a[0], r, J);
+      if (use_m) M = neq_gram_g(s.act[1], s.jac[0], s.a[1], r, J);
+      if (use_n) N = neq_gram_g(s.act[2], s.jac[0], s.a[2], r, J);
+      // the centre of a triple is pulled against its ends
+      neq_emit_g(g, b, r, (wp * P - (2.0 * wm) * M) + wn * N, add);
     }
   }
 }
@@ -175,18 +138,16 @@ extern "C" long long shr_sphere_accel_normal_workspace_bytes(int B, int T, int J
 extern "C" int shr_sphere_accel_normal(const float *keypoints, const float *jac, const float *triple_weight, float accel_weight,
                                        float acc_max, int B, int T, int J, int accumulate, int accumulate_E, double *A, double *g,
                                        double *E, double *F, double *cost, int32_t *count, void *workspace, void *stream) {
-  const float finite = 3.40282346638528859812e38f;
   if (B < 0 || T < 1 || J < 1 || !(acc_max >= 0.f) || (accumulate != 0 && accumulate != 1)) return SHR_EINVAL;
   if (accumulate_E != 0 && accumulate_E != 1) return SHR_EINVAL;
-  if (!(accel_weight >= 0.f) || !(accel_weight <= finite) || B % T != 0) return SHR_EINVAL;
-  if (B > 65535 || J > kSanMaxJ) return SHR_ETOOLARGE;
+  if (!neq_weight_ok(accel_weight) || B % T != 0) return SHR_EINVAL;
+  if (neq_too_large(B, 1, J)) return SHR_ETOOLARGE;
   if (B == 0) return SHR_OK;
   if (!keypoints || !jac || !A || !g || !E || !F || !cost || !count) return SHR_EINVAL;
-  if ((((uintptr_t)jac | (uintptr_t)triple_weight | (uintptr_t)count) & 3u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)E | (uintptr_t)F | (uintptr_t)cost) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)keypoints | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if (!neq_aligned(4, jac, triple_weight, count) || !neq_aligned(8, A, g, E, F, cost) || !neq_aligned(16, keypoints, workspace))
+    return SHR_EINVAL;
   const double cap = (double)acc_max;
-  hipLaunchKernelGGL(sphere_accel_kernel, dim3((unsigned)B), dim3(kSanThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(sphere_accel_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4 *>(keypoints), jac, triple_weight, (double)accel_weight, cap * cap, T, J,
                      accumulate, accumulate_E, accel_weight > 0.f ? 1 : 0, A, g, E, F, cost, count);
   return (int)hipGetLastError();

@@ -17,7 +17,7 @@
 //             list holds (h, u) and (a, b, rowed); u = 0 where the centres coincide.
 //   add       the list is taken in groups of 64 pairs: the group's rows, 26 entries each, are formed once from the Jacobian
 //             in LDS (one entry per thread and pass), and thread t, which owns entries t, t + 256 of A's 351 lower entries
-//             and g's 26 as sphere_prior_kernel does, adds the group's pairs with rows to them in order: two barriers per
+//             and g's 26 (normal_eq.h's neq_owned), adds the group's pairs with rows to them in order: two barriers per
 //             group, none per pair.  The last thread runs the cost chain.
 //   The Jacobian is staged when the first pair with a row turns up: a sample without one (the common case) never reads it.
 //   LDS banks: a pair's record is read at one address by all lanes (a broadcast).  In the add loop every lane reads
@@ -26,16 +26,12 @@
 //   four pairs (26 entries each): their Jacobian reads fall into up to four rows of 26 consecutive dwords, at most a 4-way
 //   conflict on the 32 banks of a ds_read_b32, in the pass that runs once per pair; the rows are written to consecutive
 //   doubles.
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kScnThreads = 256;
-constexpr int kScnMaxJ = 64;
 constexpr int kScnMaxK = 4096;
-constexpr int kScnN = 26;                                  // pose parameters
-constexpr int kScnTri = kScnN * (kScnN + 1) / 2;           // 351
-constexpr int kScnWaves = kScnThreads / 64;
+constexpr int kScnWaves = kNeqThreads / 64;
 constexpr int kScnGroup = 64;                             // pairs whose rows are held in LDS at a time
 
 struct ScnPair {
@@ -43,28 +39,24 @@ struct ScnPair {
 };
 
 struct ScnLds {
-  ScnPair pair[kScnThreads];                               // the chunk's active pairs, k ascending
-  double row[kScnGroup][kScnN];                            // the rows of a group of the chunk's pairs
-  float jac[kScnMaxJ * 3 * kScnN];
-  float4 centre[kScnMaxJ];
-  int ab[kScnThreads];                                     // a | b << 8 | (the pair has a row) << 16
+  ScnPair pair[kNeqThreads];                               // the chunk's active pairs, k ascending
+  double row[kScnGroup][kNeqN];                            // the rows of a group of the chunk's pairs
+  float jac[kNeqMaxJ * 3 * kNeqN];
+  float4 centre[kNeqMaxJ];
+  int ab[kNeqThreads];                                     // a | b << 8 | (the pair has a row) << 16
   int wave_active[kScnWaves], wave_rows[kScnWaves];
 };
 
-// mode 0: A, g, cost = the term's; 1: they are added to what the buffers hold (A's lower triangle is read and the sum
-// written to both triangles); 2: A, g and cost are left alone (the term is not used on top of the others)
-enum { kScnWrite = 0, kScnAdd = 1, kScnKeep = 2 };
-
 // row_c of a pair = d h / d params_c: 0 - ((u0 D_0c + u1 D_1c) + u2 D_2c), D_ic = jac[3a + i, c] - jac[3b + i, c] in fp64
 __device__ inline double scn_row(const float *jac, int a, int b, int c, double u0, double u1, double u2) {
-  const float *qa = jac + 3 * a * kScnN + c, *qb = jac + 3 * b * kScnN + c;
+  const float *qa = jac + 3 * a * kNeqN + c, *qb = jac + 3 * b * kNeqN + c;
   const double d0 = (double)qa[0] - (double)qb[0];
-  const double d1 = (double)qa[kScnN] - (double)qb[kScnN];
-  const double d2 = (double)qa[2 * kScnN] - (double)qb[2 * kScnN];
+  const double d1 = (double)qa[kNeqN] - (double)qb[kNeqN];
+  const double d2 = (double)qa[2 * kNeqN] - (double)qb[2 * kNeqN];
   return 0.0 - ((u0 * d0 + u1 * d1) + u2 * d2);
 }
 
-__global__ void __launch_bounds__(kScnThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_collision_kernel(const float4 *__restrict__ centres, const float *__restrict__ jac, const int *__restrict__ pair_a,
                         const int *__restrict__ pair_b, const float *__restrict__ pair_min, double w, int J, int K, int mode,
                         int used, double *__restrict__ A, double *__restrict__ g, double *__restrict__ cost,
@@ -73,24 +65,12 @@ sphere_collision_kernel(const float4 *__restrict__ centres, const float *__restr
   const int tid = threadIdx.x, b = blockIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   if (tid < J) s.centre[tid] = centres[(size_t)b * J + tid];
-  // the entries this thread owns: idx0 = tid is one of A's; idx1 = tid + 256 is one of A's, one of g's, or none
-  int a0 = 0;
-  while ((a0 + 1) * (a0 + 2) / 2 <= tid) a0++;
-  const int c0 = tid - a0 * (a0 + 1) / 2;                  // a0 >= c0
-  const int idx1 = tid + kScnThreads;
-  int a1 = a0, c1 = -1;                                    // c1 < 0: no second entry of A
-  if (idx1 < kScnTri) {
-    while ((a1 + 1) * (a1 + 2) / 2 <= idx1) a1++;
-    c1 = idx1 - a1 * (a1 + 1) / 2;
-  } else if (idx1 < kScnTri + kScnN) {
-    a1 = idx1 - kScnTri;                                   // g's entry
-  }
-  const bool own_g = idx1 >= kScnTri && idx1 < kScnTri + kScnN;
+  const NeqOwned own = neq_owned(tid);
   double acc0 = 0.0, acc1 = 0.0, C = 0.0;
   int rows = 0;
   bool staged = false;
   __syncthreads();
-  for (int base = 0; base < K; base += kScnThreads) {
+  for (int base = 0; base < K; base += kNeqThreads) {
     const int k = base + tid;
     bool active = false, rowed = false;
     double h = 0.0, u0 = 0.0, u1 = 0.0, u2 = 0.0;
@@ -142,18 +122,18 @@ sphere_collision_kernel(const float4 *__restrict__ centres, const float *__restr
       s.ab[offset + pos] = pa | (pb << 8) | ((int)rowed << 16);
     }
     if (used && nrows > 0 && !staged) {                    // (uniform: every thread holds the same nrows)
-      for (int idx = tid; idx < 3 * J * kScnN; idx += kScnThreads) s.jac[idx] = jac[(size_t)b * 3 * J * kScnN + idx];
+      for (int idx = tid; idx < 3 * J * kNeqN; idx += kNeqThreads) s.jac[idx] = jac[(size_t)b * 3 * J * kNeqN + idx];
       staged = true;
     }
     __syncthreads();
     if (used) {
-      if (tid == kScnThreads - 1)                          // the cost: the active pairs, k ascending
+      if (tid == kNeqThreads - 1)                          // the cost: the active pairs, k ascending
         for (int i = 0; i < nact; i++) C += s.pair[i].h * s.pair[i].h;
       if (nrows > 0)                                       // (uniform, and so are the barriers inside)
         for (int first = 0; first < nact; first += kScnGroup) {
           const int ng = nact - first < kScnGroup ? nact - first : kScnGroup;
-          for (int idx = tid; idx < ng * kScnN; idx += kScnThreads) {      // the group's rows, every entry once
-            const int i = idx / kScnN, c = idx - i * kScnN;
+          for (int idx = tid; idx < ng * kNeqN; idx += kNeqThreads) {      // the group's rows, every entry once
+            const int i = idx / kNeqN, c = idx - i * kNeqN;
             const int ab = s.ab[first + i];
             double r = 0.0;
             if (ab >> 16) {
@@ -166,9 +146,9 @@ sphere_collision_kernel(const float4 *__restrict__ centres, const float *__restr
           for (int i = 0; i < ng; i++) {
             if (!(s.ab[first + i] >> 16)) continue;        // no row (uniform)
             const double *r = s.row[i];
-            acc0 += r[a0] * r[c0];
-            if (c1 >= 0) acc1 += r[a1] * r[c1];
-            else if (own_g) acc1 += s.pair[first + i].h * r[a1];
+            acc0 += r[own.a0] * r[own.c0];
+            if (own.c1 >= 0) acc1 += r[own.a1] * r[own.c1];
+            else if (own.own_g) acc1 += s.pair[first + i].h * r[own.a1];
           }
           __syncthreads();                                 // the next group rewrites the rows
         }
@@ -176,29 +156,12 @@ sphere_collision_kernel(const float4 *__restrict__ centres, const float *__restr
     __syncthreads();                                       // the next chunk rewrites the list
   }
   if (tid == 0) count[b] = rows;
-  if (mode == kScnKeep) return;
-  if (tid == kScnThreads - 1) {
-    const double c = used ? w * C : 0.0;
-    cost[b] = mode == kScnAdd ? cost[b] + c : c;
-  }
-  {
-    const double mine = used ? w * acc0 : 0.0;
-    double *low = A + ((size_t)b * kScnN + a0) * kScnN + c0;
-    const double v = mode == kScnAdd ? *low + mine : mine;
-    *low = v;
-    A[((size_t)b * kScnN + c0) * kScnN + a0] = v;
-  }
-  if (c1 >= 0) {
-    const double mine = used ? w * acc1 : 0.0;
-    double *low = A + ((size_t)b * kScnN + a1) * kScnN + c1;
-    const double v = mode == kScnAdd ? *low + mine : mine;
-    *low = v;
-    A[((size_t)b * kScnN + c1) * kScnN + a1] = v;
-  } else if (own_g) {
-    const double mine = used ? w * acc1 : 0.0;
-    double *out = g + (size_t)b * kScnN + a1;
-    *out = mode == kScnAdd ? *out + mine : mine;
-  }
+  if (mode == kNeqKeep) return;
+  const bool add = mode == kNeqAdd;
+  if (tid == kNeqThreads - 1) neq_emit_cost(cost, b, used ? w * C : 0.0, add);
+  neq_emit_A(A, b, own.a0, own.c0, used ? w * acc0 : 0.0, add);
+  if (own.c1 >= 0) neq_emit_A(A, b, own.a1, own.c1, used ? w * acc1 : 0.0, add);
+  else if (own.own_g) neq_emit_g(g, b, own.a1, used ? w * acc1 : 0.0, add);
 }
 
 }  // namespace shr
@@ -214,21 +177,19 @@ extern "C" int shr_sphere_collision_normal(const float *centres, const float *ja
                                            const float *pair_min, float weight, int B, int J, int K, int accumulate, double *A,
                                            double *g, double *cost, int32_t *count, double *penetration, void *workspace,
                                            void *stream) {
-  const float finite = 3.40282346638528859812e38f;
   if (B < 0 || J < 1 || K < 0 || (accumulate != 0 && accumulate != 1)) return SHR_EINVAL;
-  if (!(weight >= 0.f) || !(weight <= finite)) return SHR_EINVAL;
+  if (!neq_weight_ok(weight)) return SHR_EINVAL;
   if ((pair_a == nullptr) != (pair_b == nullptr) || (pair_a == nullptr) != (pair_min == nullptr)) return SHR_EINVAL;
   if (K > 0 && !pair_a) return SHR_EINVAL;
-  if (B > 65535 || J > kScnMaxJ || K > kScnMaxK) return SHR_ETOOLARGE;
+  if (neq_too_large(B, 1, J) || K > kScnMaxK) return SHR_ETOOLARGE;
   if (B == 0) return SHR_OK;
   if (!centres || !jac || !A || !g || !cost || !count) return SHR_EINVAL;
-  if ((((uintptr_t)jac | (uintptr_t)pair_a | (uintptr_t)pair_b | (uintptr_t)pair_min | (uintptr_t)count) & 3u) != 0)
+  if (!neq_aligned(4, jac, pair_a, pair_b, pair_min, count) || !neq_aligned(8, A, g, cost, penetration) ||
+      !neq_aligned(16, centres, workspace))
     return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost | (uintptr_t)penetration) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)centres | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   const int used = pair_a && K > 0 && weight > 0.f;
-  const int mode = !accumulate ? kScnWrite : (used ? kScnAdd : kScnKeep);
-  hipLaunchKernelGGL(sphere_collision_kernel, dim3((unsigned)B), dim3(kScnThreads), 0, (hipStream_t)stream,
+  const int mode = !accumulate ? kNeqWrite : (used ? kNeqAdd : kNeqKeep);
+  hipLaunchKernelGGL(sphere_collision_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4 *>(centres), jac, pair_a, pair_b, pair_min, (double)weight, J,
                      pair_a ? K : 0, mode, used, A, g, cost, count, penetration);
   return (int)hipGetLastError();

@@ -15,7 +15,7 @@ namespace shr {
 
 constexpr int kSicpMom = 12;                               // doubles per sphere: the layout of `moments`
 
-__global__ void __launch_bounds__(kSicpThreads, 4)
+__global__ void __launch_bounds__(kNeqThreads, 4)
 sphere_icp_scan_kernel(const float *__restrict__ observed, const float4 *__restrict__ centres, const float *__restrict__ radii,
                        const float *__restrict__ view, int J, int W, int H, float ax, float bx, float ay, float by, float fg_max,
                        float max_dist, double *__restrict__ part, float *__restrict__ dist, int *__restrict__ owner) {
@@ -23,7 +23,7 @@ sphere_icp_scan_kernel(const float *__restrict__ observed, const float4 *__restr
   sicp_scan_body<kSicpMom>(s, observed, centres, radii, view, J, W, H, ax, bx, ay, by, fg_max, max_dist, part, dist, owner);
 }
 
-__global__ void __launch_bounds__(kSicpThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_icp_assemble_kernel(const double *__restrict__ part, const float *__restrict__ jac, int J, int records,
                            double *__restrict__ A, double *__restrict__ g, double *__restrict__ cost, int *__restrict__ count,
                            double *__restrict__ moments) {
@@ -47,18 +47,16 @@ extern "C" int shr_sphere_icp_normal(const float *observed, const float *view_ce
   if (int rc = sicp_check(B, V, J, W, H, max_dist)) return rc;
   if (B == 0) return SHR_OK;
   if (!observed || !view_centres || !radii || !view || !jac || !A || !g || !cost || !count || !workspace) return SHR_EINVAL;
-  if ((((uintptr_t)observed | (uintptr_t)radii | (uintptr_t)view | (uintptr_t)jac | (uintptr_t)count | (uintptr_t)dist |
-        (uintptr_t)owner) & 3u) != 0)
+  if (!neq_aligned(4, observed, radii, view, jac, count, dist, owner) || !neq_aligned(8, A, g, cost, moments) ||
+      !neq_aligned(16, view_centres, workspace))
     return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost | (uintptr_t)moments) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)view_centres | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int tiles = (int)sicp_tiles(W, H);
   double *part = reinterpret_cast<double *>(workspace);
-  hipLaunchKernelGGL(sphere_icp_scan_kernel, dim3((unsigned)tiles, (unsigned)V, (unsigned)B), dim3(kSicpThreads), 0, s, observed,
+  hipLaunchKernelGGL(sphere_icp_scan_kernel, dim3((unsigned)tiles, (unsigned)V, (unsigned)B), dim3(kNeqThreads), 0, s, observed,
                      reinterpret_cast<const float4 *>(view_centres), radii, view, J, W, H, ax, bx, ay, by, fg_max, max_dist, part,
                      dist, owner);
-  hipLaunchKernelGGL(sphere_icp_assemble_kernel, dim3((unsigned)B), dim3(kSicpThreads), 0, s, part, jac, J, V * tiles, A, g, cost,
+  hipLaunchKernelGGL(sphere_icp_assemble_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, s, part, jac, J, V * tiles, A, g, cost,
                      count, moments);
   return (int)hipGetLastError();
 }

@@ -31,7 +31,7 @@ __device__ __forceinline__ bool srad_void(const float *__restrict__ radii, int J
   return bad;
 }
 
-__global__ void __launch_bounds__(kSicpThreads, 4)
+__global__ void __launch_bounds__(kNeqThreads, 4)
 sphere_icp_radii_scan_kernel(const float *__restrict__ observed, const float4 *__restrict__ centres,
                              const float *__restrict__ radii, const float *__restrict__ view, int J, int N, int W, int H, float ax,
                              float bx, float ay, float by, float fg_max, float max_dist, double *__restrict__ part,
@@ -41,7 +41,7 @@ sphere_icp_radii_scan_kernel(const float *__restrict__ observed, const float4 *_
                            max_dist, part, dist, owner);
 }
 
-__global__ void __launch_bounds__(kSicpThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_icp_radii_assemble_kernel(const double *__restrict__ part, const float *__restrict__ jac,
                                  const float *__restrict__ radii, int J, int N, int records, double *__restrict__ A,
                                  double *__restrict__ g, double *__restrict__ cost, int *__restrict__ count,
@@ -51,14 +51,14 @@ sphere_icp_radii_assemble_kernel(const double *__restrict__ part, const float *_
   const bool void_all = srad_void(radii + (size_t)(b / N) * J, J);
   sicp_assemble_body<kSradMom>(s, part, jac, J, records, void_all, A, g, cost, count, moments);
   // (the body's barrier stands between the moments and the Jacobian in LDS and these reads)
-  for (int idx = tid; idx < kSicpN * J; idx += kSicpThreads) {
+  for (int idx = tid; idx < kNeqN * J; idx += kNeqThreads) {
     const int a = idx / J, j = idx - a * J;
     const double *m = s.mom + j * kSradMom;
-    const float *q = s.jac + 3 * j * kSicpN;
+    const float *q = s.jac + 3 * j * kNeqN;
     double v = 0.0;                                        // a sphere without a row: an exact +0
     if (m[10] != 0.0 && !void_all)
-      v = ((double)q[a] * m[12] + (double)q[kSicpN + a] * m[13]) + (double)q[2 * kSicpN + a] * m[14];
-    C[(size_t)b * kSicpN * J + idx] = v;
+      v = ((double)q[a] * m[12] + (double)q[kNeqN + a] * m[13]) + (double)q[2 * kNeqN + a] * m[14];
+    C[(size_t)b * kNeqN * J + idx] = v;
   }
   if (tid < J) {
     sums[((size_t)b * J + tid) * 2] = s.mom[tid * kSradMom + 10];
@@ -106,20 +106,17 @@ extern "C" int shr_sphere_icp_radii_normal(const float *observed, const float *v
   if (B == 0) return SHR_OK;
   if (!observed || !view_centres || !radii || !view || !jac || !A || !g || !cost || !count || !C || !R || !gs || !workspace)
     return SHR_EINVAL;
-  if ((((uintptr_t)observed | (uintptr_t)radii | (uintptr_t)view | (uintptr_t)jac | (uintptr_t)count | (uintptr_t)dist |
-        (uintptr_t)owner) & 3u) != 0)
+  if (!neq_aligned(4, observed, radii, view, jac, count, dist, owner) || !neq_aligned(8, A, g, cost, C, R, gs, moments) ||
+      !neq_aligned(16, view_centres, workspace))
     return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost | (uintptr_t)C | (uintptr_t)R | (uintptr_t)gs | (uintptr_t)moments) & 7u) != 0)
-    return SHR_EINVAL;
-  if ((((uintptr_t)view_centres | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int tiles = (int)sicp_tiles(W, H);
   double *part = reinterpret_cast<double *>(workspace);
   double *sums = part + srad_part_doubles(B, V, J, W, H);
-  hipLaunchKernelGGL(sphere_icp_radii_scan_kernel, dim3((unsigned)tiles, (unsigned)V, (unsigned)B), dim3(kSicpThreads), 0, s,
+  hipLaunchKernelGGL(sphere_icp_radii_scan_kernel, dim3((unsigned)tiles, (unsigned)V, (unsigned)B), dim3(kNeqThreads), 0, s,
                      observed, reinterpret_cast<const float4 *>(view_centres), radii, view, J, N, W, H, ax, bx, ay, by, fg_max,
                      max_dist, part, dist, owner);
-  hipLaunchKernelGGL(sphere_icp_radii_assemble_kernel, dim3((unsigned)B), dim3(kSicpThreads), 0, s, part, jac, radii, J, N,
+  hipLaunchKernelGGL(sphere_icp_radii_assemble_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, s, part, jac, radii, J, N,
                      V * tiles, A, g, cost, count, moments, C, sums);
   hipLaunchKernelGGL(sphere_icp_radii_group_kernel, dim3((unsigned)(B / N)), dim3(kWave), 0, s, sums, radii, J, N, R, gs);
   return (int)hipGetLastError();

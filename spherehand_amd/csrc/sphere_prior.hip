@@ -17,36 +17,28 @@
 //             Slot 10 counts the pairs with rows; slot 11, the record's spare, carries the sphere's cost chain sum_v w t
 //             in LDS and is written as 0.  The moments are written contiguously (thread t to double t: no bank
 //             conflict) and read as broadcasts, so the record needs no odd stride here.
-//   phase 2   thread t owns entries t, t + 256 of A's 351 lower entries and g's 26, spheres ascending, as
-//             sphere_icp_assemble_kernel does.
+//   phase 2   thread t owns entries t, t + 256 of A's 351 lower entries and g's 26 and sums normal_eq.h's chains of the
+//             moments, spheres ascending.
 //   phase 3   the owner of a diagonal entry (and of g_i) adds the limit term of parameter i; then weight and accumulate.
 //             The last thread runs the cost: the spheres' chains ascending, then the limits.
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kSpnThreads = 256;
-constexpr int kSpnMaxJ = 64;
 constexpr int kSpnMom = 12;                                // doubles per sphere: the layout of `moments`
-constexpr int kSpnN = 26;                                  // pose parameters
-constexpr int kSpnTri = kSpnN * (kSpnN + 1) / 2;           // 351
 
 struct SpnLds {
-  double mom[kSpnMaxJ * kSpnMom];
-  float jac[kSpnMaxJ * 3 * kSpnN];
-  double h[kSpnN];                                         // the limit term's h_i (0: no row)
+  double mom[kNeqMaxJ * kSpnMom];
+  float jac[kNeqMaxJ * 3 * kNeqN];
+  double h[kNeqN];                                         // the limit term's h_i (0: no row)
 };
-
-// mode 0: A, g, cost = the terms'; 1: they are added to what the buffers hold (A's lower triangle is read and the sum
-// written to both triangles); 2: A, g and cost are left alone (no term with a weight on top of the others)
-enum { kSpnWrite = 0, kSpnAdd = 1, kSpnKeep = 2 };
 
 // h_i of the limit term: fp64 from the fp32 values; a comparison with a NaN never fires, a value ON a bound gives 0
 __device__ inline double spn_hinge(float p, float lo, float hi) {
   return p > hi ? (double)p - (double)hi : (p < lo ? (double)p - (double)lo : 0.0);
 }
 
-__global__ void __launch_bounds__(kSpnThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_prior_kernel(const float4 *__restrict__ centres, const float *__restrict__ view, const float *__restrict__ jac,
                     const float *__restrict__ params, const float *__restrict__ keypoints,
                     const float *__restrict__ confidence, const float *__restrict__ lower, const float *__restrict__ upper,
@@ -56,12 +48,12 @@ sphere_prior_kernel(const float4 *__restrict__ centres, const float *__restrict_
   __shared__ SpnLds s;
   const int tid = threadIdx.x, b = blockIdx.x;
   const int nmom = kSpnMom * J;
-  const bool use_kp = use & 1, use_lim = use & 2;
-  if (tid < kSpnN) s.h[tid] = lower ? spn_hinge(params[b * kSpnN + tid], lower[tid], upper[tid]) : 0.0;
+  const bool use_kp = use & 1, use_lim = use & 2, add = mode == kNeqAdd;
+  if (tid < kNeqN) s.h[tid] = lower ? spn_hinge(params[b * kNeqN + tid], lower[tid], upper[tid]) : 0.0;
   if (use_kp)
-    for (int idx = tid; idx < 3 * J * kSpnN; idx += kSpnThreads) s.jac[idx] = jac[(size_t)b * 3 * J * kSpnN + idx];
+    for (int idx = tid; idx < 3 * J * kNeqN; idx += kNeqThreads) s.jac[idx] = jac[(size_t)b * 3 * J * kNeqN + idx];
   // phase 1: the chains of (sphere, moment) over the views
-  for (int idx = tid; idx < nmom; idx += kSpnThreads) {
+  for (int idx = tid; idx < nmom; idx += kNeqThreads) {
     const int j = idx / kSpnMom, m = idx - j * kSpnMom;
     double acc = 0.0;
     if (keypoints) {
@@ -106,11 +98,11 @@ sphere_prior_kernel(const float4 *__restrict__ centres, const float *__restrict_
   }
   if (tid == 1) {
     int rows = 0;
-    for (int i = 0; i < kSpnN; i++) rows += s.h[i] != 0.0;
+    for (int i = 0; i < kNeqN; i++) rows += s.h[i] != 0.0;
     count[2 * b + 1] = rows;
   }
-  if (mode == kSpnKeep) return;
-  if (tid == kSpnThreads - 1) {                            // the cost: the spheres' chains ascending, then the limits
+  if (mode == kNeqKeep) return;
+  if (tid == kNeqThreads - 1) {                            // the cost: the spheres' chains ascending, then the limits
     double kp_part = 0.0, lim_part = 0.0;
     if (use_kp) {
       double K = 0.0;
@@ -119,50 +111,24 @@ sphere_prior_kernel(const float4 *__restrict__ centres, const float *__restrict_
     }
     if (use_lim) {
       double L = 0.0;
-      for (int i = 0; i < kSpnN; i++) L += s.h[i] * s.h[i];
+      for (int i = 0; i < kNeqN; i++) L += s.h[i] * s.h[i];
       lim_part = lw * L;
     }
-    const double c = kp_part + lim_part;
-    cost[b] = mode == kSpnAdd ? cost[b] + c : c;
+    neq_emit_cost(cost, b, kp_part + lim_part, add);
   }
   // phases 2 and 3: A's lower triangle and g from the moments and the Jacobian, the limit term on the diagonal
-  for (int idx = tid; idx < kSpnTri + kSpnN; idx += kSpnThreads) {
-    double acc = 0.0;
-    if (idx < kSpnTri) {
-      int a = 0;
-      while ((a + 1) * (a + 2) / 2 <= idx) a++;
-      const int c = idx - a * (a + 1) / 2;                 // a >= c
-      if (use_kp)
-        for (int j = 0; j < J; j++) {
-          const double *m = s.mom + j * kSpnMom;
-          if (m[10] == 0.0) continue;                      // a sphere without a row adds nothing
-          const float *q = s.jac + 3 * j * kSpnN;
-          const double c0 = (double)q[c], c1 = (double)q[kSpnN + c], c2 = (double)q[2 * kSpnN + c];
-          const double t0 = (m[0] * c0 + m[1] * c1) + m[2] * c2;
-          const double t1 = (m[1] * c0 + m[3] * c1) + m[4] * c2;
-          const double t2 = (m[2] * c0 + m[4] * c1) + m[5] * c2;
-          acc += ((double)q[a] * t0 + (double)q[kSpnN + a] * t1) + (double)q[2 * kSpnN + a] * t2;
-        }
-      double lim = 0.0;
-      if (use_lim && a == c && s.h[a] != 0.0) lim = lw;
-      const double mine = (use_kp ? kw * acc : 0.0) + lim;
-      double *low = A + ((size_t)b * kSpnN + a) * kSpnN + c;
-      const double v = mode == kSpnAdd ? *low + mine : mine;
-      *low = v;
-      A[((size_t)b * kSpnN + c) * kSpnN + a] = v;
+  for (int idx = tid; idx < kNeqTri + kNeqN; idx += kNeqThreads) {
+    double acc = 0.0, lim = 0.0;
+    if (idx < kNeqTri) {
+      const NeqEntry e = neq_entry(idx);
+      if (use_kp) acc = neq_moments_A<kSpnMom>(s.mom, s.jac, J, e.a, e.c);
+      if (use_lim && e.a == e.c && s.h[e.a] != 0.0) lim = lw;
+      neq_emit_A(A, b, e.a, e.c, (use_kp ? kw * acc : 0.0) + lim, add);
     } else {
-      const int a = idx - kSpnTri;
-      if (use_kp)
-        for (int j = 0; j < J; j++) {
-          const double *m = s.mom + j * kSpnMom;
-          if (m[10] == 0.0) continue;
-          const float *q = s.jac + 3 * j * kSpnN;
-          acc += ((double)q[a] * m[6] + (double)q[kSpnN + a] * m[7]) + (double)q[2 * kSpnN + a] * m[8];
-        }
-      double lim = 0.0;
+      const int a = neq_g_entry(idx);
+      if (use_kp) acc = neq_moments_g<kSpnMom>(s.mom, s.jac, J, a);
       if (use_lim && s.h[a] != 0.0) lim = lw * s.h[a];
-      const double mine = (use_kp ? kw * (0.0 - acc) : 0.0) + lim;
-      g[(size_t)b * kSpnN + a] = mode == kSpnAdd ? g[(size_t)b * kSpnN + a] + mine : mine;
+      neq_emit_g(g, b, a, (use_kp ? kw * (0.0 - acc) : 0.0) + lim, add);
     }
   }
 }
@@ -181,22 +147,19 @@ extern "C" int shr_sphere_prior_normal(const float *view_centres, const float *v
                                        const float *lower, const float *upper, float limit_weight, int B, int V, int J,
                                        int accumulate, double *A, double *g, double *cost, int32_t *count, double *moments,
                                        void *workspace, void *stream) {
-  const float finite = 3.40282346638528859812e38f;
   if (B < 0 || V < 1 || J < 1 || !(kp_max >= 0.f) || (accumulate != 0 && accumulate != 1)) return SHR_EINVAL;
-  if (!(kp_weight >= 0.f) || !(kp_weight <= finite) || !(limit_weight >= 0.f) || !(limit_weight <= finite)) return SHR_EINVAL;
+  if (!neq_weight_ok(kp_weight) || !neq_weight_ok(limit_weight)) return SHR_EINVAL;
   if ((lower == nullptr) != (upper == nullptr) || (confidence && !keypoints)) return SHR_EINVAL;
-  if (B > 65535 || (long long)B * V > 65535 || J > kSpnMaxJ) return SHR_ETOOLARGE;
+  if (neq_too_large(B, V, J)) return SHR_ETOOLARGE;
   if (B == 0) return SHR_OK;
   if (!view_centres || !view || !jac || !params || !A || !g || !cost || !count) return SHR_EINVAL;
-  if ((((uintptr_t)view | (uintptr_t)jac | (uintptr_t)params | (uintptr_t)keypoints | (uintptr_t)confidence |
-        (uintptr_t)lower | (uintptr_t)upper | (uintptr_t)count) & 3u) != 0)
+  if (!neq_aligned(4, view, jac, params, keypoints, confidence, lower, upper, count) || !neq_aligned(8, A, g, cost, moments) ||
+      !neq_aligned(16, view_centres, workspace))
     return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)cost | (uintptr_t)moments) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)view_centres | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
   const int use_kp = keypoints && kp_weight > 0.f, use_lim = lower && limit_weight > 0.f;
-  const int mode = !accumulate ? kSpnWrite : ((use_kp || use_lim) ? kSpnAdd : kSpnKeep);
+  const int mode = !accumulate ? kNeqWrite : ((use_kp || use_lim) ? kNeqAdd : kNeqKeep);
   const double cap = (double)kp_max;
-  hipLaunchKernelGGL(sphere_prior_kernel, dim3((unsigned)B), dim3(kSpnThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(sphere_prior_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4 *>(view_centres), view, jac, params, keypoints, confidence, lower, upper,
                      (double)kp_weight, cap * cap, (double)limit_weight, V, J, mode, use_kp | (use_lim << 1), A, g, cost, count,
                      moments);

@@ -15,36 +15,29 @@
 //   (2 x 19 968 bytes at the unit's J = 64) beside both pairs' e, cost terms and flags: 44 544 bytes.
 //   decide    thread j < J decides (prev, j), thread 64 + j decides (next, j): e in fp64 from the fp32 centres, n2, the
 //             cost term min(n2, cap2) and whether the sphere has rows (n2 < cap2; a NaN n2: no term at all).
-//   add       thread t owns entries t, t + 256 of A's 351 lower entries and g's 26, as sphere_prior_kernel does, and entries
-//             t, t + 256, t + 512 of E's 676: chains from 0 over the spheres with rows, ascending, a sphere's three axes
-//             summed first.  The last thread runs prev's cost chain: the pair's cost is stored with frame t + 1.
+//   add       thread t owns entries t, t + 256 of A's 351 lower entries and g's 26 (normal_eq.h's entry map), and entries
+//             t, t + 256, t + 512 of E's 676: normal_eq.h's chains from 0 over the spheres with rows, ascending, a sphere's
+//             three axes summed first.  The last thread runs prev's cost chain: the pair's cost is stored with frame t + 1.
 //   A frame reads its neighbours' inputs and writes only its own outputs: every entry has one owner thread, and a
 //   sequence does not see the other sequences of the batch.
 //   LDS banks: in the add loops a wave's lanes read jac[3j + axis][a] and [c] of ONE sphere: 26 consecutive dwords, distinct
 //   entries in distinct banks, equal entries one address; e, term and act are read at one address by all lanes.
-#include "common.h"
+#include "normal_eq.h"
 
 namespace shr {
 
-constexpr int kStnThreads = 256;
-constexpr int kStnMaxJ = 64;
-constexpr int kStnN = 26;                                  // pose parameters
-constexpr int kStnTri = kStnN * (kStnN + 1) / 2;           // 351
-
 struct StnLds {
-  float jac[2][kStnMaxJ * 3 * kStnN];                      // frame b's, frame b + 1's
-  double e[2][kStnMaxJ][3];                                // prev: c(b) - c(b - 1); next: c(b + 1) - c(b)
-  double term[2][kStnMaxJ];                                // min(n2, cap2); 0 where the sphere has no term
-  int act[2][kStnMaxJ];                                    // the sphere has rows
+  float jac[2][kNeqMaxJ * 3 * kNeqN];                      // frame b's, frame b + 1's
+  double e[2][kNeqMaxJ][3];                                // prev: c(b) - c(b - 1); next: c(b + 1) - c(b)
+  double term[2][kNeqMaxJ];                                // min(n2, cap2); 0 where the sphere has no term
+  int act[2][kNeqMaxJ];                                    // the sphere has rows
 };
 
-// mode 0: A, g, cost = the term's; 1: they are added to what the buffers hold (A's lower triangle is read and the sum
-// written to both triangles); a frame none of whose pairs carries a weight is left alone
-enum { kStnWrite = 0, kStnAdd = 1 };
+// add: A, g and cost are added to what the buffers hold, and a frame none of whose pairs carries a weight is left alone
 
-__global__ void __launch_bounds__(kStnThreads)
+__global__ void __launch_bounds__(kNeqThreads)
 sphere_temporal_kernel(const float4 *__restrict__ centres, const float *__restrict__ jac, const float *__restrict__ frame_weight,
-                       double tw, double cap2, int T, int J, int mode, int used, double *__restrict__ A, double *__restrict__ g,
+                       double tw, double cap2, int T, int J, int add, int used, double *__restrict__ A, double *__restrict__ g,
                        double *__restrict__ E, double *__restrict__ cost, int *__restrict__ count) {
   __shared__ StnLds s;
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -55,11 +48,11 @@ sphere_temporal_kernel(const float4 *__restrict__ centres, const float *__restri
   const bool live_p = fwp > 0.f, live_n = fwn > 0.f;       // (a NaN weight: no term)
   const bool use_p = used && live_p, use_n = used && live_n;
   const double wp = use_p ? tw * (double)fwp : 0.0, wn = use_n ? tw * (double)fwn : 0.0;
-  const size_t jsize = (size_t)3 * J * kStnN;
+  const size_t jsize = (size_t)3 * J * kNeqN;
   if (use_p || use_n)
-    for (int idx = tid; idx < 3 * J * kStnN; idx += kStnThreads) s.jac[0][idx] = jac[(size_t)b * jsize + idx];
+    for (int idx = tid; idx < 3 * J * kNeqN; idx += kNeqThreads) s.jac[0][idx] = jac[(size_t)b * jsize + idx];
   if (use_n)
-    for (int idx = tid; idx < 3 * J * kStnN; idx += kStnThreads) s.jac[1][idx] = jac[(size_t)(b + 1) * jsize + idx];
+    for (int idx = tid; idx < 3 * J * kNeqN; idx += kNeqThreads) s.jac[1][idx] = jac[(size_t)(b + 1) * jsize + idx];
   if (tid < 2 * 64) {                                      // decide: wave 0 the prev pair, wave 1 the next pair
     const int which = tid >> 6, j = tid & 63;
     if (j < J) {
@@ -91,71 +84,30 @@ sphere_temporal_kernel(const float4 *__restrict__ centres, const float *__restri
     count[b] = rows;
   }
   // E: always written; +0 where the frame has no weighted next pair
-  for (int idx = tid; idx < kStnN * kStnN; idx += kStnThreads) {
-    double out = 0.0;
-    if (use_n) {
-      const int r = idx / kStnN, c = idx - r * kStnN;
-      double acc = 0.0;
-      for (int j = 0; j < J; j++) {
-        if (!s.act[1][j]) continue;
-        const float *q0 = s.jac[0] + 3 * j * kStnN + r, *q1 = s.jac[1] + 3 * j * kStnN + c;
-        acc += ((double)q0[0] * (double)q1[0] + (double)q0[kStnN] * (double)q1[kStnN]) +
-               (double)q0[2 * kStnN] * (double)q1[2 * kStnN];
-      }
-      out = 0.0 - wn * acc;
-    }
-    E[(size_t)b * kStnN * kStnN + idx] = out;
+  for (int idx = tid; idx < kNeqN * kNeqN; idx += kNeqThreads) {
+    const int r = idx / kNeqN, c = idx - r * kNeqN;
+    E[(size_t)b * kNeqN * kNeqN + idx] = use_n ? 0.0 - wn * neq_gram(s.act[1], s.jac[0], s.jac[1], r, c, J) : 0.0;
   }
-  if (mode == kStnAdd && !use_p && !use_n) return;         // nothing with a weight: A, g and cost are not touched
-  if (tid == kStnThreads - 1) {                            // the prev pair's cost: the spheres' terms ascending
+  if (add && !use_p && !use_n) return;         // nothing with a weight: A, g and cost are not touched
+  if (tid == kNeqThreads - 1) {                            // the prev pair's cost: the spheres' terms ascending
     double C = 0.0;
     if (use_p)
       for (int j = 0; j < J; j++) C += s.term[0][j];
-    const double c = wp * C;
-    if (mode == kStnAdd) {
-      if (use_p) cost[b] = cost[b] + c;
-    } else {
-      cost[b] = c;
-    }
+    if (!add || use_p) neq_emit_cost(cost, b, wp * C, add);
   }
-  for (int idx = tid; idx < kStnTri + kStnN; idx += kStnThreads) {
+  for (int idx = tid; idx < kNeqTri + kNeqN; idx += kNeqThreads) {
     double P = 0.0, N = 0.0;
-    if (idx < kStnTri) {
-      int a = 0;
-      while ((a + 1) * (a + 2) / 2 <= idx) a++;
-      const int c = idx - a * (a + 1) / 2;                 // a >= c
-      for (int which = 0; which < 2; which++) {
-        if (!(which == 0 ? use_p : use_n)) continue;
-        double acc = 0.0;
-        for (int j = 0; j < J; j++) {
-          if (!s.act[which][j]) continue;                  // a sphere without rows adds nothing
-          const float *q = s.jac[0] + 3 * j * kStnN;
-          acc += ((double)q[a] * (double)q[c] + (double)q[kStnN + a] * (double)q[kStnN + c]) +
-                 (double)q[2 * kStnN + a] * (double)q[2 * kStnN + c];
-        }
-        if (which == 0) P = acc; else N = acc;
-      }
-      const double mine = wp * P + wn * N;
-      double *low = A + ((size_t)b * kStnN + a) * kStnN + c;
-      const double v = mode == kStnAdd ? *low + mine : mine;
-      *low = v;
-      A[((size_t)b * kStnN + c) * kStnN + a] = v;
+    if (idx < kNeqTri) {
+      const NeqEntry e = neq_entry(idx);
+      if (use_p) P = neq_gram(s.act[0], s.jac[0], s.jac[0], e.a, e.c, J);
+      if (use_n) N = neq_gram(s.act[1], s.jac[0], s.jac[0], e.a, e.c, J);
+      neq_emit_A(A, b, e.a, e.c, wp * P + wn * N, add);
     } else {
-      const int a = idx - kStnTri;
-      for (int which = 0; which < 2; which++) {
-        if (!(which == 0 ? use_p : use_n)) continue;
-        double acc = 0.0;
-        for (int j = 0; j < J; j++) {
-          if (!s.act[which][j]) continue;
-          const float *q = s.jac[0] + 3 * j * kStnN;
-          const double *e = s.e[which][j];
-          acc += ((double)q[a] * e[0] + (double)q[kStnN + a] * e[1]) + (double)q[2 * kStnN + a] * e[2];
-        }
-        if (which == 0) P = acc; else N = acc;
-      }
-      const double mine = wp * P + wn * (0.0 - N);         // the later frame of a pair is pulled back, the earlier one forward
-      double *out = g + (size_t)b * kStnN + a;
-      *out = mode == kStnAdd ? *out + mine : mine;
+      const int a = neq_g_entry(idx);
+      if (use_p) P = neq_gram_g(s.act[0], s.jac[0], s.e[0], a, J);
+      if (use_n) N = neq_gram_g(s.act[1], s.jac[0], s.e[1], a, J);
+      // the later frame of a pair is pulled back, the earlier one forward
+      neq_emit_g(g, b, a, wp * P + wn * (0.0 - N), add);
     }
   }
 }
@@ -172,18 +124,16 @@ extern "C" long long shr_sphere_temporal_normal_workspace_bytes(int B, int T, in
 extern "C" int shr_sphere_temporal_normal(const float *keypoints, const float *jac, const float *frame_weight,
                                           float temporal_weight, float ts_max, int B, int T, int J, int accumulate, double *A,
                                           double *g, double *E, double *cost, int32_t *count, void *workspace, void *stream) {
-  const float finite = 3.40282346638528859812e38f;
   if (B < 0 || T < 1 || J < 1 || !(ts_max >= 0.f) || (accumulate != 0 && accumulate != 1)) return SHR_EINVAL;
-  if (!(temporal_weight >= 0.f) || !(temporal_weight <= finite) || B % T != 0) return SHR_EINVAL;
-  if (B > 65535 || J > kStnMaxJ) return SHR_ETOOLARGE;
+  if (!neq_weight_ok(temporal_weight) || B % T != 0) return SHR_EINVAL;
+  if (neq_too_large(B, 1, J)) return SHR_ETOOLARGE;
   if (B == 0) return SHR_OK;
   if (!keypoints || !jac || !A || !g || !E || !cost || !count) return SHR_EINVAL;
-  if ((((uintptr_t)jac | (uintptr_t)frame_weight | (uintptr_t)count) & 3u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)A | (uintptr_t)g | (uintptr_t)E | (uintptr_t)cost) & 7u) != 0) return SHR_EINVAL;
-  if ((((uintptr_t)keypoints | (uintptr_t)workspace) & 15u) != 0) return SHR_EINVAL;
+  if (!neq_aligned(4, jac, frame_weight, count) || !neq_aligned(8, A, g, E, cost) || !neq_aligned(16, keypoints, workspace))
+    return SHR_EINVAL;
   const double cap = (double)ts_max;
-  hipLaunchKernelGGL(sphere_temporal_kernel, dim3((unsigned)B), dim3(kStnThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(sphere_temporal_kernel, dim3((unsigned)B), dim3(kNeqThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4 *>(keypoints), jac, frame_weight, (double)temporal_weight, cap * cap, T, J,
-                     accumulate ? kStnAdd : kStnWrite, temporal_weight > 0.f ? 1 : 0, A, g, E, cost, count);
+                     accumulate, temporal_weight > 0.f ? 1 : 0, A, g, E, cost, count);
   return (int)hipGetLastError();
 }

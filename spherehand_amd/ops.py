@@ -2247,6 +2247,32 @@ def pose_icp_views(observed, view, params0, faces, offset, offset_inv, skin_vert
     return params, cost0, cost
 
 
+def _weight_arg(value, name):
+    """A term's weight as a float: finite and >= 0."""
+    value = float(value)
+    if not (value >= 0.0 and value < float("inf")):
+        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, value))
+    return value
+
+
+def _new_normal(B, dev):
+    """(A [B,26,26], g [B,26], cost [B]) fp64, uninitialised: what a *_normal entry writes."""
+    return (torch.empty((B, 26, 26), dtype=torch.float64, device=dev), torch.empty((B, 26), dtype=torch.float64, device=dev),
+            torch.empty((B,), dtype=torch.float64, device=dev))
+
+
+def _accumulate_args(accumulate_into, B, dev, where="the parameters' device"):
+    """accumulate_into = (A, g, cost) of the other terms, checked; None: new buffers (call under _on(dev))."""
+    if accumulate_into is None:
+        return None
+    A, g, cost = accumulate_into
+    for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
+        _check_input(t, name, torch.float64)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError("accumulate_into's %s must be %s fp64 on %s" % (name, shape, where))
+    return A, g, cost
+
+
 def _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, radii, pixel_to_model, max_dist, name="parameters"):
     B, V, H, W = _icp_views_args(observed, view)
     Bp, J = _ik_tables(params, offset, offset_inv, bone, wv, name)
@@ -2282,9 +2308,7 @@ def sphere_icp_normal(observed, view, params, offset, offset_inv, bone, wv, radi
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
         centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
-        A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-        g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-        cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = _new_normal(B, dev)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
         dist = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
@@ -2306,37 +2330,8 @@ def sphere_icp(observed, view, params0, offset, offset_inv, bone, wv, radii, rig
     model frame to view v's.  Each of the iters + 1 evaluations is shr_pose_keypoints_jacobian -> shr_view_vertices_fwd
     (NV := J) -> shr_sphere_icp_normal -> shr_pose_lm_step on torch's current stream, into buffers allocated once before
     the loop; nothing returns to the host: capturable in a graph.  iters = 0 returns params0 and cost = cost0."""
-    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
-                                                    max_dist, "start parameters")
-    iters = int(iters)
-    if iters < 0:
-        raise RuntimeError("iters must be >= 0")
-    dev = observed.device
-    state, trial = pose_lm_begin(params0, lambda0)
-    _lm_prior_args(prior, stiffness, B)
-    lib = _lib.lib()
-    right, fg_max = int(bool(right_hand)), float(fg_max)
-    with _on(dev):
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
-        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
-        params, cost0, cost = f32(B, 26), f32(B), f32(B)
-        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
-        stream = _stream()
-        for it in range(iters + 1):
-            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
-                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
-            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
-            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
-                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
-                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
-            solve = int(it < iters)
-            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
-                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
-                                            _ptr(cost0), stream), "shr_pose_lm_step")
-    return params, cost0, cost
-
+    return sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand, pixel_to_model, fg_max,
+                             max_dist, iters, lambda0, stiffness, prior, render_weight=0.0)
 
 def _sphere_render_args(max_resid, background, weight, name="weight"):
     max_resid, background, weight = float(max_resid), float(background), float(weight)
@@ -2344,9 +2339,7 @@ def _sphere_render_args(max_resid, background, weight, name="weight"):
         raise RuntimeError("max_resid must be >= 0 (inf: no saturation), not %r" % (max_resid,))
     if not abs(background) < float("inf"):
         raise RuntimeError("background must be finite, not %r" % (background,))
-    if not (weight >= 0.0 and weight < float("inf")):
-        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
-    return max_resid, background, weight
+    return max_resid, background, _weight_arg(weight, name)
 
 
 def sphere_render_normal(observed, view, params, offset, offset_inv, bone, wv, radii, right_hand=True,
@@ -2362,21 +2355,13 @@ def sphere_render_normal(observed, view, params, offset, offset_inv, bone, wv, r
     B, V, H, W, J, p2m, _ = _sphere_icp_args(observed, view, params, offset, offset_inv, bone, wv, radii, pixel_to_model, 0.0)
     max_resid, background, weight = _sphere_render_args(max_resid, background, weight)
     dev = observed.device
-    if accumulate_into is not None:
-        A, g, cost = accumulate_into
-        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
-            _check_input(t, name, torch.float64)
-            if tuple(t.shape) != shape or t.device != dev:
-                raise RuntimeError("accumulate_into's %s must be %s fp64 on observed's device" % (name, shape))
+    into = _accumulate_args(accumulate_into, B, dev, "observed's device")
     lib = _lib.lib()
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
         centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
-        if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = into or _new_normal(B, dev)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
         depth = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
@@ -2400,53 +2385,12 @@ def sphere_icp_render(observed, view, params0, offset, offset_inv, bone, wv, rad
     shr_sphere_render_normal(accumulate = 1) after shr_sphere_icp_normal, on torch's current stream, into buffers allocated
     once before the loop; nothing returns to the host: capturable in a graph.  render_weight = 0 issues no launch of the
     new entry: sphere_icp bit for bit."""
-    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
-                                                    max_dist, "start parameters")
-    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
-    iters = int(iters)
-    if iters < 0:
-        raise RuntimeError("iters must be >= 0")
-    dev = observed.device
-    state, trial = pose_lm_begin(params0, lambda0)
-    _lm_prior_args(prior, stiffness, B)
-    lib = _lib.lib()
-    right, fg_max = int(bool(right_hand)), float(fg_max)
-    with _on(dev):
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
-        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
-        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
-        params, cost0, cost = f32(B, 26), f32(B), f32(B)
-        # (one workspace: the two entries' formulas agree, and each writes it before it reads it)
-        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
-                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
-        stream = _stream()
-        for it in range(iters + 1):
-            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
-                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
-            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
-            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
-                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
-                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
-            if render_weight > 0.0:
-                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
-                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
-                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
-                                                        stream), "shr_sphere_render_normal")
-            solve = int(it < iters)
-            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
-                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
-                                            _ptr(cost0), stream), "shr_pose_lm_step")
-    return params, cost0, cost
-
+    return sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand, pixel_to_model, fg_max,
+                             max_dist, iters, lambda0, stiffness, prior, render_weight, max_resid, background)
 
 def _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max, limits, limit_weight):
     kp_weight, kp_max, limit_weight = float(kp_weight), float(kp_max), float(limit_weight)
-    if not (kp_weight >= 0.0 and kp_weight < float("inf")):
-        raise RuntimeError("kp_weight must be finite and >= 0, not %r" % (kp_weight,))
-    if not (limit_weight >= 0.0 and limit_weight < float("inf")):
-        raise RuntimeError("limit_weight must be finite and >= 0, not %r" % (limit_weight,))
+    kp_weight, limit_weight = _weight_arg(kp_weight, "kp_weight"), _weight_arg(limit_weight, "limit_weight")
     if not kp_max >= 0.0:
         raise RuntimeError("kp_max must be >= 0 (inf: no saturation), not %r" % (kp_max,))
     if confidence is not None and keypoints is None:
@@ -2490,21 +2434,13 @@ def sphere_prior_normal(view, params, offset, offset_inv, bone, wv, right_hand=T
         raise RuntimeError("every tensor must be on the parameters' device")
     kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
                                                                        limits, limit_weight)
-    if accumulate_into is not None:
-        A, g, cost = accumulate_into
-        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
-            _check_input(t, name, torch.float64)
-            if tuple(t.shape) != shape or t.device != dev:
-                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    into = _accumulate_args(accumulate_into, B, dev)
     lib = _lib.lib()
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
         centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
-        if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = into or _new_normal(B, dev)
         count = torch.empty((B, 2), dtype=torch.int32, device=dev)
         moments = torch.empty((B, J, 12), dtype=torch.float64, device=dev)
         _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(params), _ptr(keypoints),
@@ -2517,9 +2453,7 @@ def sphere_prior_normal(view, params, offset, offset_inv, bone, wv, right_hand=T
 def _sphere_collision_args(J, dev, pairs, weight, name="weight"):
     """(pair_a, pair_b, pair_min, K, weight): pairs = (a [K] int32, b [K] int32, m [K] fp32) on `dev`, or None (K = 0).
     hand_model.collision_table validates the table where it is built; the entry skips a bad pair."""
-    weight = float(weight)
-    if not (weight >= 0.0 and weight < float("inf")):
-        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
+    weight = _weight_arg(weight, name)
     if pairs is None:
         return None, None, None, 0, weight
     try:
@@ -2554,19 +2488,11 @@ def sphere_collision_normal(params, offset, offset_inv, bone, wv, right_hand=Tru
     if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
         raise RuntimeError("every tensor must be on the parameters' device")
     pa, pb, pm, K, weight = _sphere_collision_args(J, dev, pairs, weight)
-    if accumulate_into is not None:
-        A, g, cost = accumulate_into
-        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
-            _check_input(t, name, torch.float64)
-            if tuple(t.shape) != shape or t.device != dev:
-                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    into = _accumulate_args(accumulate_into, B, dev)
     lib = _lib.lib()
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
-        if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = into or _new_normal(B, dev)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         penetration = torch.empty((B, K), dtype=torch.float64, device=dev)
         _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pa), _ptr(pb), _ptr(pm), weight, B, J, K,
@@ -2579,10 +2505,7 @@ def sphere_collision_normal(params, offset, offset_inv, bone, wv, right_hand=Tru
 def _pose_vae_args(J, dev, blob, weight, latent_weight, name="weight"):
     """(blob, weight, latent_weight) of the pose-VAE term: the blob of pose_vae.pack_fit_weights on `dev`."""
     weight, latent_weight = float(weight), float(latent_weight)
-    if not (weight >= 0.0 and weight < float("inf")):
-        raise RuntimeError("%s must be finite and >= 0, not %r" % (name, weight))
-    if not (latent_weight >= 0.0 and latent_weight < float("inf")):
-        raise RuntimeError("latent_weight must be finite and >= 0, not %r" % (latent_weight,))
+    weight, latent_weight = _weight_arg(weight, name), _weight_arg(latent_weight, "latent_weight")
     if J != 41:
         raise RuntimeError("the pose-VAE term is built for the hand's 41 spheres, not %d" % J)
     _check_input(blob, "the pose-VAE blob")
@@ -2619,19 +2542,11 @@ def pose_vae_normal(params, offset, offset_inv, bone, wv, right_hand, blob, weig
     if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
         raise RuntimeError("every tensor must be on the parameters' device")
     blob, weight, latent_weight = _pose_vae_args(J, dev, blob, weight, latent_weight)
-    if accumulate_into is not None:
-        A, g, cost = accumulate_into
-        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
-            _check_input(t, name, torch.float64)
-            if tuple(t.shape) != shape or t.device != dev:
-                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    into = _accumulate_args(accumulate_into, B, dev)
     lib = _lib.lib()
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
-        if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = into or _new_normal(B, dev)
         residual = torch.empty((B, 123), dtype=torch.float64, device=dev)
         latent = torch.empty((B, 32), dtype=torch.float64, device=dev)
         relu_mask = torch.empty((B, 32), dtype=torch.int32, device=dev)
@@ -2639,6 +2554,111 @@ def pose_vae_normal(params, offset, offset_inv, bone, wv, right_hand, blob, weig
                                            int(accumulate_into is not None), _ptr(A), _ptr(g), _ptr(cost), _ptr(residual),
                                            _ptr(latent), _ptr(relu_mask), None, _stream()), "shr_pose_vae_normal")
     return A, g, cost, residual, latent, relu_mask
+
+
+class _FrameTerms:
+    """One evaluation of the per-frame terms of the sphere fit at a trial pose, for the loops (sphere_icp_priors and through
+    it sphere_icp and sphere_icp_render, the sequence loops, sphere_icp_calibrate).  The constructor checks the terms'
+    arguments in the loops' order and decides which terms carry a weight; allocate() makes, once, the buffers every evaluation
+    writes -- kp, jac, centres, A, g, cost_data, the row counters and the image terms' shared workspace --; evaluate() issues
+    shr_pose_keypoints_jacobian -> shr_view_vertices_fwd -> the data term (shr_sphere_icp_normal, or with group_size
+    shr_sphere_icp_radii_normal) -> render -> keypoints and limits -> collision -> pose-VAE, each later term with
+    accumulate = 1 and none for a term without a weight.  Afterwards A, g and cost_data hold the frame's equations."""
+
+    def __init__(self, observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand, pixel_to_model, fg_max, max_dist,
+                 render_weight=0.0, max_resid=float("inf"), background=100.0, keypoints=None, confidence=None, kp_weight=0.0,
+                 kp_max=float("inf"), limits=None, limit_weight=0.0, collision=None, collision_weight=0.0, pose_prior=None,
+                 group_size=None):
+        if group_size is None:
+            B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii,
+                                                            pixel_to_model, max_dist, "start parameters")
+            self.N = self.G = None
+        else:                                                  # radii [G,J]: the start of the groups' tables
+            B, V, H, W, J, self.N, self.G, p2m, max_dist = _sphere_radii_args(
+                observed, view, params0, offset, offset_inv, bone, wv, radii, group_size, pixel_to_model, max_dist,
+                "start parameters")
+        self.max_resid, self.background, self.render_weight = _sphere_render_args(max_resid, background, render_weight,
+                                                                                  "render_weight")
+        self.dev = dev = observed.device
+        self.kp_weight, self.kp_max, self.limit_weight, self.lower, self.upper = _sphere_prior_args(
+            B, V, J, dev, keypoints, confidence, kp_weight, kp_max, limits, limit_weight)
+        self.priors = (keypoints is not None and self.kp_weight > 0.0) or (self.lower is not None and self.limit_weight > 0.0)
+        self.pairs = _sphere_collision_args(J, dev, collision, collision_weight, "collision_weight")
+        self.collide = self.pairs[3] > 0 and self.pairs[4] > 0.0
+        self.vae = _pose_prior_args(J, dev, pose_prior)
+        self.dims, self.p2m, self.fg_max, self.max_dist = (B, V, J, W, H), p2m, float(fg_max), max_dist
+        self.right = int(bool(right_hand))
+        self.tables = (offset, offset_inv, bone, wv)
+        self.observed, self.view, self.radii, self.keypoints, self.confidence = observed, view, radii, keypoints, confidence
+
+    def allocate(self):
+        """The evaluation's buffers (call under _on(self.dev))."""
+        B, V, J, W, H = self.dims
+        lib, dev = _lib.lib(), self.dev
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        rows = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)    # noqa: E731
+        self.kp, self.jac, self.centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
+        self.A, self.g, self.cost_data = _new_normal(B, dev)
+        self.count = rows(B)
+        if self.G is not None:
+            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+            self.C, self.R, self.gs = f64(B, 26, J), f64(self.G, J, J), f64(self.G, J)
+            ws_bytes = lib.shr_sphere_icp_radii_normal_workspace_bytes(B, V, J, W, H)
+        else:
+            ws_bytes = lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H)
+        if self.render_weight > 0.0:
+            # (one workspace: the two entries' formulas agree, and each writes it before it reads it)
+            ws_bytes = max(ws_bytes, lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H))
+            self.model_rows = rows(B)
+        if self.priors:
+            self.prior_rows = rows(B, 2)
+        if self.collide:
+            self.pair_rows = rows(B)
+        self.ws = torch.empty((max(16, ws_bytes),), dtype=torch.uint8, device=dev)
+
+    def evaluate(self, trial, stream, radii=None):
+        """The frame's terms at trial [B,26]; radii: the trial tables [G,J] of a fit with group_size."""
+        B, V, J, W, H = self.dims
+        lib = _lib.lib()
+        offset, offset_inv, bone, wv = self.tables
+        observed, view, kp, jac, centres = self.observed, self.view, self.kp, self.jac, self.centres
+        A, g, cost_data = self.A, self.g, self.cost_data
+        _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
+                                                   self.right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
+        _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
+        if self.G is None:
+            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(self.radii), _ptr(view), _ptr(jac), B, V, J, W,
+                                                 H, *self.p2m, self.fg_max, self.max_dist, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                 _ptr(self.count), None, None, None, _ptr(self.ws), stream),
+                       "shr_sphere_icp_normal")
+        else:
+            _lib.check(lib.shr_sphere_icp_radii_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
+                                                       W, H, self.N, *self.p2m, self.fg_max, self.max_dist, _ptr(A), _ptr(g),
+                                                       _ptr(cost_data), _ptr(self.count), _ptr(self.C), _ptr(self.R),
+                                                       _ptr(self.gs), None, None, None, _ptr(self.ws), stream),
+                       "shr_sphere_icp_radii_normal")
+        if self.render_weight > 0.0:
+            _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(self.radii), _ptr(view), _ptr(jac), B, V, J,
+                                                    W, H, *self.p2m, self.fg_max, self.background, self.max_resid,
+                                                    self.render_weight, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                    _ptr(self.model_rows), None, None, None, _ptr(self.ws), stream),
+                       "shr_sphere_render_normal")
+        if self.priors:
+            _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(self.keypoints),
+                                                   _ptr(self.confidence), self.kp_weight, self.kp_max, _ptr(self.lower),
+                                                   _ptr(self.upper), self.limit_weight, B, V, J, 1, _ptr(A), _ptr(g),
+                                                   _ptr(cost_data), _ptr(self.prior_rows), None, None, stream),
+                       "shr_sphere_prior_normal")
+        if self.collide:                                       # (kp: the trial's keypoints in the MODEL frame)
+            pair_a, pair_b, pair_min, K, collision_weight = self.pairs
+            _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
+                                                       collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
+                                                       _ptr(self.pair_rows), None, None, stream), "shr_sphere_collision_normal")
+        if self.vae is not None:
+            blob, weight, latent_weight = self.vae
+            _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(blob), blob.shape[0], weight, latent_weight, B, J, 1,
+                                               _ptr(A), _ptr(g), _ptr(cost_data), None, None, None, None, stream),
+                       "shr_pose_vae_normal")
 
 
 def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand=True,
@@ -2661,67 +2681,27 @@ def sphere_icp_priors(observed, view, params0, offset, offset_inv, bone, wv, rad
     pose_prior = (blob, weight, latent_weight), the pose-VAE prior (pose_vae_normal) with weight > 0, adds
     weight (sum r^2 + latent_weight sum mu^2): shr_pose_vae_normal (accumulate = 1) after the collision entry in every
     evaluation.  With pose_prior = None or weight = 0 no launch of it is issued: the loop without the argument, bit for bit."""
-    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
-                                                    max_dist, "start parameters")
-    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
-    dev = observed.device
-    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
-                                                                       limits, limit_weight)
-    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
-    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
-                                                                           "collision_weight")
-    collide = K > 0 and collision_weight > 0.0
-    vae = _pose_prior_args(J, dev, pose_prior)
+    terms = _FrameTerms(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand, pixel_to_model, fg_max, max_dist,
+                        render_weight, max_resid, background, keypoints, confidence, kp_weight, kp_max, limits, limit_weight,
+                        collision, collision_weight, pose_prior)
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
+    B, dev = terms.dims[0], terms.dev
     state, trial = pose_lm_begin(params0, lambda0)
     _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
-    right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
-        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
-        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
-        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
-        params, cost0, cost = f32(B, 26), f32(B), f32(B)
-        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
-                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
+        terms.allocate()
+        params, cost0, cost = (torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((B, 26), (B,), (B,)))
         stream = _stream()
         for it in range(iters + 1):
-            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
-                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
-            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
-            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
-                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
-                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
-            if render_weight > 0.0:
-                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
-                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
-                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
-                                                        stream), "shr_sphere_render_normal")
-            if priors:
-                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
-                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
-                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
-            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
-                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
-                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
-            if vae is not None:
-                _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(vae[0]), vae[0].shape[0], vae[1], vae[2], B, J, 1,
-                                                   _ptr(A), _ptr(g), _ptr(cost_data), None, None, None, None, stream),
-                           "shr_pose_vae_normal")
+            terms.evaluate(trial, stream)
             solve = int(it < iters)
-            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(A), _ptr(g), _ptr(cost_data), _ptr(trial), _ptr(prior),
-                                            _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params), _ptr(cost),
-                                            _ptr(cost0), stream), "shr_pose_lm_step")
+            _lib.check(lib.shr_pose_lm_step(_ptr(state), _ptr(terms.A), _ptr(terms.g), _ptr(terms.cost_data), _ptr(trial),
+                                            _ptr(prior), _ptr(stiffness), solve, B, _ptr(trial) if solve else None, _ptr(params),
+                                            _ptr(cost), _ptr(cost0), stream), "shr_pose_lm_step")
     return params, cost0, cost
-
 
 def _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight):
     try:
@@ -2731,8 +2711,7 @@ def _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight
     if T < 1 or B % T != 0:
         raise RuntimeError("seq_len must be >= 1 and divide the %d frames of the batch, not %r" % (B, seq_len))
     temporal_weight, ts_max = float(temporal_weight), float(ts_max)
-    if not (temporal_weight >= 0.0 and temporal_weight < float("inf")):
-        raise RuntimeError("temporal_weight must be finite and >= 0, not %r" % (temporal_weight,))
+    temporal_weight = _weight_arg(temporal_weight, "temporal_weight")
     if not ts_max >= 0.0:
         raise RuntimeError("ts_max must be >= 0 (inf: no saturation), not %r" % (ts_max,))
     if frame_weight is not None:
@@ -2758,19 +2737,11 @@ def sphere_temporal_normal(params, offset, offset_inv, bone, wv, seq_len, right_
     if any(t.device != dev for t in (offset, offset_inv, bone, wv)):
         raise RuntimeError("every tensor must be on the parameters' device")
     T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
-    if accumulate_into is not None:
-        A, g, cost = accumulate_into
-        for t, name, shape in ((A, "A", (B, 26, 26)), (g, "g", (B, 26)), (cost, "cost", (B,))):
-            _check_input(t, name, torch.float64)
-            if tuple(t.shape) != shape or t.device != dev:
-                raise RuntimeError("accumulate_into's %s must be %s fp64 on the parameters' device" % (name, shape))
+    into = _accumulate_args(accumulate_into, B, dev)
     lib = _lib.lib()
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
-        if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+        A, g, cost = into or _new_normal(B, dev)
         E = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T, J,
@@ -2872,8 +2843,7 @@ def sphere_icp_sequence(observed, view, params0, offset, offset_inv, bone, wv, r
 
 def _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight):
     accel_weight, acc_max = float(accel_weight), float(acc_max)
-    if not (accel_weight >= 0.0 and accel_weight < float("inf")):
-        raise RuntimeError("accel_weight must be finite and >= 0, not %r" % (accel_weight,))
+    accel_weight = _weight_arg(accel_weight, "accel_weight")
     if not acc_max >= 0.0:
         raise RuntimeError("acc_max must be >= 0 (inf: no saturation), not %r" % (acc_max,))
     if triple_weight is not None:
@@ -2913,9 +2883,7 @@ def sphere_accel_normal(params, offset, offset_inv, bone, wv, seq_len, right_han
     with _on(dev):
         kp, jac = pose_keypoints_jacobian(params, offset, offset_inv, bone, wv, right_hand)
         if accumulate_into is None:
-            A = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
-            g = torch.empty((B, 26), dtype=torch.float64, device=dev)
-            cost = torch.empty((B,), dtype=torch.float64, device=dev)
+            A, g, cost = _new_normal(B, dev)
         if E is None:
             E = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
         F = torch.empty((B, 26, 26), dtype=torch.float64, device=dev)
@@ -3100,17 +3068,10 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
     shr_sphere_accel_normal follows the first-difference entry and the step is shr_pose_lm_seq2_begin / _step's.
     window_prior = (Lambda, eta, offset, point) of pose_window_marginalize (None: no prior, no launch): the carried prior's
     entry shr_pose_window_prior_normal (accumulate = 1) follows shr_sphere_accel_normal in every evaluation."""
-    B, V, H, W, J, p2m, max_dist = _sphere_icp_args(observed, view, params0, offset, offset_inv, bone, wv, radii, pixel_to_model,
-                                                    max_dist, "start parameters")
-    max_resid, background, render_weight = _sphere_render_args(max_resid, background, render_weight, "render_weight")
-    dev = observed.device
-    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
-                                                                       limits, limit_weight)
-    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
-    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
-                                                                           "collision_weight")
-    collide = K > 0 and collision_weight > 0.0
-    vae = _pose_prior_args(J, dev, pose_prior)
+    terms = _FrameTerms(observed, view, params0, offset, offset_inv, bone, wv, radii, right_hand, pixel_to_model, fg_max, max_dist,
+                        render_weight, max_resid, background, keypoints, confidence, kp_weight, kp_max, limits, limit_weight,
+                        collision, collision_weight, pose_prior)
+    (B, _, J, _, _), dev = terms.dims, terms.dev
     T, temporal_weight, ts_max = _sphere_temporal_args(B, dev, seq_len, temporal_weight, ts_max, frame_weight)
     temporal = T > 1 and temporal_weight > 0.0
     accel_weight, acc_max = _sphere_accel_args(B, dev, accel_weight, acc_max, triple_weight)
@@ -3123,50 +3084,21 @@ def _sphere_sequence_loop(observed, view, params0, offset, offset_inv, bone, wv,
     state, trial = (pose_lm_seq2_begin if accel else pose_lm_seq_begin)(params0, T, lambda0)
     _lm_prior_args(prior, stiffness, B)
     lib = _lib.lib()
-    right, fg_max = int(bool(right_hand)), float(fg_max)
     S = B // T
     with _on(dev):
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
-        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
+        terms.allocate()
+        kp, jac, A, g, cost_data = terms.kp, terms.jac, terms.A, terms.g, terms.cost_data
         E = torch.zeros((B, 26, 26), dtype=torch.float64, device=dev)       # (stays zero without a term between frames)
         F = f64(B, 26, 26) if accel else None
-        model_rows = torch.empty((B,), dtype=torch.int32, device=dev)
-        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
         temporal_rows = torch.empty((B,), dtype=torch.int32, device=dev) if temporal else None
         accel_rows = torch.empty((B,), dtype=torch.int32, device=dev) if accel else None
         params, cost0, cost = f32(B, 26), f32(S), f32(S)
-        ws = torch.empty((max(16, lib.shr_sphere_icp_normal_workspace_bytes(B, V, J, W, H),
-                              lib.shr_sphere_render_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
         seq_ws = f64(max(1, (lib.shr_pose_lm_seq2_workspace_bytes if accel else lib.shr_pose_lm_seq_workspace_bytes)(B) // 8))
         stream = _stream()
         for it in range(iters + 1):
-            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
-                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
-            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
-            _lib.check(lib.shr_sphere_icp_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J, W, H,
-                                                 *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data), _ptr(count), None,
-                                                 None, None, _ptr(ws), stream), "shr_sphere_icp_normal")
-            if render_weight > 0.0:
-                _lib.check(lib.shr_sphere_render_normal(_ptr(observed), _ptr(centres), _ptr(radii), _ptr(view), _ptr(jac), B, V, J,
-                                                        W, H, *p2m, fg_max, background, max_resid, render_weight, 1, _ptr(A),
-                                                        _ptr(g), _ptr(cost_data), _ptr(model_rows), None, None, None, _ptr(ws),
-                                                        stream), "shr_sphere_render_normal")
-            if priors:
-                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
-                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
-                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
-            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
-                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
-                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
-            if vae is not None:
-                _lib.check(lib.shr_pose_vae_normal(_ptr(kp), _ptr(jac), _ptr(vae[0]), vae[0].shape[0], vae[1], vae[2], B, J, 1,
-                                                   _ptr(A), _ptr(g), _ptr(cost_data), None, None, None, None, stream),
-                           "shr_pose_vae_normal")
+            terms.evaluate(trial, stream)
             if temporal:
                 _lib.check(lib.shr_sphere_temporal_normal(_ptr(kp), _ptr(jac), _ptr(frame_weight), temporal_weight, ts_max, B, T,
                                                           J, 1, _ptr(A), _ptr(g), _ptr(E), _ptr(cost_data), _ptr(temporal_rows),
@@ -3372,7 +3304,7 @@ def sphere_icp_radii_normal(observed, view, params, offset, offset_inv, bone, wv
         centres = torch.empty((B, V, J, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), _stream()), "shr_view_vertices_fwd")
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        A, g, cost, C, R, gs, moments = f64(B, 26, 26), f64(B, 26), f64(B), f64(B, 26, J), f64(G, J, J), f64(G, J), f64(B, J, 16)
+        (A, g, cost), C, R, gs, moments = _new_normal(B, dev), f64(B, 26, J), f64(G, J, J), f64(G, J), f64(B, J, 16)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         dist = torch.empty((B, V, H, W), dtype=torch.float32, device=dev) if want_maps else None
         owner = torch.empty((B, V, H, W), dtype=torch.int32, device=dev) if want_maps else None
@@ -3399,15 +3331,10 @@ def sphere_icp_calibrate(observed, view, params0, offset, offset_inv, bone, wv, 
     and add to A, g and the cost only) -> shr_pose_lm_shared_step, on torch's current stream, into buffers allocated once
     before the loop; nothing returns to the host: capturable in a graph.  The collision table is NOT rebuilt from the trial
     radii.  iters = 0 returns the starts and cost = cost0."""
-    B, V, H, W, J, N, G, p2m, max_dist = _sphere_radii_args(observed, view, params0, offset, offset_inv, bone, wv, radii0,
-                                                            group_size, pixel_to_model, max_dist, "start parameters")
-    dev = observed.device
-    kp_weight, kp_max, limit_weight, lower, upper = _sphere_prior_args(B, V, J, dev, keypoints, confidence, kp_weight, kp_max,
-                                                                       limits, limit_weight)
-    priors = (keypoints is not None and kp_weight > 0.0) or (lower is not None and limit_weight > 0.0)
-    pair_a, pair_b, pair_min, K, collision_weight = _sphere_collision_args(J, dev, collision, collision_weight,
-                                                                           "collision_weight")
-    collide = K > 0 and collision_weight > 0.0
+    terms = _FrameTerms(observed, view, params0, offset, offset_inv, bone, wv, radii0, right_hand, pixel_to_model, fg_max,
+                        max_dist, keypoints=keypoints, confidence=confidence, kp_weight=kp_weight, kp_max=kp_max, limits=limits,
+                        limit_weight=limit_weight, collision=collision, collision_weight=collision_weight, group_size=group_size)
+    (B, _, J, _, _), N, G, dev = terms.dims, terms.N, terms.G, terms.dev
     iters = int(iters)
     if iters < 0:
         raise RuntimeError("iters must be >= 0")
@@ -3420,41 +3347,19 @@ def sphere_icp_calibrate(observed, view, params0, offset, offset_inv, bone, wv, 
             raise RuntimeError("%s must be %s on observed's device" % (name, list(shape)))
     state, trial, trial_shape = pose_lm_shared_begin(params0, radii0, N, lambda0)
     lib = _lib.lib()
-    right, fg_max = int(bool(right_hand)), float(fg_max)
     with _on(dev):
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
-        kp, jac, centres = f32(B, J, 4), f32(B, 3 * J, 26), f32(B, V, J, 4)
-        A, g, cost_data, count = f64(B, 26, 26), f64(B, 26), f64(B), torch.empty((B,), dtype=torch.int32, device=dev)
-        C, R, gs = f64(B, 26, J), f64(G, J, J), f64(G, J)
-        prior_rows = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        pair_rows = torch.empty((B,), dtype=torch.int32, device=dev) if collide else None
+        terms.allocate()
         params, radii, cost0, cost = f32(B, 26), f32(G, J), f32(G), f32(G)
-        ws = torch.empty((max(16, lib.shr_sphere_icp_radii_normal_workspace_bytes(B, V, J, W, H)),), dtype=torch.uint8, device=dev)
         lm_ws = torch.empty((max(1, lib.shr_pose_lm_shared_workspace_bytes(B, G, J) // 8),), dtype=torch.float64, device=dev)
         stream = _stream()
         for it in range(iters + 1):
-            _lib.check(lib.shr_pose_keypoints_jacobian(_ptr(trial), B, _ptr(offset), _ptr(offset_inv), J, _ptr(bone), _ptr(wv),
-                                                       right, _ptr(kp), _ptr(jac), stream), "shr_pose_keypoints_jacobian")
-            _lib.check(lib.shr_view_vertices_fwd(_ptr(kp), _ptr(view), B, V, J, _ptr(centres), stream), "shr_view_vertices_fwd")
-            _lib.check(lib.shr_sphere_icp_radii_normal(_ptr(observed), _ptr(centres), _ptr(trial_shape), _ptr(view), _ptr(jac), B,
-                                                       V, J, W, H, N, *p2m, fg_max, max_dist, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                       _ptr(count), _ptr(C), _ptr(R), _ptr(gs), None, None, None, _ptr(ws),
-                                                       stream), "shr_sphere_icp_radii_normal")
-            if priors:
-                _lib.check(lib.shr_sphere_prior_normal(_ptr(centres), _ptr(view), _ptr(jac), _ptr(trial), _ptr(keypoints),
-                                                       _ptr(confidence), kp_weight, kp_max, _ptr(lower), _ptr(upper),
-                                                       limit_weight, B, V, J, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                       _ptr(prior_rows), None, None, stream), "shr_sphere_prior_normal")
-            if collide:                                        # (kp: the trial's keypoints in the MODEL frame)
-                _lib.check(lib.shr_sphere_collision_normal(_ptr(kp), _ptr(jac), _ptr(pair_a), _ptr(pair_b), _ptr(pair_min),
-                                                           collision_weight, B, J, K, 1, _ptr(A), _ptr(g), _ptr(cost_data),
-                                                           _ptr(pair_rows), None, None, stream), "shr_sphere_collision_normal")
+            terms.evaluate(trial, stream, trial_shape)
             solve = int(it < iters)
             _lib.check(lib.shr_pose_lm_shared_step(
-                _ptr(state), _ptr(A), _ptr(g), _ptr(C), _ptr(R), _ptr(gs), _ptr(cost_data), _ptr(trial), _ptr(trial_shape),
-                _ptr(prior), _ptr(stiffness), _ptr(shape_prior), _ptr(shape_stiffness), solve, B, N, J,
-                _ptr(trial) if solve else None, _ptr(trial_shape) if solve else None, _ptr(params), _ptr(radii), _ptr(cost),
+                _ptr(state), _ptr(terms.A), _ptr(terms.g), _ptr(terms.C), _ptr(terms.R), _ptr(terms.gs), _ptr(terms.cost_data),
+                _ptr(trial), _ptr(trial_shape), _ptr(prior), _ptr(stiffness), _ptr(shape_prior), _ptr(shape_stiffness), solve, B,
+                N, J, _ptr(trial) if solve else None, _ptr(trial_shape) if solve else None, _ptr(params), _ptr(radii), _ptr(cost),
                 _ptr(cost0), _ptr(lm_ws), stream), "shr_pose_lm_shared_step")
     return params, radii, cost0, cost
 

@@ -136,8 +136,10 @@ def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
         assert k["vgpr_count"] <= 64 and k["sgpr_count"] <= 106
     assert "43 552" in section
     unit = open(os.path.join(ROOT, "spherehand_amd", "csrc", "sphere_collision.hip")).read()
-    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["common.h"]
-    assert "atomic" not in unit.lower()
+    header = open(os.path.join(ROOT, "spherehand_amd", "csrc", "normal_eq.h")).read()
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["normal_eq.h"]
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', header) == ["common.h"]
+    assert "atomic" not in unit.lower() and "atomic" not in header.lower()
 
 
 def test_collision_table(mesh):

@@ -138,8 +138,9 @@ def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
     assert "24 344" in section and "47 328" in section and "6 128" in section
     inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
                                   open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
-    assert inc("lm_shared.hip") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["common.h"]
-    for unit in ("lm_shared.hip", "lm_state.h", "lm_solve.h"):
+    assert inc("lm_shared.hip") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["normal_eq.h"]
+    assert inc("normal_eq.h") == ["common.h"]
+    for unit in ("lm_shared.hip", "lm_state.h", "lm_solve.h", "normal_eq.h"):
         assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
 
 
@@ -361,7 +362,8 @@ def test_radii_unit_compiles_for_gfx950_without_scratch(tmp_path):
     inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
                                   open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
     assert inc("sphere_icp_radii.hip") == ["sphere_icp_scan.h"] == inc("sphere_icp.hip")
-    for unit in ("sphere_icp_radii.hip", "sphere_icp_scan.h"):
+    assert inc("sphere_icp_scan.h") == ["normal_eq.h"] and inc("normal_eq.h") == ["common.h"]
+    for unit in ("sphere_icp_radii.hip", "sphere_icp_scan.h", "normal_eq.h"):
         assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower().replace("no atomics", "")
 
 

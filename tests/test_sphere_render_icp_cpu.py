@@ -139,7 +139,7 @@ def test_unit_compiles_for_gfx950_without_scratch(tmp_path):
         assert short[0] in section, short[0]
     assert "28 704" in section and "26 112" in section
     unit = open(os.path.join(ROOT, "spherehand_amd", "csrc", "sphere_render_icp.hip")).read()
-    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["common.h"]
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', unit) == ["sphere_icp_scan.h"]
 
 
 def evaluations(mesh):

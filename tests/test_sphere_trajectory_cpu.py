@@ -211,9 +211,10 @@ def test_units_compile_for_gfx950_without_scratch(tmp_path):
     assert "66 816" in section and "33 080" in section
     inc = lambda unit: re.findall(r'#include\s+[<"]([^>"]+)[>"]',                       # noqa: E731
                                   open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read())
-    assert inc("sphere_accel.hip") == ["common.h"] and inc("lm_seq2.hip") == ["lm_band.h"]
-    assert inc("lm_band.h") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["common.h"]
-    for unit in ("sphere_accel.hip", "lm_seq2.hip", "lm_band.h", "lm_state.h", "lm_solve.h"):
+    assert inc("sphere_accel.hip") == ["normal_eq.h"] and inc("lm_seq2.hip") == ["lm_band.h"]
+    assert inc("lm_band.h") == ["lm_state.h"] and inc("lm_state.h") == ["lm_solve.h"] and inc("lm_solve.h") == ["normal_eq.h"]
+    assert inc("normal_eq.h") == ["common.h"]
+    for unit in ("sphere_accel.hip", "lm_seq2.hip", "lm_band.h", "lm_state.h", "lm_solve.h", "normal_eq.h"):
         assert "atomic" not in open(os.path.join(ROOT, "spherehand_amd", "csrc", unit)).read().lower()
 
 
